@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """DLRM-Criteo training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full training step of examples/dlrm_criteo.config (26 tables x dim 16, 204M rows,
 fused sparse Adagrad in backward, bottom/top MLPs, dot interaction, BCE, dense Adam) over one
 synthetic Criteo-shaped batch.  Headline workload: GLOBAL batch 65536, i.e. 65536/N
 per rank (8192 at N = 8 = `batch_size: 8192` of the config) -- strong scaling; at N > 1 the weak
-reading at 8192 per rank is timed as well and reported under `secondary` (`--scaling weak` makes
+reading at 8192 per rank is timed as well under --full and reported under `secondary` (`--scaling weak` makes
 --global-batch the per-rank batch instead).  Inputs are resident in HBM.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the loss, the logits,
+the dense parameters and a fixed sample of embedding rows + optimizer state after the step's update.
+
+Extra objects on the line, only with --full (every other reading runs only there):
   roofline      the north-star quantity: HBM roofline of the pooled embedding forward + backward
                 (gather kernel, the backward index plan, the fused-optimizer reduce kernel):
                 achieved = algorithmic bytes of fwd + bwd / the sum of the launch
@@ -20,6 +24,8 @@ Extra objects on the line:
   e2e           the same step driven through TrainPipeline.progress from pinned HOST batches (H2D of
                 the next batch on a copy stream under the current step): the PCIe-inclusive rate.
   cpu_baseline  the CPU oracle ("port") timed on this host on a bounded sample of the workload.
+  secondary     config 2 (batch 8192), Zipf ids, row-wise Adagrad, the MFMA kernels alone, the other model
+                families, the 1-rank sharded proxy (N = 1); the other scaling regime (N > 1).
 """
 from __future__ import annotations
 
@@ -143,7 +149,16 @@ def parse_args():
     ap.add_argument("--form-trial-steps", type=int, default=50, help="--forms ab: steps of each form's trial (at least --steps)")
     ap.add_argument("--no-spawn", action="store_true",
                     help="--gpus N > 1 outside torch.distributed.run: fail instead of re-launching under it")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also every reading beyond the headline: secondary readings, e2e, per-stage roofline, CPU baseline, "
+                         "sharded proxy (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a few MB)")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_e2e = args.no_secondary = args.no_cpu_baseline = args.no_sharded_proxy = args.no_config_models = True
+        args.secondary_global_batch = 0
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -538,6 +553,44 @@ def pmc_traffic(args, B_local):
     return None, f"no profiles/r*/pmc_traffic.json recorded on library digest {dig[:16]} (kernels changed since the last PMC pass)"
 
 
+DUMP_ROWS = 512  # embedding rows sampled per table for --dump-outputs (+ as many of the last batch's ids)
+
+
+def dump_outputs(out_dir, model, loss, logits, kjt, sharded):
+    """What the last timed step computed, as float32 .npy files: `loss`, `logits` (when the step path returns them), every
+    dense parameter after the optimizer step, and per table the rows the last batch looked up (its first DUMP_ROWS ids)
+    plus DUMP_ROWS rows drawn with a fixed seed, weights and optimizer state after the fused sparse update (one GPU only:
+    a sharded rank holds row shards).  A few MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    if loss.is_cuda:
+        torch.cuda.synchronize()
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+
+    save("loss", loss.reshape(-1))
+    if logits is not None:
+        save("logits", logits.reshape(-1))
+    dense_params = model.dense_parameters() if hasattr(model, "dense_parameters") else ()
+    for i, p in enumerate(dense_params):
+        save(f"dense_param{i:02d}", p)
+    if sharded:
+        return
+    weights, states = model.ebc.table_weights(), model.ebc.table_states()
+    keys, B = kjt.keys(), kjt.values().numel() // max(len(kjt.keys()), 1)
+    vals = kjt.values().view(len(keys), B)  # one id per bag: key-major [keys, batch]
+    for t, name in enumerate(sorted(weights)):
+        w = weights[name]
+        g = torch.Generator().manual_seed(7000 + t)
+        rnd = torch.randint(0, w.shape[0], (DUMP_ROWS,), generator=g)
+        k = name[:-len("_emb")] if name.endswith("_emb") else name
+        seen = vals[keys.index(k), :DUMP_ROWS].cpu() if k in keys else rnd[:0]
+        idx = torch.cat([seen.long(), rnd]).to(w.device)
+        save(f"emb_{name}_weight", w[idx])
+        if name in states:
+            save(f"emb_{name}_state", states[name][idx])
+
+
 def cpu_baseline(seconds: float):
     """CPU oracle train step (oracle/tzrec_oracle.py, kind "port") on a bounded sample:
     per-rank batch 8192, the five 40M-row tables scaled to 4M rows so the host holds them."""
@@ -806,16 +859,19 @@ def main():
     if sharded and not args.no_pipeline:
         train_step = make_train_step(False if (args.no_native_driver or args.forms == "overlapped" or forms_ab) else None)
 
+    last_logits = [None]  # the logits of the latest step_body call (--dump-outputs)
+
     def step_body(dense, kjt, label, next_kjt=None):
         if train_step is not None:
             return train_step.step(dense, kjt, label, next_kjt=next_kjt)
         if not sharded and not args.torch_bce and not args.layerwise_loss:
             # the training forward of a one-label rank model = logits + loss (TrainWrapper.forward, tzrec/models/model.py:271-297):
             # the bottom MLP and the top MLP's tail + loss + their backward run as whole-stack kernels (csrc/mlp_ops.hip)
-            loss, _ = model.forward_loss(dense, kjt, label)
+            loss, logits = model.forward_loss(dense, kjt, label)
         else:
             logits = model(dense, kjt)
             loss = bce_with_logits(logits, label)
+        last_logits[0] = logits if args.dump_outputs else None
         with root_loss():  # the unscaled loss is the root of the backward pass
             loss.backward(gradient=unit_gradient(loss))
         if sharded:
@@ -838,12 +894,15 @@ def main():
         # One hipGraph per distinct batch (inputs already in HBM, nothing is copied per step); all
         # graphs share one memory pool since they never run concurrently.  A step = one replay:
         # forward, backward with the fused sparse optimizer, dense Adam -- nothing is skipped.
-        graphs, pool, losses = [], None, []
+        graphs, pool, losses, graph_logits = [], None, [], []
         del loss  # drop the eager autograd graph before capturing
+        last_logits[0] = None
         for bi in range(nb):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, stream=work_stream):
                 losses.append(step_body(*batches[bi]))
+            graph_logits.append(last_logits[0])  # (None without --dump-outputs)
+            last_logits[0] = None
             pool = g.pool()
             graphs.append(g)
         sync()
@@ -864,6 +923,7 @@ def main():
     def run_step(i, last=False):
         if graphs is not None:
             graphs[i % nb].replay()
+            last_logits[0] = graph_logits[i % nb]
             return losses[i % nb]
         return step_body(*batches[i % nb], next_kjt=None if last else batches[(i + 1) % nb][1])
 
@@ -1006,6 +1066,8 @@ def main():
 
     elapsed, host_elapsed, host_flag_wait, loss = official if official is not None else timed_block(args.steps, first=args.warmup)
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:  # before any other reading touches the model
+        dump_outputs(args.dump_outputs, model, loss, last_logits[0], batches[(args.warmup + args.steps - 1) % nb][1], sharded)
 
     # Secondary reading for N > 1: the OTHER scaling regime on the same model (BASELINE.md quotes the
     # headline both ways: 65 536 per rank = tzrec's per-rank batch_size, and 65 536 global).  Same
@@ -1240,7 +1302,7 @@ def main():
         secondary["sharded_w1_proxy_b8192"] = proxy_child
 
     # inside a captured graph); the kernels and inputs are the ones of the timed region
-    if ebc is not None and not emu:
+    if ebc is not None and not emu and args.full:
         # The three C-ABI calls of the embedding path (pooled forward, backward plan, backward
         # apply) are launched on the batches of the timed region with HIP events recorded right
         # before/after each call on the launching stream.  A GPU-side sleep first lets the host

@@ -91,3 +91,25 @@ def test_bench_refuses_a_world_it_was_not_launched_with(emu_path):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--emulator"], capture_output=True, text=True,
                        timeout=300, env=env, cwd=ROOT)
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)
+
+
+def test_bench_plain_line_and_dumped_outputs(emu_path, tmp_path):
+    """a plain `--gpus 1` run times exactly --steps steps and carries nothing but the headline (the other readings are --full's);
+    --dump-outputs writes the last timed step's outputs as float32 .npy files, the same from run to run with the same arguments."""
+    flags = ("--gpus", "1", "--emulator", "--global-batch", "64", "--steps", "3", "--warmup", "1")
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    for d_dir in dumps:
+        d = _run(*flags, "--dump-outputs", str(d_dir))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["secondary"] is None and not any(k in d for k in ("roofline", "embedding", "e2e", "cpu_baseline"))
+    import numpy as np
+
+    names = sorted(p.name for p in dumps[0].iterdir())
+    assert names == sorted(p.name for p in dumps[1].iterdir())
+    assert {"loss.npy", "logits.npy", "dense_param00.npy"} <= set(names) and any(n.startswith("emb_") for n in names)
+    assert sum((dumps[0] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dumps[0] / n), np.load(dumps[1] / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), n
+    assert np.load(dumps[0] / "logits.npy").shape == (64,)

@@ -18,7 +18,7 @@ from torcheasyrec_amd.rank_model import build_rank_model  # noqa: E402
 from torcheasyrec_amd.sparse import KeyedJaggedTensor, KeyedTensor  # noqa: E402
 
 HERE = os.path.dirname(__file__)
-REF = "/root/reference/examples"
+REF = os.path.join(HERE, "golden", "reference_configs")  # the upstream example configs this test parses, stored verbatim
 
 
 def test_text_format_parser_basics():
@@ -28,7 +28,6 @@ def test_text_format_parser_basics():
     assert m.many("a")[1].one("b") == 2.5 and m.one("f") is True
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_reference_example_configs_parse():
     spec = load_pipeline_spec(open(os.path.join(REF, "dlrm_criteo.config")).read())
     assert spec.model_name == "dlrm" and spec.batch_size == 8192
@@ -192,16 +191,15 @@ def test_multi_tower_din_config_to_training(dev):
     DEEP and a SEQUENCE group, `multi_tower_din`.  Logits against the oracle restatement (pooled
     lookup + per-id rows padded to the batch's longest history + DIN attention + MLPs), then training."""
     emu_heavy(dev)
-    ref_cfg = os.path.join(REF, "multi_tower_din_taobao.config")
-    if os.path.exists(ref_cfg):  # the reference's own example parses into the same structures
-        big = load_pipeline_spec(open(ref_cfg).read())
-        assert big.model_name == "multi_tower_din" and len(big.features) == 19
-        seqf = [f for f in big.features if f.is_sequence]
-        assert [f.name for f in seqf] == ["click_50_seq__adgroup_id", "click_50_seq__cate_id", "click_50_seq__brand"]
-        assert all(f.sequence_length == 100 and f.embedding_dim == 16 for f in seqf)
-        price = next(f for f in big.features if f.name == "price")
-        assert price.is_sparse and price.num_embeddings == 99  # 98 boundaries + 1 (raw_feature.py:50-60)
-        assert [g.group_type for g in big.feature_groups] == ["DEEP", "SEQUENCE"]
+    # the reference's own example parses into the same structures
+    big = load_pipeline_spec(open(os.path.join(REF, "multi_tower_din_taobao.config")).read())
+    assert big.model_name == "multi_tower_din" and len(big.features) == 19
+    seqf = [f for f in big.features if f.is_sequence]
+    assert [f.name for f in seqf] == ["click_50_seq__adgroup_id", "click_50_seq__cate_id", "click_50_seq__brand"]
+    assert all(f.sequence_length == 100 and f.embedding_dim == 16 for f in seqf)
+    price = next(f for f in big.features if f.name == "price")
+    assert price.is_sparse and price.num_embeddings == 99  # 98 boundaries + 1 (raw_feature.py:50-60)
+    assert [g.group_type for g in big.feature_groups] == ["DEEP", "SEQUENCE"]
     spec = load_pipeline_spec(open(os.path.join(HERE, "golden", "din_mini.config")).read())
     torch.manual_seed(0)
     model = build_rank_model(spec, device=dev)
@@ -378,12 +376,10 @@ def test_multi_tower_din_on_jagged_positions_equals_the_padded_model(dev):
 def test_mmoe_with_zch_config_to_training(dev):
     """BASELINE config 5 at the config level: `mmoe {...}` over a group whose user id goes through a
     zero-collision hash (LFU eviction); two task towers, two labels, two losses."""
-    ref_cfg = os.path.join(REF, "mmoe_taobao.config")
-    if os.path.exists(ref_cfg):
-        big = load_pipeline_spec(open(ref_cfg).read())
-        assert big.model_name == "mmoe" and int(big.model.one("num_expert")) == 3
-        assert [str(t.one("tower_name")) for t in big.model.many("task_towers")] == ["ctr", "cvr"]
-        assert big.label_fields == ["clk", "buy"]
+    big = load_pipeline_spec(open(os.path.join(REF, "mmoe_taobao.config")).read())
+    assert big.model_name == "mmoe" and int(big.model.one("num_expert")) == 3
+    assert [str(t.one("tower_name")) for t in big.model.many("task_towers")] == ["ctr", "cvr"]
+    assert big.label_fields == ["clk", "buy"]
     spec = load_pipeline_spec(open(os.path.join(HERE, "golden", "mmoe_mini.config")).read())
     torch.manual_seed(0)
     model = build_rank_model(spec, device=dev)
