@@ -56,6 +56,28 @@ extern "C" {
 #define TZR_OPT_ACCUMULATE 3      /* no update: the summed gradient of every touched row is
                                      written to TzrTable.m (dense float [rows, dim]); used for
                                      replicated (data_parallel) tables before the all-reduce  */
+/* The norm-based and partial row-wise kinds (fbgemm split-TBE optimizer templates [upstream]).  Per touched
+ * row, on g = the row's summed (clipped) gradient, w = its weights before the update (fp32), lr = *d_lr,
+ * c1 = 1 - beta1^t and c2 = 1 - beta2^t from d_adam, wd = weight_decay, |.| = the L2 norm over the
+ * row's D columns (a column-wise shard: its own columns):
+ *   PARTIAL_ROWWISE_ADAM: v = b2 v + (1-b2) mean_d(g^2) (one scalar), m = b1 m + (1-b1) g,
+ *                         w -= lr ((m/c1) / (sqrt(v/c2) + eps) + wd w)
+ *   LAMB:                 m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2,
+ *                         u = (m/c1) / (sqrt(v/c2) + eps) + wd w, r = |w| / |u|, w -= lr r u
+ *   PARTIAL_ROWWISE_LAMB: v as PARTIAL_ROWWISE_ADAM, m, u, r and w as LAMB
+ *   LARS_SGD:             lambda = lr eta |w| / (|g| + wd |w|), m = mu m + lambda (g + wd w), w -= m
+ *                         (mu = TzrSparseOptim.beta1, eta = TzrSparseOptim.beta2)
+ * r = 0 when |u| = 0 and lambda = 0 when its denominator is 0: the term each multiplies is 0 exactly then,
+ * so no row turns NaN -- and under the two LAMB kinds a row whose weights are all zero does not move.
+ * Kinds 5-7 need d_adam and are advanced by tzr_sparse_adam_tick like TZR_OPT_ADAM.  State rows:
+ *   5, 7: [m(D) | v | 3 floats of padding], m_stride = D + 4 (float4 aligned, one state row per weight row)
+ *   6:    [m(D) | v(D)], m_stride >= 2 D          8: [m(D)], m_stride >= D
+ * The entry points receive the TzrTable records as a device array and do NOT check m_stride against these rules: the
+ * caller must (the Python layer does, embedding.check_state_stride).                                            */
+#define TZR_OPT_PARTIAL_ROWWISE_ADAM 5
+#define TZR_OPT_LAMB 6
+#define TZR_OPT_PARTIAL_ROWWISE_LAMB 7
+#define TZR_OPT_LARS_SGD 8
 
 #define TZR_WD_NONE 0
 #define TZR_WD_L2 1
@@ -129,9 +151,10 @@ typedef struct TzrSparseOptim {
   float weight_decay;
   float max_gradient;        /* used when gradient_clipping != 0                                */
   int32_t gradient_clipping;
-  float beta1;               /* TZR_OPT_ADAM (protos/optimizer.proto:89-96)                     */
-  float beta2;
-  uint64_t d_adam;           /* TZR_OPT_ADAM: float[4] DEVICE state {step, 1 - beta1^step,
+  float beta1;               /* TZR_OPT_ADAM and kinds 5-7 (protos/optimizer.proto:89-96);
+                                TZR_OPT_LARS_SGD: the momentum mu                               */
+  float beta2;               /* TZR_OPT_LARS_SGD: the trust coefficient eta (fbgemm default 0.001) */
+  uint64_t d_adam;           /* TZR_OPT_ADAM, kinds 5-7: float[4] DEVICE state {step, 1 - beta1^step,
                                 1 - beta2^step, -}, advanced once per training step by
                                 tzr_sparse_adam_tick (graph-replay safe)                        */
 } TzrSparseOptim; /* 48 bytes */

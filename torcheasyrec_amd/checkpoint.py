@@ -56,6 +56,8 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
+from .embedding import TICKING_KINDS
+
 FORMAT_VERSION = 2  # 2: DCP entries under the reference's module paths (DCP_NAMES); "files" checkpoints of format 1 still load
 DCP_NAMES = "reference-2"  # naming scheme of the DCP entries; a checkpoint written under another one is refused by name
 
@@ -292,7 +294,7 @@ def save_checkpoint(checkpoint_dir: str, model: nn.Module, dense_optimizer: Opti
     adam_steps = {}
     for path, col in cols:  # sparse Adam: the step count of every fused optimizer that ticks one
         for key, f in _fused_optimizers(path, col):
-            if getattr(f, "cfg", None) is not None and f.cfg.kind == "adam" and f._adam is not None:
+            if getattr(f, "cfg", None) is not None and f.cfg.kind in TICKING_KINDS and f._adam is not None:
                 adam_steps[key] = float(f._adam[0])
     torch.save({"tables": o_tables, "sparse_lr": None if fo is None else fo.param_groups[0]["lr"], "adam_steps": adam_steps,
                 "dense": dense_optimizer.state_dict() if (dense_optimizer is not None and rank == 0) else None},
@@ -414,7 +416,7 @@ def restore_checkpoint(checkpoint_dir: str, model: nn.Module, dense_optimizer: O
         for key, f in _fused_optimizers(path, col):
             # (older files hold one count per collection: every lane of it gets that one)
             t = saved_steps.get(key, saved_steps.get(path))
-            if t is not None and f.cfg.kind == "adam":
+            if t is not None and f.cfg.kind in TICKING_KINDS:
                 f.set_adam_step(float(t))
     if dense_optimizer is not None and o_files[0].get("dense") is not None:
         dense_optimizer.load_state_dict(o_files[0]["dense"])

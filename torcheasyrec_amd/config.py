@@ -178,7 +178,9 @@ def sparse_optimizer_from_config(opt: Msg) -> SparseOptimizerConfig:
     """create_sparse_optimizer mapping (tzrec/optim/optimizer_builder.py:30-97) for the kinds this
     library fuses; field defaults from protos/optimizer.proto:76-139."""
     table = {"sgd_optimizer": "sgd", "adagrad_optimizer": "adagrad", "rowwise_adagrad_optimizer": "rowwise_adagrad",
-             "adam_optimizer": "adam"}
+             "adam_optimizer": "adam", "partial_rowwise_adam_optimizer": "partial_rowwise_adam",
+             "lamb_optimizer": "lamb", "partial_rowwise_lamb_optimizer": "partial_rowwise_lamb",
+             "lars_sgd_optimizer": "lars_sgd"}
     for key, kind in table.items():
         if opt.has(key):
             m = opt.one(key)
@@ -189,6 +191,7 @@ def sparse_optimizer_from_config(opt: Msg) -> SparseOptimizerConfig:
                 max_gradient=float(m.one("max_gradient", 1.0)),
                 initial_accumulator_value=float(m.one("initial_accumulator_value", 0.0)),
                 beta1=float(m.one("beta1", 0.9)), beta2=float(m.one("beta2", 0.999)),
+                momentum=float(m.one("momentum", 0.9)),
             )
     raise ValueError(f"Unknown optimizer: {[k for k in opt.keys()]}")
 

@@ -79,7 +79,10 @@ def algorithmic_bytes(kjt_values: np.ndarray, B: int, rows: List[int], dim: int 
                       optimizer: str = "adagrad") -> Dict[str, float]:
     """Compulsory HBM bytes of the pooled forward / backward for one batch:
     fwd = 8N + 4FB + 4D*U + 4*sumD*B; bwd adagrad = 4*sumD*B + 8N + 16D*U;
-    bwd rowwise = 4*sumD*B + 8N + (8D+8)*U, with U = distinct (table,row) pairs in the batch."""
+    bwd rowwise = 4*sumD*B + 8N + (8D+8)*U, with U = distinct (table,row) pairs in the batch.
+    The norm kinds (weights and the state they update, read and written once per touched row):
+    bwd lamb = 4*sumD*B + 8N + 24D*U; partial row-wise adam / lamb = 4*sumD*B + 8N + (16D+8)*U;
+    lars_sgd = 4*sumD*B + 8N + 16D*U."""
     F = len(rows)
     N = len(kjt_values)
     U = 0
@@ -91,6 +94,12 @@ def algorithmic_bytes(kjt_values: np.ndarray, B: int, rows: List[int], dim: int 
         bwd = 4 * sumD * B + 8 * N + 16 * dim * U
     elif optimizer == "rowwise_adagrad":
         bwd = 4 * sumD * B + 8 * N + (8 * dim + 8) * U
+    elif optimizer == "lamb":
+        bwd = 4 * sumD * B + 8 * N + 24 * dim * U
+    elif optimizer in ("partial_rowwise_adam", "partial_rowwise_lamb"):
+        bwd = 4 * sumD * B + 8 * N + (16 * dim + 8) * U
+    elif optimizer == "lars_sgd":
+        bwd = 4 * sumD * B + 8 * N + 16 * dim * U
     else:
         bwd = 4 * sumD * B + 8 * N + 8 * dim * U
     return {"N": N, "U": U, "fwd": float(fwd), "bwd": float(bwd)}

@@ -16,6 +16,16 @@ struct BwdOpt {
   const float* adam;  // {step, 1 - beta1^step, 1 - beta2^step}
 };
 
+// Compile-time optimizer families of the row update (the FAM template parameter below): the code each family compiles to
+// holds only its own kinds' arithmetic.
+#define BWD_FAM_LEGACY 0  // SGD, Adagrad, row-wise Adagrad, accumulate (the code that was there before Adam)
+#define BWD_FAM_ADAM 1    // TZR_OPT_ADAM
+#define BWD_FAM_NORM 2    // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS-SGD: row norms / a row's second moment
+
+inline bool bwd_norm_kind(int kind) { return kind >= TZR_OPT_PARTIAL_ROWWISE_ADAM && kind <= TZR_OPT_LARS_SGD; }
+// the kinds that read the step state d_adam (ticked by tzr_sparse_adam_tick)
+inline bool bwd_step_kind(int kind) { return kind == TZR_OPT_ADAM || (bwd_norm_kind(kind) && kind != TZR_OPT_LARS_SGD); }
+
 // Gradient sources of one lookup (key -> table), resolved once per workgroup when the table is
 // read by a single key (the common case).
 // (scalar fields, no arrays: a runtime-indexed array in this struct lands in scratch memory and
@@ -95,20 +105,85 @@ __device__ __forceinline__ float bwd_group_sum(float v, int lg, int lane_in_grou
   return s;
 }
 
+__device__ __forceinline__ float bwd_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// The row update of BWD_FAM_NORM (formulas: include/tzrec_hip.h at TZR_OPT_PARTIAL_ROWWISE_ADAM).  `m4` = the row's m
+// chunk (bwd_load_state), g already clipped.  All 64 lanes call: the row norms and the partial row-wise second moment are
+// sums over the row's `lg` lanes (inactive lanes add 0); the partial row-wise v is read and written by the group's first
+// lane.  opt.kind is uniform across the kernel.
+__device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const BwdOpt& opt, float lr, int64_t row, int c,
+                                                   float4 g, float4 w4, float4 m4, bool active, int lg, int lane_in_group,
+                                                   int lane) {
+  const int kind = opt.kind;
+  float* const mp = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c;
+  const float wd = opt.wd;
+  if (kind == TZR_OPT_LARS_SGD) {
+    const float wn = sqrtf(bwd_group_sum(active ? bwd_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
+    const float gn = sqrtf(bwd_group_sum(active ? bwd_dot4(g, g) : 0.f, lg, lane_in_group, lane));
+    const float den = gn + wd * wn;
+    const float lam = den > 0.f ? lr * opt.beta2 * wn / den : 0.f;  // beta2 = eta
+    const float mu = opt.beta1;
+    if (active) {
+      m4.x = mu * m4.x + lam * (g.x + wd * w4.x); m4.y = mu * m4.y + lam * (g.y + wd * w4.y);
+      m4.z = mu * m4.z + lam * (g.z + wd * w4.z); m4.w = mu * m4.w + lam * (g.w + wd * w4.w);
+      tzr_st4(mp, m4);
+      w4.x -= m4.x; w4.y -= m4.y; w4.z -= m4.z; w4.w -= m4.w;
+      tzr_stw4(reinterpret_cast<void*>(tb.w), tb.w_dtype, row * (int64_t)tb.w_stride + 4 * c, w4);
+    }
+    return;
+  }
+  const float b1 = opt.beta1, b2 = opt.beta2;
+  const float c1 = opt.adam[1], c2 = opt.adam[2];
+  m4.x = b1 * m4.x + (1.0f - b1) * g.x; m4.y = b1 * m4.y + (1.0f - b1) * g.y;
+  m4.z = b1 * m4.z + (1.0f - b1) * g.z; m4.w = b1 * m4.w + (1.0f - b1) * g.w;
+  float4 v4;
+  float* const vrow = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + tb.dim;  // the partial row-wise v
+  float vnew = 0.f;
+  if (kind == TZR_OPT_LAMB) {
+    v4 = active ? tzr_ld4(mp + tb.dim) : tzr_zero4();
+    v4.x = b2 * v4.x + (1.0f - b2) * g.x * g.x; v4.y = b2 * v4.y + (1.0f - b2) * g.y * g.y;
+    v4.z = b2 * v4.z + (1.0f - b2) * g.z * g.z; v4.w = b2 * v4.w + (1.0f - b2) * g.w * g.w;
+  } else {  // partial row-wise: one v per row, the mean of g^2 over the row's columns
+    const float ss = bwd_group_sum(active ? bwd_dot4(g, g) : 0.f, lg, lane_in_group, lane);
+    float vold = (active && lane_in_group == 0) ? *vrow : 0.f;
+    vold = __shfl(vold, lane - lane_in_group, 64);
+    vnew = b2 * vold + (1.0f - b2) * (ss / (float)tb.dim);
+    v4 = make_float4(vnew, vnew, vnew, vnew);
+  }
+  float4 u;
+  u.x = (m4.x / c1) / (sqrtf(v4.x / c2) + opt.eps) + wd * w4.x;
+  u.y = (m4.y / c1) / (sqrtf(v4.y / c2) + opt.eps) + wd * w4.y;
+  u.z = (m4.z / c1) / (sqrtf(v4.z / c2) + opt.eps) + wd * w4.z;
+  u.w = (m4.w / c1) / (sqrtf(v4.w / c2) + opt.eps) + wd * w4.w;
+  float step = lr;
+  if (kind != TZR_OPT_PARTIAL_ROWWISE_ADAM) {  // the two LAMB kinds: trust ratio |w| / |u|
+    const float wn = sqrtf(bwd_group_sum(active ? bwd_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
+    const float un = sqrtf(bwd_group_sum(active ? bwd_dot4(u, u) : 0.f, lg, lane_in_group, lane));
+    step = un > 0.f ? lr * (wn / un) : 0.f;
+  }
+  if (active) {
+    tzr_st4(mp, m4);
+    if (kind == TZR_OPT_LAMB) tzr_st4(mp + tb.dim, v4);
+    else if (lane_in_group == 0) *vrow = vnew;
+    w4.x -= step * u.x; w4.y -= step * u.y; w4.z -= step * u.z; w4.w -= step * u.w;
+    tzr_stw4(reinterpret_cast<void*>(tb.w), tb.w_dtype, row * (int64_t)tb.w_stride + 4 * c, w4);
+  }
+}
+
 // Prefetch of the elementwise optimizer state of (row, chunk c): issued together with the weight
 // load, before the reduction, so the update itself waits on no memory.
-// (ADAM is a template parameter of everything below: with the Adam arithmetic as one more run-time
+// (The family FAM is a template parameter of everything below: with the Adam arithmetic as one more run-time
 // branch of the row update the reduce kernel needed 99 instead of 78 VGPRs, one wave per SIMD less,
-// and the DLRM-Criteo Adagrad step lost 17 us -- profiles/r01k.  The <false> instantiations are the
-// code that was there before.)
-template <bool ADAM>
+// and the DLRM-Criteo Adagrad step lost 17 us -- profiles/r01k.  The BWD_FAM_LEGACY instantiations are the
+// code that was there before.  Every kind of BWD_FAM_NORM keeps exp_avg / momentum m(D) at the front of its state row.)
+template <int FAM>
 __device__ __forceinline__ float4 bwd_load_state(const TzrTable& tb, const BwdOpt& opt, int64_t row,
                                                  int c, bool active) {
-  if (active && (ADAM || opt.kind == TZR_OPT_ADAGRAD))  // Adam: exp_avg
+  if (active && (FAM != BWD_FAM_LEGACY || opt.kind == TZR_OPT_ADAGRAD))  // Adam: exp_avg
     return tzr_ld4(reinterpret_cast<const float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c);
   // row-wise Adagrad: the row's scalar, fetched by the group's first lane (c == lane in group at every call site)
   // together with the weights -- not after the gradient reduction, where its latency was exposed once per run
-  if (!ADAM && active && c == 0 && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
+  if (FAM == BWD_FAM_LEGACY && active && c == 0 && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
     return make_float4(reinterpret_cast<const float*>(tb.m)[row * (int64_t)tb.m_stride], 0.f, 0.f, 0.f);
   return tzr_zero4();
 }
@@ -117,11 +192,11 @@ __device__ __forceinline__ float4 bwd_load_state(const TzrTable& tb, const BwdOp
 // exists for the lanes it will not use): a load inside `if (active)` is a branch to hipcc and a branch between two loads a
 // wait between them -- the gradient gather, the weights and the state of a tile ran as three dependent round trips
 // (pooled_bwd_direct.hip: "branch-free").  Row-wise Adagrad: all lanes of the group read the row's scalar (one address).
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ float4 bwd_load_state_all(const TzrTable& tb, const BwdOpt& opt, int64_t row, int c) {
-  if (ADAM || opt.kind == TZR_OPT_ADAGRAD)  // (kernel-uniform)
+  if (FAM != BWD_FAM_LEGACY || opt.kind == TZR_OPT_ADAGRAD)  // (kernel-uniform)
     return tzr_ld4(reinterpret_cast<const float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c);
-  if (!ADAM && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
+  if (FAM == BWD_FAM_LEGACY && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
     return make_float4(reinterpret_cast<const float*>(tb.m)[row * (int64_t)tb.m_stride], 0.f, 0.f, 0.f);
   return tzr_zero4();
 }
@@ -129,7 +204,7 @@ __device__ __forceinline__ float4 bwd_load_state_all(const TzrTable& tb, const B
 // ONE update of row `row`, chunk c; `active` lanes hold the summed gradient g, the row's current
 // weights w4 and (elementwise adagrad) state m4.  All 64 lanes of the wave must call (row-wise
 // adagrad reduces in the group).
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& opt, float lr,
                                               int64_t row, int c, float4 g, float4 w4, float4 m4,
                                               bool active, int lg, int lane_in_group, int lane) {
@@ -141,7 +216,11 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
   }
   void* const wbase = reinterpret_cast<void*>(tb.w);
   const int64_t woff = row * (int64_t)tb.w_stride + 4 * c;
-  if constexpr (ADAM) {
+  if constexpr (FAM == BWD_FAM_NORM) {
+    bwd_apply_row_norm(tb, opt, lr, row, c, g, w4, m4, active, lg, lane_in_group, lane);
+    return;
+  }
+  if constexpr (FAM == BWD_FAM_ADAM) {
     // fbgemm split Adam [upstream]: m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2,
     // w -= lr * ((m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps) + wd * w); only touched rows move
     if (active) {
@@ -269,14 +348,14 @@ __device__ __forceinline__ float4 bwd_shfl4(float4 v, int src) {
 
 // One row update done by a whole wave acting as a single group (lanes >= D/4 idle): used by the
 // stitching steps, where runs are few.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_apply_row_wave(const TzrTable& tb, const BwdOpt& opt, float lr,
                                                    uint32_t key, float4 g, int lane) {
   const bool on = lane < (tb.dim >> 2);
   float4 w4 = tzr_zero4();
   if (on) w4 = tzr_ldw4(reinterpret_cast<const void*>(tb.w), tb.w_dtype, (int64_t)key * tb.w_stride + 4 * lane);
-  const float4 m4 = bwd_load_state<ADAM>(tb, opt, (int64_t)key, lane, on);
-  bwd_apply_row<ADAM>(tb, opt, lr, (int64_t)key, lane, g, w4, m4, on, TZR_WAVE, lane, lane);
+  const float4 m4 = bwd_load_state<FAM>(tb, opt, (int64_t)key, lane, on);
+  bwd_apply_row<FAM>(tb, opt, lr, (int64_t)key, lane, g, w4, m4, on, TZR_WAVE, lane, lane);
 }
 
 // Boundary record of a unit: written by wave 0 of its workgroup, read by whichever workgroup
@@ -318,7 +397,7 @@ struct BwdUnitLds {
 // (The predicates of the loads are known up front: equal keys are adjacent, so "this lookup belongs to the run inherited
 // from the range before" is `key == leadkey` for the whole range.)  The planned apply keeps its own copy: it is compiled
 // for exactly 7 waves per SIMD (71 of 72 VGPRs) and any re-arrangement of its source moved live ranges into scratch.
-template <bool ADAM, int NT, int FK = 0, class Tail>
+template <int FAM, int NT, int FK = 0, class Tail>
 __device__ __forceinline__ void bwd_reduce_unit(
     const TzrTable& tb, const TzrFeature* __restrict__ feats, const int32_t* __restrict__ feat_by_order,
     const uint32_t* __restrict__ bag_of, const int64_t* __restrict__ offsets, const float* __restrict__ weights,
@@ -386,7 +465,7 @@ __device__ __forceinline__ void bwd_reduce_unit(
         g[u] = bwd_lookup_grad(feats, tb, feat_by_order, sG, one, single, grad_mode, offsets, weights, bag_of, B, uniform,
                                sS[idc], c);
         w4[u] = tzr_ldw4(reinterpret_cast<const void*>(tb.w), tb.w_dtype, (int64_t)kc * tb.w_stride + 4 * c);
-        m4[u] = bwd_load_state_all<ADAM>(tb, opt, (int64_t)kc, c);
+        m4[u] = bwd_load_state_all<FAM>(tb, opt, (int64_t)kc, c);
       }
       vmask |= valid ? 1u << u : 0u;
       tmask |= tl ? 1u << u : 0u;
@@ -420,7 +499,7 @@ __device__ __forceinline__ void bwd_reduce_unit(
         lead_open = false;
       }
       if constexpr (FK != 0) bwd_apply_row_fast<FK>(tb, opt, lr, (int64_t)key[u], c, gg, w4[u], m4[u], do_apply, lg, c, lane);
-      else bwd_apply_row<ADAM>(tb, opt, lr, (int64_t)key[u], c, gg, w4[u], m4[u], do_apply, lg, c, lane);
+      else bwd_apply_row<FAM>(tb, opt, lr, (int64_t)key[u], c, gg, w4[u], m4[u], do_apply, lg, c, lane);
       // carry out of the tile: its last valid lookup, if that run goes on
       const int nv = min(gw, r1 - (t0 + u * gw));
       const int last = (nv - 1) * lg;
@@ -498,12 +577,12 @@ __device__ __forceinline__ void bwd_reduce_unit(
       const bool act = on && q < nc;
       cw[q] = tzr_zero4();
       if (act) cw[q] = tzr_ldw4(reinterpret_cast<const void*>(tb.w), tb.w_dtype, (int64_t)ck[q] * tb.w_stride + 4 * lane);
-      cm[q] = bwd_load_state<ADAM>(tb, opt, (int64_t)(q < nc ? ck[q] : 0u), lane, act);
+      cm[q] = bwd_load_state<FAM>(tb, opt, (int64_t)(q < nc ? ck[q] : 0u), lane, act);
     }
 #pragma unroll
     for (int q = 0; q < BWD_WAVES - 1; ++q) {
       if (q >= nc) break;  // wave-uniform
-      bwd_apply_row<ADAM>(tb, opt, lr, (int64_t)ck[q], lane, cs[q], cw[q], cm[q], on, TZR_WAVE, lane, lane);
+      bwd_apply_row<FAM>(tb, opt, lr, (int64_t)ck[q], lane, cs[q], cw[q], cm[q], on, TZR_WAVE, lane, lane);
     }
   }
   if (open) cf |= BWD_TRAIL;

@@ -130,7 +130,7 @@ __device__ __forceinline__ void bwd_stage_unit(const BwdPlan& P, const BwdChunkD
 
 // Runs crossing unit boundaries: the unit holding the run's first lookup adds the leading pieces
 // of the following units (in order) and updates the row.  One wave.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_stitch_unit(const TzrTable& tb, const BwdOpt& opt, float lr,
                                                 int max_dim, const BwdPlan& P, int chunk,
                                                 int last_chunk, int lane) {
@@ -171,7 +171,7 @@ __device__ __forceinline__ void bwd_stitch_unit(const TzrTable& tb, const BwdOpt
       }
     }
   }
-  bwd_apply_row_wave<ADAM>(tb, opt, lr, key, sum, lane);
+  bwd_apply_row_wave<FAM>(tb, opt, lr, key, sum, lane);
 }
 
 // Called by wave 0 of every unit once its boundary record is published.  Runs can only cross unit
@@ -181,7 +181,7 @@ __device__ __forceinline__ void bwd_stitch_unit(const TzrTable& tb, const BwdOpt
 // not depend on the arrival order; buckets are stitched in parallel, and no second launch is
 // needed (round 1: tzr_bwd_stitch_kernel, 10 us at B = 65536).  A unit touches at most two such
 // buckets: the one its first lookup and the one its last lookup falls in.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_arrive_and_stitch(const TzrTable& tb, const BwdOpt& opt, float lr,
                                                       int max_dim, const BwdPlan& P,
                                                       const BwdChunkDesc& cd, uint32_t b_first,
@@ -214,13 +214,13 @@ __device__ __forceinline__ void bwd_arrive_and_stitch(const TzrTable& tb, const 
       while (open) {
         const int k = __ffsll(open) - 1;
         open &= open - 1;
-        bwd_stitch_unit<ADAM>(tb, opt, lr, max_dim, P, cb + k, u1 + 1, lane);
+        bwd_stitch_unit<FAM>(tb, opt, lr, max_dim, P, cb + k, u1 + 1, lane);
       }
     }
   }
 }
 
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_reduce_body(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
@@ -287,7 +287,7 @@ __device__ __forceinline__ void bwd_reduce_body(
     float4 w4 = tzr_zero4();
     if (do_apply)  // issued before the scan: overlaps the gradient gathers
       w4 = tzr_ldw4(reinterpret_cast<const void*>(tb.w), tb.w_dtype, (int64_t)key * tb.w_stride + 4 * c);
-    const float4 m4 = bwd_load_state<ADAM>(tb, opt, (int64_t)key, c, do_apply);
+    const float4 m4 = bwd_load_state<FAM>(tb, opt, (int64_t)key, c, do_apply);
     // segmented inclusive scan over the lane groups of the tile (keys are sorted, so equality at
     // distance d implies one run in between)
     for (int d = 1; d < gw; d <<= 1) {
@@ -305,7 +305,7 @@ __device__ __forceinline__ void bwd_reduce_body(
       flags |= BWD_LEAD;
       lead_open = false;
     }
-    bwd_apply_row<ADAM>(tb, opt, lr, (int64_t)key, c, g, w4, m4, do_apply, lg, c, lane);
+    bwd_apply_row<FAM>(tb, opt, lr, (int64_t)key, c, g, w4, m4, do_apply, lg, c, lane);
     // carry out of the tile: its last valid lookup, if that run goes on
     const int nv = min(gw, r1 - t0);
     const int last = (nv - 1) * lg;
@@ -344,7 +344,7 @@ __device__ __forceinline__ void bwd_reduce_body(
       if (open) {
         osum = tzr_add4(osum, lv);
         if (!(f & BWD_LEAD_WHOLE)) {
-          bwd_apply_row_wave<ADAM>(tb, opt, lr, okey, osum, lane);
+          bwd_apply_row_wave<FAM>(tb, opt, lr, okey, osum, lane);
           open = false;
         }
       } else {  // still inside the run inherited from the previous chunk
@@ -370,16 +370,16 @@ __device__ __forceinline__ void bwd_reduce_body(
     tzr_publish_u32(P.clkey + blockIdx.x, sK[1]);
     tzr_publish_u32(P.ctkey + blockIdx.x, okey);
   }
-  bwd_arrive_and_stitch<ADAM>(tb, opt, lr, max_dim, P, cd, bwd_bucket(sK[1], cd.mult),
+  bwd_arrive_and_stitch<FAM>(tb, opt, lr, max_dim, P, cd, bwd_bucket(sK[1], cd.mult),
                               bwd_bucket(sK[n], cd.mult), lane);
 }
 
-template <bool ADAM>
+template <int FAM>
 __global__ __launch_bounds__(BWD_THREADS) void tzr_bwd_reduce_kernel(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
     int grad_mode, BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {
-  bwd_reduce_body<ADAM>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
+  bwd_reduce_body<FAM>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
 }
 
 // the same body compiled for 7 / 8 waves per SIMD (72 / 64 VGPRs); tzr_tune("bwd_apply_waves") = 6 | 7 | 8, 0 = 7
@@ -387,13 +387,13 @@ __global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(7) void tzr_bwd_reduc
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
     int grad_mode, BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {
-  bwd_reduce_body<false>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
+  bwd_reduce_body<BWD_FAM_LEGACY>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
 }
 __global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(8) void tzr_bwd_reduce_w8_kernel(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
     int grad_mode, BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {
-  bwd_reduce_body<false>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
+  bwd_reduce_body<BWD_FAM_LEGACY>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
 }
 int g_tzr_bwd_apply_waves = 0;
 
@@ -449,14 +449,14 @@ __device__ __forceinline__ void bwd_reduce_body_fast(
       tzr_publish_u32(P.clkey + blockIdx.x, U.sK[1]);
       tzr_publish_u32(P.ctkey + blockIdx.x, okey);
     }
-    bwd_arrive_and_stitch<false>(tb, opt, lr, max_dim, P, cd, bwd_bucket(U.sK[1], cd.mult), bwd_bucket(U.sK[n], cd.mult), lane);
+    bwd_arrive_and_stitch<BWD_FAM_LEGACY>(tb, opt, lr, max_dim, P, cd, bwd_bucket(U.sK[1], cd.mult), bwd_bucket(U.sK[n], cd.mult), lane);
     BWD_PROF_MARK(4);  // unit boundaries done: the workgroup ends
   };
   const bool fast = tb.w_dtype == TZR_DT_F32 && (grad_mode == 1 || (tb.n_feats == 1 && ft_dst == 1));  // (workgroup-uniform)
   if (fast)
-    bwd_reduce_unit<false, NT, FK>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
+    bwd_reduce_unit<BWD_FAM_LEGACY, NT, FK>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
   else
-    bwd_reduce_unit<false, 1, 0>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
+    bwd_reduce_unit<BWD_FAM_LEGACY, 1, 0>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
 }
 
 #define TZR_REDUCE_FAST_KERNEL(NAME, FK_, NT_, ATTR)                                                                  \
@@ -492,9 +492,10 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
   if (!h_optim->d_lr) return TZR_ERR_INVALID;
   if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD &&
       h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD && h_optim->kind != TZR_OPT_ACCUMULATE &&
-      h_optim->kind != TZR_OPT_ADAM)
+      h_optim->kind != TZR_OPT_ADAM &&
+      !bwd_norm_kind(h_optim->kind))
     return TZR_ERR_UNSUPPORTED;
-  if (h_optim->kind == TZR_OPT_ADAM && !h_optim->d_adam) return TZR_ERR_INVALID;
+  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
   if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TZR_ERR_WORKSPACE;
   if (n_positions < 0 || n_positions >= (1LL << 32)) return TZR_ERR_UNSUPPORTED;
   BwdPlan P;
@@ -541,9 +542,11 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
       if (two) TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast2_sgd_kernel); else TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_sgd_kernel);
     }
   } else if (opt.kind == TZR_OPT_ADAM) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<true>));  // Adam holds two state rows per lane: no registers for a second tile
+    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ADAM>));  // Adam holds two state rows per lane: no registers for a second tile
+  } else if (bwd_norm_kind(opt.kind)) {
+    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_NORM>));
   } else if (g_tzr_bwd_apply_waves == 6) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<false>));
+    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_LEGACY>));
   } else if (g_tzr_bwd_apply_waves == 8) {
     TZR_REDUCE_LAUNCH(tzr_bwd_reduce_w8_kernel);
   } else {
@@ -561,7 +564,7 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
 // Dense update of replicated tables: lane group <-> row of the concatenated row space; the row's
 // gradient comes from the all-reduced accumulation buffer; rows with an all-zero gradient are
 // skipped (a sparse update never visits them).  Same per-row arithmetic as the sparse path.
-template <bool ADAM>
+template <int FAM>
 __global__ __launch_bounds__(BWD_THREADS) void tzr_dense_rows_update_kernel(
     const TzrTable* __restrict__ tables, int T, const int64_t* __restrict__ row_start,
     int64_t total_rows, float* __restrict__ acc, int dim, BwdOpt opt, int clear) {
@@ -595,8 +598,8 @@ __global__ __launch_bounds__(BWD_THREADS) void tzr_dense_rows_update_kernel(
     const TzrTable tb = tables[t];
     float4 w4 = tzr_zero4();
     if (active) w4 = tzr_ldw4(reinterpret_cast<const void*>(tb.w), tb.w_dtype, row * (int64_t)tb.w_stride + 4 * c);
-    const float4 m4 = bwd_load_state<ADAM>(tb, opt, row, c, active);
-    bwd_apply_row<ADAM>(tb, opt, lr, row, c, g, w4, m4, active, lg, c, lane);
+    const float4 m4 = bwd_load_state<FAM>(tb, opt, row, c, active);
+    bwd_apply_row<FAM>(tb, opt, lr, row, c, g, w4, m4, active, lg, c, lane);
   }
 }
 
@@ -621,9 +624,10 @@ static int dense_rows_update(const TzrTable* d_tables, int n_tables, const int64
   if (!d_tables || n_tables <= 0 || !d_row_start || total_rows < 0 || !h_optim || !h_optim->d_lr ||
       dim <= 0 || (dim & 3) || dim > BWD_MAXDIM)
     return TZR_ERR_INVALID;
-  if (h_optim->kind == TZR_OPT_ADAM && !h_optim->d_adam) return TZR_ERR_INVALID;
+  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
   if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD && h_optim->kind != TZR_OPT_ADAM)
+      h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD && h_optim->kind != TZR_OPT_ADAM &&
+      !bwd_norm_kind(h_optim->kind))
     return TZR_ERR_UNSUPPORTED;
   if (total_rows == 0) return TZR_OK;
   if (!d_acc || (reinterpret_cast<uintptr_t>(d_acc) & 15)) return TZR_ERR_INVALID;
@@ -641,11 +645,15 @@ static int dense_rows_update(const TzrTable* d_tables, int n_tables, const int64
   const int gpb = (TZR_WAVE / (dim >> 2)) * BWD_WAVES;
   const unsigned grid = (unsigned)std::min<int64_t>(4096, (total_rows + gpb - 1) / gpb);
   if (opt.kind == TZR_OPT_ADAM) {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<true>), dim3(grid), dim3(BWD_THREADS), 0,
+    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_ADAM>), dim3(grid), dim3(BWD_THREADS), 0,
+                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
+                       d_acc, dim, opt, clear);
+  } else if (bwd_norm_kind(opt.kind)) {
+    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_NORM>), dim3(grid), dim3(BWD_THREADS), 0,
                        static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
                        d_acc, dim, opt, clear);
   } else {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<false>), dim3(grid), dim3(BWD_THREADS), 0,
+    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_LEGACY>), dim3(grid), dim3(BWD_THREADS), 0,
                        static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
                        d_acc, dim, opt, clear);
   }

@@ -444,7 +444,7 @@ __device__ __forceinline__ uint2 bwd_cells_elem(const uint2* __restrict__ slab, 
 
 // Partial sum of one unit of a split row -> its record; the last of the row's units to arrive adds the records in unit order
 // and updates the row.  Wave 0; `sum` valid in the lanes < dim / 4.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_cells_combine(const BwdCellUnit& u, const BwdCellsView& V, const BwdOpt& opt, float lr,
                                                   int max_dim, float4 sum, uint32_t count, int lane) {
   const int lg = u.tb.dim >> 2;
@@ -479,7 +479,7 @@ __device__ __forceinline__ void bwd_cells_combine(const BwdCellUnit& u, const Bw
       cnt += (uint32_t)__shfl((int)cn, g * lg, TZR_WAVE);
     }
   }
-  if (cnt) bwd_apply_row_wave<ADAM>(u.tb, opt, lr, (uint32_t)u.b0, tot, lane);  // (a row nobody looked up is not touched)
+  if (cnt) bwd_apply_row_wave<FAM>(u.tb, opt, lr, (uint32_t)u.b0, tot, lane);  // (a row nobody looked up is not touched)
 }
 
 // Sum of the gradient rows of the lookups of ONE row held by the cells in LDS (cpre / cbase, n lookups; `row`: only lookups of
@@ -572,7 +572,7 @@ __device__ __forceinline__ float4 bwd_cells_stream_row(
 //
 // bwd_cells_next_piece: advances `cur` over the unit's rows [cur, khi) until a piece is staged -- L.S.pk / ps[0 .. np) hold its
 // lookups in arrival order, returns np > 0 -- or the rows are exhausted (0).  Rows streamed on the way are updated here.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ int bwd_cells_next_piece(
     const BwdCellUnit& u, const BwdCellsView& V, const uint2* __restrict__ slab, const uint32_t* cpre, const uint32_t* cbase,
     int ncell, int n, uint32_t& cur, uint32_t khi, const TzrFeature* __restrict__ feats, const float* __restrict__ weights, int64_t B,
@@ -648,7 +648,7 @@ __device__ __forceinline__ int bwd_cells_next_piece(
       if (end0 - cur <= 1u) {  // one row with more lookups than a unit: streamed
         uint32_t cnt;
         const float4 sum = bwd_cells_stream_row<false>(u, V, slab, cpre, cbase, ncell, n, cur, feats, weights, B, grad_mode, sG, red, sm, &cnt);
-        if (wv == 0 && cnt) bwd_apply_row_wave<ADAM>(tb, opt, lr, cur, sum, lane);
+        if (wv == 0 && cnt) bwd_apply_row_wave<FAM>(tb, opt, lr, cur, sum, lane);
         cur += 1;
         break;
       }
@@ -677,7 +677,7 @@ __device__ __forceinline__ int bwd_cells_bounds(const BwdCellUnit& u, int i0, in
 
 // The ordinary unit from its lookups in registers: sort by (row id, arrival) in LDS, reduction, the split rows' records.  `np`
 // lookups, element r of a lane = arrival position wv * pw + r * 64 + lane (bwd_stage_unit's fused form).
-template <bool ADAM, int FK, int NT, int MAXR>
+template <int FAM, int FK, int NT, int MAXR>
 __device__ __forceinline__ void bwd_cells_sort_reduce(
     const BwdCellUnit& u, const BwdCellsView& V, uint32_t (&kreg)[MAXR], uint32_t (&sreg)[MAXR], uint32_t vmask, uint32_t kmin,
     uint32_t kmax, int np, int ft_dst, const TzrFeature* __restrict__ feats, const float* __restrict__ weights, int64_t B,
@@ -737,22 +737,22 @@ __device__ __forceinline__ void bwd_cells_sort_reduce(
     (void)cf;
     (void)okey;
     (void)osum;
-    if (u.split > 0) bwd_cells_combine<ADAM>(u, V, opt, lr, max_dim, clead, (uint32_t)np, lane);
+    if (u.split > 0) bwd_cells_combine<FAM>(u, V, opt, lr, max_dim, clead, (uint32_t)np, lane);
   };
   if constexpr (FK != 0) {
     const bool fast = tb.w_dtype == TZR_DT_F32 && (grad_mode == 1 || (tb.n_feats == 1 && ft_dst == 1));  // (workgroup-uniform)
     if (fast)
-      bwd_reduce_unit<false, NT, FK>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
+      bwd_reduce_unit<BWD_FAM_LEGACY, NT, FK>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
     else
-      bwd_reduce_unit<false, 1, 0>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
+      bwd_reduce_unit<BWD_FAM_LEGACY, 1, 0>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
   } else {
-    bwd_reduce_unit<ADAM, 1, 0>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
+    bwd_reduce_unit<FAM, 1, 0>(tb, feats, V.feat_by_order, nullptr, nullptr, weights, B, 1, grad_mode, opt, L.U, sG, np, tail);
   }
 }
 
 // Worker workgroups (the last BWD_CELLS_WORKERS of the apply launch's grid): wait until every unit has looked at its size, then
 // take the units that did not fit off the list, piece by piece.  The last worker to finish resets the launch's counters.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_cells_worker(
     const BwdCellsView& V, int n_units, const TzrFeature* __restrict__ feats, const float* __restrict__ weights, int64_t B,
     int grad_mode, const BwdOpt& opt, int max_dim, const uint2* __restrict__ slab, const uint16_t* __restrict__ bnd, int ch,
@@ -787,7 +787,7 @@ __device__ __forceinline__ void bwd_cells_worker(
       uint32_t cnt;
       const float4 sum = bwd_cells_stream_row<false>(u, V, slab, cpre, cbase, ncell, n, BWD_SENT, feats, weights, B, grad_mode, sG,
                                                      reinterpret_cast<float*>(&L.S.L), L.S.gstart + 264, &cnt);
-      if (wv == 0) bwd_cells_combine<ADAM>(u, V, opt, lr, max_dim, sum, cnt, lane);
+      if (wv == 0) bwd_cells_combine<FAM>(u, V, opt, lr, max_dim, sum, cnt, lane);
       continue;
     }
     int nb;
@@ -799,7 +799,7 @@ __device__ __forceinline__ void bwd_cells_worker(
     if (khi64 > (uint64_t)tb.rows) khi64 = (uint64_t)tb.rows;
     const uint32_t khi = (uint32_t)khi64;
     for (;;) {
-      const int np = bwd_cells_next_piece<ADAM>(u, V, slab, cpre, cbase, ncell, n, cur, khi, feats, weights, B, grad_mode, opt, lr, L, sG);
+      const int np = bwd_cells_next_piece<FAM>(u, V, slab, cpre, cbase, ncell, n, cur, khi, feats, weights, B, grad_mode, opt, lr, L, sG);
       if (np == 0) break;
       constexpr int kRounds = BWD_UMAX / BWD_THREADS;
       const int pw = bwd_wave_span(np);
@@ -819,7 +819,7 @@ __device__ __forceinline__ void bwd_cells_worker(
         }
       }
       __syncthreads();
-      bwd_cells_sort_reduce<ADAM, 0, 1, kRounds>(u, V, kreg, sreg, vmask, kmin, kmax, np, ft_dst, feats, weights, B, grad_mode, opt, lr,
+      bwd_cells_sort_reduce<FAM, 0, 1, kRounds>(u, V, kreg, sreg, vmask, kmin, kmax, np, ft_dst, feats, weights, B, grad_mode, opt, lr,
                                                  max_dim, L, sG);
       __syncthreads();  // (waves 1.. left the reduction before wave 0's stitch: everyone is here before the next piece's passes)
     }
@@ -834,7 +834,7 @@ __device__ __forceinline__ void bwd_cells_worker(
   }
 }
 
-template <bool ADAM, int FK, int NT>
+template <int FAM, int FK, int NT>
 __device__ __forceinline__ void bwd_cells_apply_body(
     BwdCellsView V, int n_units, const TzrFeature* __restrict__ feats, const float* __restrict__ weights, int64_t B, int grad_mode,
     const BwdGrads& G, const BwdOpt& opt, int max_dim, const uint2* __restrict__ slab, const uint16_t* __restrict__ bnd, int ch) {
@@ -848,7 +848,7 @@ __device__ __forceinline__ void bwd_cells_apply_body(
   if ((int)blockIdx.x >= n_units) {  // (workgroup-uniform; nothing of the unit path below is live here)
     __syncthreads();
 #ifndef CELLS_NO_WORKER  // (timing experiment: the units' code alone; units that do not fit are then simply dropped)
-    bwd_cells_worker<ADAM>(V, n_units, feats, weights, B, grad_mode, opt, max_dim, slab, bnd, ch, L, sG, xcell);
+    bwd_cells_worker<FAM>(V, n_units, feats, weights, B, grad_mode, opt, max_dim, slab, bnd, ch, L, sG, xcell);
 #endif
     return;
   }
@@ -907,23 +907,24 @@ __device__ __forceinline__ void bwd_cells_apply_body(
     }
   }
   CELLS_MARK(2);
-  bwd_cells_sort_reduce<ADAM, FK, NT, kRounds>(u, V, kreg, sreg, vmask, kmin, kmax, n, ft_dst, feats, weights, B, grad_mode, opt, lr,
+  bwd_cells_sort_reduce<FAM, FK, NT, kRounds>(u, V, kreg, sreg, vmask, kmin, kmax, n, ft_dst, feats, weights, B, grad_mode, opt, lr,
                                                max_dim, L, sG);
   CELLS_MARK(8);
 }
 
-#define TZR_CELLS_APPLY_KERNEL(NAME, ADAM_, FK_, ATTR)                                                                         \
+#define TZR_CELLS_APPLY_KERNEL(NAME, FAM_, FK_, ATTR)                                                                         \
   __global__ __launch_bounds__(BWD_THREADS) ATTR void NAME(BwdCellsView V, int n_units, const TzrFeature* __restrict__ feats,  \
                                                           const float* __restrict__ weights, int64_t B, int grad_mode,         \
                                                           BwdGrads G, BwdOpt opt, int max_dim, const uint2* __restrict__ slab, \
                                                           const uint16_t* __restrict__ bnd, int ch) {                          \
-    bwd_cells_apply_body<ADAM_, FK_, 1>(V, n_units, feats, weights, B, grad_mode, G, opt, max_dim, slab, bnd, ch);             \
+    bwd_cells_apply_body<FAM_, FK_, 1>(V, n_units, feats, weights, B, grad_mode, G, opt, max_dim, slab, bnd, ch);             \
   }
-TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_adagrad_kernel, false, TZR_OPT_ADAGRAD, TZR_WAVES_PER_EU(7))
-TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_rowwise_kernel, false, TZR_OPT_ROWWISE_ADAGRAD, TZR_WAVES_PER_EU(7))
-TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_sgd_kernel, false, TZR_OPT_SGD, TZR_WAVES_PER_EU(7))
-TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_general_kernel, false, 0, TZR_WAVES_PER_EU(7))
-TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_adam_kernel, true, 0, )
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_adagrad_kernel, BWD_FAM_LEGACY, TZR_OPT_ADAGRAD, TZR_WAVES_PER_EU(7))
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_rowwise_kernel, BWD_FAM_LEGACY, TZR_OPT_ROWWISE_ADAGRAD, TZR_WAVES_PER_EU(7))
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_sgd_kernel, BWD_FAM_LEGACY, TZR_OPT_SGD, TZR_WAVES_PER_EU(7))
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_general_kernel, BWD_FAM_LEGACY, 0, TZR_WAVES_PER_EU(7))
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_adam_kernel, BWD_FAM_ADAM, 0, )
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_norm_kernel, BWD_FAM_NORM, 0, )  // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS
 
 // ------------------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -1039,9 +1040,10 @@ extern "C" int tzr_pooled_bwd_cells_apply(const TzrTable* d_tables, const TzrFea
     return TZR_ERR_INVALID;
   if (!h_optim->d_lr) return TZR_ERR_INVALID;
   if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD && h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM)
+      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM &&
+      !bwd_norm_kind(h_optim->kind))
     return TZR_ERR_UNSUPPORTED;
-  if (h_optim->kind == TZR_OPT_ADAM && !h_optim->d_adam) return TZR_ERR_INVALID;
+  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
   BwdCellsGeo g;
   BwdCellsView V;
   BwdPlan P;
@@ -1074,6 +1076,8 @@ extern "C" int tzr_pooled_bwd_cells_apply(const TzrTable* d_tables, const TzrFea
   const bool fast_shape = !d_weights && (opt.kind == TZR_OPT_ADAGRAD || opt.kind == TZR_OPT_ROWWISE_ADAGRAD || opt.kind == TZR_OPT_SGD);
   if (opt.kind == TZR_OPT_ADAM) {
     TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_adam_kernel);
+  } else if (bwd_norm_kind(opt.kind)) {
+    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_norm_kernel);
   } else if (!fast_shape) {
     TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_general_kernel);
   } else if (opt.kind == TZR_OPT_ADAGRAD) {

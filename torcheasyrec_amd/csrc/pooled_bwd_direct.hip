@@ -270,7 +270,7 @@ __device__ __forceinline__ uint32_t bwd_direct_gather_waves(const BwdGeo& G, con
 
 // The unit's lookups in LDS in position order -> sorted by row id -> reduced and applied.  `regions`: they lie in the four
 // wave regions of bwd_direct_gather_waves (L.wcnt[w] entries each); else in S.pk / S.ps[0 .. n), n <= BWD_UMAX.
-template <bool ADAM, int NT, int FK = 0>
+template <int FAM, int NT, int FK = 0>
 __device__ __forceinline__ void bwd_direct_unit(const TzrTable& tb, const TzrFeature* __restrict__ feats,
                                                 const BwdSrcArgs& A, const float* __restrict__ weights, int grad_mode,
                                                 const BwdOpt& opt, BwdDirectLds& L, int n, bool regions = false,
@@ -334,11 +334,11 @@ __device__ __forceinline__ void bwd_direct_unit(const TzrTable& tb, const TzrFea
     // the tile loop (pooled_bwd_apply.h: bwd_apply_row_fast); every other unit of the launch the general one
     const TzrFeature* const ft = feats + L.fbo[tb.first_order];
     if (tb.w_dtype == TZR_DT_F32 && !weights && (grad_mode == 1 || (tb.n_feats == 1 && ft->n_dst == 1)))
-      bwd_reduce_unit<ADAM, NT, FK>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
+      bwd_reduce_unit<FAM, NT, FK>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
     else
-      bwd_reduce_unit<ADAM, NT>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
+      bwd_reduce_unit<FAM, NT>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
   } else {
-    bwd_reduce_unit<ADAM, NT>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
+    bwd_reduce_unit<FAM, NT>(tb, feats, L.fbo, nullptr, A.offsets, weights, A.B, A.uniform, grad_mode, opt, L.U, L.sG, n, none);
   }
   __syncthreads();  // wave 0's stitch reads U while the others would already refill S
 }
@@ -408,7 +408,7 @@ __device__ __forceinline__ float4 bwd_direct_row_sum(const BwdGeo& G, const TzrT
 }
 
 // ONE row with more lookups than an LDS unit holds, owned by this workgroup alone: summed over the whole table, applied.
-template <bool ADAM>
+template <int FAM>
 __device__ __forceinline__ void bwd_direct_stream_row(const BwdGeo& G, const TzrTable& tb,
                                                       const TzrFeature* __restrict__ feats, const BwdSrcArgs& A,
                                                       const float* __restrict__ weights, int grad_mode,
@@ -416,7 +416,7 @@ __device__ __forceinline__ void bwd_direct_stream_row(const BwdGeo& G, const Tzr
                                                       BwdDirectLds& L) {
   const float4 sum = bwd_direct_row_sum(G, tb, feats, A, weights, grad_mode, ts, te, row, L);
   if (threadIdx.x < TZR_WAVE)  // (the row update is wave-collective: all 64 lanes of wave 0)
-    bwd_apply_row_wave<ADAM>(tb, opt, *opt.lr, row, sum, (int)threadIdx.x);
+    bwd_apply_row_wave<FAM>(tb, opt, *opt.lr, row, sum, (int)threadIdx.x);
   __syncthreads();
 }
 
@@ -425,7 +425,7 @@ __device__ __forceinline__ uint32_t bwd_direct_sub_start(uint32_t cur, uint64_t 
   return cur + (uint32_t)((((uint64_t)p << 32) + m2 - 1) / m2);
 }
 
-template <bool ADAM, int NT, int FK = 0>
+template <int FAM, int NT, int FK = 0>
 __device__ __forceinline__ void bwd_direct_body(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats, int F, const BwdSrcArgs& A,
     const float* __restrict__ weights, int grad_mode, const BwdGrads& Gr, const BwdOpt& opt, int ch,
@@ -517,7 +517,7 @@ __device__ __forceinline__ void bwd_direct_body(
     float4 tot = tzr_zero4();
     for (uint32_t q = 0; q < P; ++q)
       if (lane < lg) tot = tzr_add4(tot, bwd_consume4(wpart + (size_t)(c0 + q * R + row) * max_dim + 4 * lane));
-    bwd_apply_row_wave<ADAM>(tb, opt, *opt.lr, row, tot, lane);
+    bwd_apply_row_wave<FAM>(tb, opt, *opt.lr, row, tot, lane);
     return;
   }
   // range j of k: rows [(j << 32) / mult, ((j + 1) << 32) / mult), bucket(row) = (row * mult) >> 32 (bwd_bucket_params)
@@ -559,7 +559,7 @@ __device__ __forceinline__ void bwd_direct_body(
     total = bwd_direct_gather_waves(G, tb, A, ts, te, lo, hi, L, &fits, false, nullptr, nullptr, nullptr, true, crow);
   }
   if (total != 0 && fits) {
-    bwd_direct_unit<ADAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)total, true, dbg == 3);
+    bwd_direct_unit<FAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)total, true, dbg == 3);
   } else if (total != 0) {
     __syncthreads();  // (S is reused by the walk below)
     // ---- more lookups than one LDS unit: piece by piece ----
@@ -606,14 +606,14 @@ __device__ __forceinline__ void bwd_direct_body(
         if (p >= 1) {
           const uint32_t end = p >= (uint32_t)BWD_NB ? lim : min(lim, bwd_direct_sub_start(cur, m2, p));
           const uint32_t n = bwd_direct_gather(G, tb, A, ts, te, cur, end, L, has_x, crow);
-          bwd_direct_unit<ADAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)min(n, (uint32_t)BWD_UMAX));
+          bwd_direct_unit<FAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)min(n, (uint32_t)BWD_UMAX));
           cur = end;
           break;
         }
         // the first sub-range alone does not fit
         const uint32_t end0 = min(lim, bwd_direct_sub_start(cur, m2, 1));
         if (end0 - cur <= 1u) {
-          bwd_direct_stream_row<ADAM>(G, tb, feats, A, weights, grad_mode, opt, ts, te, cur, L);
+          bwd_direct_stream_row<FAM>(G, tb, feats, A, weights, grad_mode, opt, ts, te, cur, L);
           cur += 1;
           break;
         }
@@ -641,29 +641,30 @@ __device__ __forceinline__ void bwd_direct_body(
     float4 tot = tzr_zero4();
     for (uint32_t q = 0; q < k; ++q)
       if (lane < lg) tot = tzr_add4(tot, bwd_consume4(wpart + (size_t)(c0 + q) * max_dim + 4 * lane));
-    bwd_apply_row_wave<ADAM>(tb, opt, *opt.lr, crow, tot, lane);
+    bwd_apply_row_wave<FAM>(tb, opt, *opt.lr, crow, tot, lane);
   }
 }
 
 // (wave priorities by residency slot, tzr_gfx950.h: the four workgroups of a CU out of lock step: 36.0 -> 34.5 us at B = 8 192,
 // profiles/r06av; the same in the exact plan's apply: 76.5 -> 79.2 us, in the cells partition: 14.9 -> 15.9 -- not there)
-#define BWD_DIRECT_KERNEL(NAME, ADAM_, WAVES, NT_, FK_)                                                                      \
+#define BWD_DIRECT_KERNEL(NAME, FAM_, WAVES, NT_, FK_)                                                                      \
   __global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(WAVES) void NAME(                                        \
       const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats, int F, BwdSrcArgs A,         \
       const float* __restrict__ weights, int grad_mode, BwdGrads Gr, BwdOpt opt, int ch,                             \
       uint32_t* __restrict__ wcount, float* __restrict__ wpart, int max_dim) {                                       \
     tzr_prio_by_slot(blockIdx.x);                                                                                    \
-    bwd_direct_body<ADAM_, NT_, FK_>(tables, T, feats, F, A, weights, grad_mode, Gr, opt, ch, wcount, wpart, max_dim);    \
+    bwd_direct_body<FAM_, NT_, FK_>(tables, T, feats, F, A, weights, grad_mode, Gr, opt, ch, wcount, wpart, max_dim);    \
   }
 // 4 waves per SIMD (128 VGPRs): 1 024 workgroups resident = the whole grid of an 8 192-per-rank step at once (at 3 waves,
 // 768 slots for ~860 workgroups: 66 vs 39 us).  Two tiles of the reduction in flight per wave; four (at 3 waves) or one
 // measured the same or worse: the kernel is not bound by the reduction's round trips (profiles/r04j, r04k).
-BWD_DIRECT_KERNEL(tzr_bwd_direct_kernel, false, 4, 2, 0)
-BWD_DIRECT_KERNEL(tzr_bwd_direct_adam_kernel, true, 3, 2, 0)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_kernel, BWD_FAM_LEGACY, 4, 2, 0)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_adam_kernel, BWD_FAM_ADAM, 3, 2, 0)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_norm_kernel, BWD_FAM_NORM, 3, 2, 0)  // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS
 // the optimizer kind at compile time: units of fp32 single-key tables take the fast tile loop (tzr_tune "bwd_apply_fast" >= 0)
-BWD_DIRECT_KERNEL(tzr_bwd_direct_adagrad_kernel, false, 4, 2, TZR_OPT_ADAGRAD)
-BWD_DIRECT_KERNEL(tzr_bwd_direct_rowwise_kernel, false, 4, 2, TZR_OPT_ROWWISE_ADAGRAD)
-BWD_DIRECT_KERNEL(tzr_bwd_direct_sgd_kernel, false, 4, 2, TZR_OPT_SGD)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_adagrad_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ADAGRAD)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_rowwise_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ROWWISE_ADAGRAD)
+BWD_DIRECT_KERNEL(tzr_bwd_direct_sgd_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_SGD)
 extern int g_tzr_bwd_apply_fast;  // pooled_bwd_apply.hip
 int g_tzr_bwd_direct_debug = 0;  // tzr_tune("bwd_direct_debug"): timing experiments, see bwd_direct_body
 int g_tzr_bwd_direct_hot = 1;    // tzr_tune("bwd_direct_hot"): hot rows shared among a table's workgroups 1 = when the caller sets TZR_GRAD_HOT_ROWS, 0 = never, 2 = always
@@ -730,9 +731,10 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
   if (max_rows > (1LL << 32) || n_values >= (1LL << 32)) return TZR_ERR_UNSUPPORTED;  // row ids and positions travel as 32-bit
   if (!h_optim->d_lr) return TZR_ERR_INVALID;
   if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD && h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM)
+      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM &&
+      !bwd_norm_kind(h_optim->kind))
     return TZR_ERR_UNSUPPORTED;
-  if (h_optim->kind == TZR_OPT_ADAM && !h_optim->d_adam) return TZR_ERR_INVALID;
+  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
   if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TZR_ERR_WORKSPACE;
   uint32_t* wcount;
   float* wpart;
@@ -777,6 +779,8 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
   if (opt.kind == TZR_OPT_ADAM)
     hipLaunchKernelGGL(tzr_bwd_direct_adam_kernel, dim3(grid), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats,
                        n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
+  else if (bwd_norm_kind(opt.kind))
+    BWD_DIRECT_LAUNCH(tzr_bwd_direct_norm_kernel);
   else if (g_tzr_bwd_apply_fast >= 0 && !d_weights && opt.kind == TZR_OPT_ADAGRAD)
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_adagrad_kernel);
   else if (g_tzr_bwd_apply_fast >= 0 && !d_weights && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)

@@ -57,7 +57,11 @@ class SparseOptimizerConfig:
     protos/optimizer.proto:76-139): ``adagrad_optimizer`` -> kind "adagrad",
     ``rowwise_adagrad_optimizer`` -> "rowwise_adagrad", ``sgd_optimizer`` -> "sgd",
     ``adam_optimizer`` -> "adam" (state [rows, 2 D]: exp_avg | exp_avg_sq; one step counter per
-    optimizer, bias-corrected as fbgemm's split Adam)."""
+    optimizer, bias-corrected as fbgemm's split Adam), ``partial_rowwise_adam_optimizer`` ->
+    "partial_rowwise_adam" and ``partial_rowwise_lamb_optimizer`` -> "partial_rowwise_lamb" (state
+    [rows, D + 4]: exp_avg | one exp_avg_sq | 3 floats of padding), ``lamb_optimizer`` -> "lamb"
+    (state [rows, 2 D] as Adam), ``lars_sgd_optimizer`` -> "lars_sgd" (state [rows, D]: momentum).
+    The Adam-family kinds share Adam's step counter; formulas in include/tzrec_hip.h."""
 
     kind: str = "adagrad"
     lr: float = 0.002
@@ -67,13 +71,44 @@ class SparseOptimizerConfig:
     gradient_clipping: bool = False
     max_gradient: float = 1.0
     initial_accumulator_value: float = 0.0
-    beta1: float = 0.9  # adam
+    beta1: float = 0.9  # adam, partial_rowwise_adam, lamb, partial_rowwise_lamb
     beta2: float = 0.999
+    momentum: float = 0.9  # lars_sgd: mu
+    eta: float = 0.001  # lars_sgd: trust coefficient (fbgemm default [upstream]; tzrec does not expose it)
 
 
 _OPT_KIND = {"sgd": _lib.OPT_SGD, "adagrad": _lib.OPT_ADAGRAD, "rowwise_adagrad": _lib.OPT_ROWWISE_ADAGRAD,
-             "adam": _lib.OPT_ADAM}
+             "adam": _lib.OPT_ADAM, "partial_rowwise_adam": _lib.OPT_PARTIAL_ROWWISE_ADAM, "lamb": _lib.OPT_LAMB,
+             "partial_rowwise_lamb": _lib.OPT_PARTIAL_ROWWISE_LAMB, "lars_sgd": _lib.OPT_LARS_SGD}
 _WD_MODE = {"none": _lib.WD_NONE, "l2": _lib.WD_L2, "decouple": _lib.WD_DECOUPLE}
+# the kinds that read the device step state {step, 1 - b1^step, 1 - b2^step}, advanced once per step (begin_step)
+TICKING_KINDS = frozenset({"adam", "partial_rowwise_adam", "lamb", "partial_rowwise_lamb"})
+
+
+def _state_shape(kind: Optional[str], rows: int, D: int) -> Optional[Tuple[int, int]]:
+    """[rows, width] of the separate fp32 state tensor of the kinds that always have one (include/tzrec_hip.h)"""
+    if kind in ("adam", "lamb"):  # [exp_avg | exp_avg_sq]
+        return (rows, 2 * D)
+    if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):  # [exp_avg | exp_avg_sq | pad(3)]: float4 aligned
+        return (rows, D + 4)
+    if kind == "lars_sgd":  # [momentum]
+        return (rows, D)
+    return None
+
+
+def check_state_stride(kind: Optional[str], D: int, m_stride: int) -> None:
+    """The state row stride a norm kind needs (include/tzrec_hip.h).  The C entry points take the table records as a device
+    array and cannot check it; a stride too small would put one row's state into the next row's."""
+    if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):
+        ok = m_stride >= D + 1 and m_stride % 4 == 0
+    elif kind == "lamb":
+        ok = m_stride >= 2 * D
+    elif kind == "lars_sgd":
+        ok = m_stride >= D
+    else:
+        return
+    if not ok:
+        raise ValueError(f"{kind}: state row stride {m_stride} does not fit a row of dim {D}")
 
 
 class FusedSparseOptimizer:
@@ -98,7 +133,7 @@ class FusedSparseOptimizer:
     def begin_step(self, device: torch.device) -> None:
         """Once per training step, before the step's update kernels: advances Adam's step counter on
         the device (one tiny launch, graph-capturable); nothing for the other optimizers."""
-        if self.cfg.kind == "adam":
+        if self.cfg.kind in TICKING_KINDS:
             _lib.check(_lib.lib().tzr_sparse_adam_tick(_lib.ptr(self.adam_state(device)), self.cfg.beta1, self.cfg.beta2,
                                                        _lib.stream_ptr(device)), "tzr_sparse_adam_tick")
 
@@ -112,8 +147,8 @@ class FusedSparseOptimizer:
         opt.d_lr = _lib.ptr(self.lr_device(device))
         opt.eps, opt.weight_decay, opt.max_gradient = cfg.eps, cfg.weight_decay, cfg.max_gradient
         opt.gradient_clipping = 1 if cfg.gradient_clipping else 0
-        opt.beta1, opt.beta2 = cfg.beta1, cfg.beta2
-        opt.d_adam = _lib.ptr(self.adam_state(device)) if cfg.kind == "adam" else 0
+        opt.beta1, opt.beta2 = (cfg.momentum, cfg.eta) if cfg.kind == "lars_sgd" else (cfg.beta1, cfg.beta2)
+        opt.d_adam = _lib.ptr(self.adam_state(device)) if cfg.kind in TICKING_KINDS else 0
         return opt
 
     @property
@@ -173,7 +208,7 @@ class FusedSparseOptimizer:
                 dst.copy_(st["momentum1"])
         if sd.get("param_groups"):
             self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
-        if sd.get("adam_step") is not None and self.cfg.kind == "adam":
+        if sd.get("adam_step") is not None and self.cfg.kind in TICKING_KINDS:
             self.set_adam_step(float(sd["adam_step"]))
 
     def set_adam_step(self, t: float, device: Optional[torch.device] = None) -> None:
@@ -402,12 +437,17 @@ class EmbeddingBagCollection(nn.Module):
             dt = cfg.data_type.upper()
             if dt not in ("FP32", "FP16"):
                 raise ValueError(f"{cfg.name}: data_type {cfg.data_type!r} not supported (FP32 | FP16)")
-            if dt == "FP16":  # half weights, fp32 state, never interleaved (elements differ in size)
+            shape = _state_shape(kind, rows, D)
+            if shape is not None:  # Adam and the norm kinds: a separate fp32 state tensor, any layout
+                store = torch.empty(rows, D, dtype=torch.float16 if dt == "FP16" else torch.float32, device=self._device)
+                weight = store
+                state = torch.zeros(*shape, dtype=torch.float32, device=self._device)
+            elif dt == "FP16":  # half weights, fp32 state, never interleaved (elements differ in size)
                 store = torch.empty(rows, D, dtype=torch.float16, device=self._device)
                 weight = store
                 state = (torch.full((rows, D), init_m, dtype=torch.float32, device=self._device) if kind == "adagrad"
                          else torch.zeros(rows, dtype=torch.float32, device=self._device) if kind == "rowwise_adagrad"
-                         else torch.zeros(rows, 2 * D, dtype=torch.float32, device=self._device) if kind == "adam" else None)
+                         else None)
             elif kind == "adagrad" and self._row_layout == "interleaved":
                 store = torch.empty(rows, 2 * D, dtype=torch.float32, device=self._device)
                 weight, state = store[:, :D], store[:, D:]
@@ -426,8 +466,6 @@ class EmbeddingBagCollection(nn.Module):
                     state = torch.full((rows, D), init_m, dtype=torch.float32, device=self._device)
                 elif kind == "rowwise_adagrad":
                     state = torch.zeros(rows, dtype=torch.float32, device=self._device)
-                elif kind == "adam":  # [exp_avg | exp_avg_sq]
-                    state = torch.zeros(rows, 2 * D, dtype=torch.float32, device=self._device)
                 else:
                     state = None
             if cfg.init_fn is not None:
@@ -506,6 +544,8 @@ class EmbeddingBagCollection(nn.Module):
             tables[t]["w_stride"] = w.stride(0)
             tables[t]["w_dtype"] = _lib.DT_F16 if w.dtype == torch.float16 else _lib.DT_F32
             tables[t]["m_stride"] = st.stride(0) if st is not None else 0  # row-wise Adagrad: one float per row
+            if st is not None:
+                check_state_stride(kind, cfg.embedding_dim, st.stride(0))
             mine = [i for i, lk in enumerate(self._lookups) if lk.table == t]
             tables[t]["first_order"] = mine[0] if mine else 0
             tables[t]["n_feats"] = len(mine)

@@ -35,6 +35,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 GB = 1 << 30
+_NORM_KINDS = ("partial_rowwise_adam", "lamb", "partial_rowwise_lamb", "lars_sgd")  # their state is priced by _state_bytes_dim
 
 
 class PlannerError(RuntimeError):
@@ -120,7 +121,7 @@ class TableSpec:
     embedding_dim: int
     feature_names: Sequence[str] = ()
     pooling_factor: float = 1.0  # ids per bag
-    optimizer: str = "adagrad"  # adagrad | rowwise_adagrad | sgd
+    optimizer: str = "adagrad"  # adagrad | rowwise_adagrad | sgd | adam | partial_rowwise_adam | lamb | partial_rowwise_lamb | lars_sgd
     bytes_per_element: int = 4
     # storage layout of the collection the plan is for (EmbeddingBagCollection(row_layout=...), default "interleaved"):
     # interleaved fp32 rows are [w(D) | state] with a 2 D row stride -- ALSO for row-wise Adagrad, whose one scalar per
@@ -145,8 +146,12 @@ class EmbeddingEnumerator:
         if t.optimizer == "rowwise_adagrad":
             padded = t.row_layout == "interleaved" and t.bytes_per_element == 4  # (FP16 tables are never interleaved)
             return rows * dim * 4 if padded else rows * 4
-        if t.optimizer == "adam":
+        if t.optimizer in ("adam", "lamb"):
             return rows * dim * 8
+        if t.optimizer in ("partial_rowwise_adam", "partial_rowwise_lamb"):
+            return rows * (dim + 4) * 4
+        if t.optimizer == "lars_sgd":
+            return rows * dim * 4
         return 0
 
     def _state_bytes(self, t: TableSpec, rows: int) -> int:
@@ -218,7 +223,8 @@ class EmbeddingEnumerator:
             d = D // k
             n = ids * W
             piece_b = d * eb
-            piece_rmw = 2 * piece_b + 2 * (d * 4 if t.optimizer == "adagrad" else 4 if t.optimizer == "rowwise_adagrad" else 0)
+            piece_rmw = 2 * piece_b + 2 * (d * 4 if t.optimizer == "adagrad" else 4 if t.optimizer == "rowwise_adagrad"
+                                           else self._state_bytes_dim(t, 1, d) if t.optimizer in _NORM_KINDS else 0)
             wire = (n * (8 + 2 * piece_b) * (W - 1) / W) / top.a2a_bw
             perf = n * piece_b / top.hbm_gather_bw + n * piece_rmw / top.hbm_rmw_bw + wire + 3 * top.collective_latency
             st = t.num_embeddings * piece_b + self._state_bytes_dim(t, t.num_embeddings, d)
