@@ -430,6 +430,19 @@ union BwdCellsLds {
   BwdUnitLds U;
 };
 
+// The scratch words of bwd_cells_stream_row / bwd_cells_next_piece behind the histogram in S.gstart: `sm` starts at
+// S.gstart + BWD_CELLS_SM and takes up to 2 * BWD_WAVES + BWD_WAVES * TZR_WAVE words (one count per lane group; at D < 16 there
+// are more than 64 groups).  That runs past gstart[BWD_NB] into the pre / hb union behind it, which no cells kernel uses: the
+// space is carved out of the two arrays together, checked here.
+#define BWD_CELLS_SM 264  // (behind the 257 histogram words)
+#define BWD_CELLS_SM_WORDS (2 * BWD_WAVES + BWD_WAVES * TZR_WAVE)
+static_assert(BWD_CELLS_SM >= BWD_THREADS + 1, "sm behind the histogram of bwd_cells_next_piece");
+static_assert(offsetof(BwdSortLds, pre) == offsetof(BwdSortLds, gstart) + sizeof(unsigned) * (BWD_NB + 1),
+              "pre / hb directly behind gstart");
+static_assert(offsetof(BwdSortLds, gstart) + sizeof(unsigned) * (BWD_CELLS_SM + BWD_CELLS_SM_WORDS) <= offsetof(BwdSortLds, pk),
+              "sm fits in gstart + pre / hb");
+static_assert(sizeof(BwdRankLds<BWD_NB>) >= 4096, "red: 4 KB in S.L");
+
 // lookup `i` (0 .. n) of a unit whose cells' exclusive counts / slab starts lie in LDS
 __device__ __forceinline__ uint2 bwd_cells_elem(const uint2* __restrict__ slab, const uint32_t* cpre, const uint32_t* cbase,
                                                 int ncell, uint32_t i) {
@@ -486,7 +499,8 @@ __device__ __forceinline__ void bwd_cells_combine(const BwdCellUnit& u, const Bw
 // that row count -- pass BWD_SENT when the cells hold nothing else), in lookup order: lane group q takes lookups q, q + G,
 // q + 2 G, ... in order (UF of them in flight together: their {row, position} pairs first, then their gradient rows), the groups'
 // sums are added in group order -- a function of the ids alone.  All threads call; the result (and the number of lookups) in
-// wave 0, lanes < dim / 4.  `red`: 4 KB of LDS, `sm`: 2 * BWD_WAVES + 64 words.
+// wave 0, lanes < dim / 4.  `red`: 4 KB of LDS (groups * dim floats = BWD_WAVES * 256), `sm`: 2 * BWD_WAVES + groups words,
+// groups = BWD_WAVES * (64 / (dim / 4)): up to 2 * BWD_WAVES + 256 at D = 4 (BWD_CELLS_SM_WORDS).
 // FAST (compile time): the table is fp32-gradient "one key, one buffer" (bwd_reduce_unit's FK != 0 case): the gradient row of
 // lookup position i is fgp + (i - fkb) * fgs -- no descriptor walk, no branch around a load.
 template <bool FAST>
@@ -582,7 +596,7 @@ __device__ __forceinline__ int bwd_cells_next_piece(
   const int wv = threadIdx.x / TZR_WAVE;
   float* const red = reinterpret_cast<float*>(&L.S.L);  // 4 KB (the ranking rows: free outside the sort)
   uint32_t* const hist = L.S.gstart;
-  uint32_t* const sm = L.S.gstart + 264;                // (behind the 257 histogram words)
+  uint32_t* const sm = L.S.gstart + BWD_CELLS_SM;       // (behind the 257 histogram words; BWD_CELLS_SM_WORDS of them)
   constexpr int SB = BWD_THREADS;  // sub-ranges per pass: one per thread
   while (cur < khi) {
     uint32_t lim = khi;
@@ -786,7 +800,7 @@ __device__ __forceinline__ void bwd_cells_worker(
     if (u.split > 0) {  // one slice of ONE row: its sum is the record
       uint32_t cnt;
       const float4 sum = bwd_cells_stream_row<false>(u, V, slab, cpre, cbase, ncell, n, BWD_SENT, feats, weights, B, grad_mode, sG,
-                                                     reinterpret_cast<float*>(&L.S.L), L.S.gstart + 264, &cnt);
+                                                     reinterpret_cast<float*>(&L.S.L), L.S.gstart + BWD_CELLS_SM, &cnt);
       if (wv == 0) bwd_cells_combine<FAM>(u, V, opt, lr, max_dim, sum, cnt, lane);
       continue;
     }
