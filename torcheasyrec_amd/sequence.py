@@ -532,6 +532,7 @@ class _DinTowerFn(torch.autograd.Function):
 
 
 DIN_JAGGED_MAX_LEN = 2048  # (DA_MAXLEN of csrc/din_attention.hip: scores of one sample kept in LDS)
+DIN_JAGGED_MAX_DIM = 256  # (tzr_din_assemble_bwd: one wave holds a row of the query gradient, 4 * TZR_WAVE floats)
 
 
 class DINEncoder(nn.Module):
@@ -558,9 +559,22 @@ class DINEncoder(nn.Module):
     def output_dim(self) -> int:
         return self._sequence_dim
 
+    def jagged_limit(self) -> Optional[str]:
+        """None when `forward_jagged` evaluates this encoder, else the limit of csrc/din_attention.hip it is outside of"""
+        D, H = self._sequence_dim, self.mlp.hidden_units[-1]
+        if not getattr(self.mlp, "_plain", False):
+            return "the attention MLP must be plain Linear + bias + ReLU layers"
+        if D % 4:
+            return f"sequence_dim {D} must be a multiple of 4"
+        if D > DIN_JAGGED_MAX_DIM:
+            return f"sequence_dim {D} must be at most {DIN_JAGGED_MAX_DIM}"
+        if H % 4:
+            return f"the last attention-MLP width {H} must be a multiple of 4"
+        return None
+
     def jagged_capable(self) -> bool:
-        """plain Linear + bias + ReLU layers (the reference's defaults): what `forward_jagged` evaluates"""
-        return bool(getattr(self.mlp, "_plain", False)) and self._sequence_dim % 4 == 0
+        """plain Linear + bias + ReLU layers (the reference's defaults) within the kernels' limits: what `forward_jagged` evaluates"""
+        return self.jagged_limit() is None
 
     def _folded_first_layer(self) -> torch.Tensor:
         """W [q, k, q - k, q * k] = (Wb - Wc) k + Wd (q * k) + (Wa + Wc) q  ->  [Wb - Wc | Wd | Wa + Wc]  ([H, 3 D])"""
@@ -573,8 +587,13 @@ class DINEncoder(nn.Module):
         max_len: positions at index >= max_len inside a sample do not take part (the padded length of the reference's
         `sequence` tensor; `max_seq_length` is applied on top).  Same output and gradients as `forward` on the padded form."""
 
+        limit = self.jagged_limit()
+        if limit is not None:
+            raise ValueError(f"DINEncoder.forward_jagged: {limit} (use the padded form)")
         if self._max_seq_length > 0:
             max_len = min(max_len, self._max_seq_length)
+        if max_len > DIN_JAGGED_MAX_LEN:
+            raise ValueError(f"DINEncoder.forward_jagged: max_len {max_len} must be at most {DIN_JAGGED_MAX_LEN} (use the padded form)")
         if self._query_dim < self._sequence_dim:
             query = nn.functional.pad(query, (0, self._sequence_dim - self._query_dim))
         # the attention MLP runs on Np >= N rows, N rounded up to `row_bucket`: a GEMM library tunes (and TunableOp keys) its
