@@ -849,23 +849,39 @@ int tzr_delta_count(const uint32_t* d_bitmap, int64_t rows, int64_t* d_total, vo
 int tzr_delta_collect(uint32_t* d_bitmap, int64_t rows, int64_t id_base, int clear,
                       int64_t* d_out_ids, int64_t capacity, void* ws, size_t ws_bytes, void* stream);
 
-/* Process-wide knobs; returns TZR_ERR_INVALID for unknown names.
- *   fwd_tile_b          samples per workgroup of the pooled forward (0 = by problem size)
- *   bwd_ch              lookups per chunk of the backward plan: 256 / 512 / 768 / 1024 (0 = by problem size)
- *   bwd_force_prep      1: geometry prologue as its own launch (the > 1024 features path)
- *   ia_bwd_plain        1: the D = 16 dot-interaction backward without its software pipeline (A/B switch)
- *   ia_bwd_wgs          workgroups of that backward (0 = by batch size)
- *   ia_gen_wgs          workgroups of the generalised MFMA backward (D != 16 or 33-64 rows; 0 = the resident set)
- *   ia_fwd_wgs          workgroups of the D = 16 dot-interaction forward (0 = by batch size)
- *   mlp_mfma            -1: tzr_mlp2_* / tzr_mlp_tail use their general LDS-tiled kernels for every shape (0: the MFMA
- *                       kernels of mlp_mfma.hip where the shape is DLRM-Criteo's)
- *   it_fwd_stagger      fused interaction forward: 1 = half of the waves build the next tile's row before the product, half behind it;
- *                       2 / 3 = all before / all behind; 0 = half and half when z is written, all behind when not
- *   wg_debug            phase-skipping bits of tzr_dot_interaction_top_wgrad for timing experiments (wrong results)
- *   it_wgs              persistent workgroups of the fused interaction + first-layer kernels (0 = 256, one per CU)
- *   bwd_one_wg_heavy    1: a heavy bucket of the backward plan is sorted by ONE workgroup instead of one per
+/* Process-wide knobs; returns TZR_ERR_INVALID for unknown names.  Every knob, with its default; "tests only" = a hook that
+ * forces a path, or caps a grid, so that a small input reaches code the library otherwise picks at production sizes.
+ *   fwd_tile_b          0: samples per workgroup of the pooled forward (0 = by problem size)
+ *   fwd_variant         0: pooled forward kernel by shape; 1 = the general kernel only, 2 = the LDS-ids kernel whenever
+ *                       eligible (tests only)
+ *   fwd_plan            1: tzr_pooled_fwd_cells_plan from B = 32 768 up; 0 = never, 2 = at any batch size (tests only)
+ *   bwd_ch              0: lookups per chunk of the backward plan: 256 / 512 / 768 / 1024 (0 = by problem size)
+ *   bwd_force_prep      0; 1: geometry prologue as its own launch (the > 1024 features path; tests only)
+ *   bwd_one_wg_heavy    0; 1: a heavy bucket of the backward plan is sorted by ONE workgroup instead of one per
  *                       1024-lookup tile.  Same plan, slower under heavy skew.  Set it when plans are built on a
- *                       stream other than the one the rest of the step runs on (NOTES.md, "Side-stream plan"). */
+ *                       stream other than the one the rest of the step runs on (NOTES.md, "Side-stream plan").
+ *   bwd_no_fuse_sort    0; 1: every unit of the backward plan is sorted by the sort launch, so that
+ *                       tzr_pooled_bwd_plan_view shows the complete sorted pairs (tests only)
+ *   bwd_direct          0: tzr_pooled_bwd_direct_supported says yes up to 16 384 lookups per table on average;
+ *                       1 = at any size, -1 = never (tests only)
+ *   bwd_direct_ch       0: lookups per workgroup of tzr_pooled_bwd_direct by problem size; 64 .. 1024 = that many (tests only)
+ *   bwd_direct_hot      1: tzr_pooled_bwd_direct shares a hot row among a table's workgroups when the caller sets
+ *                       TZR_GRAD_HOT_ROWS; 0 = never, 2 = always (tests only)
+ *   bwd_direct_debug    0; 5: only the row-split workgroups of tzr_pooled_bwd_direct run (wrong results; tests only)
+ *   ia_bwd_wgs          0: workgroups of the D = 16 dot-interaction backward by batch size (at most 3 072); > 0 = at most
+ *                       that many
+ *   ia_fwd_wgs          0: workgroups of the D = 16 dot-interaction forward by batch size; > 0 = at most that many
+ *   ia_gen_wgs          0: workgroups of the generalised MFMA backward (D != 16 or 33-64 rows) = the resident set; > 0 = at
+ *                       most that many
+ *   it_wgs              0: persistent workgroups of the fused interaction + first-layer kernels = 256, one per CU
+ *   it_fwd_stagger      0: fused interaction forward, half of the waves build the next tile's row before the product and half
+ *                       behind it when z is written, all behind when not; 1 = half and half, 2 / 3 = all before / all behind
+ *   wg_debug            0; phase-skipping bits of tzr_dot_interaction_top_wgrad for timing experiments (wrong results).  Kept:
+ *                       without the run-time guard around its product the kernel's tile loop compiles to a slower schedule
+ *   mlp_mfma            0: the MFMA kernels of mlp_mfma.hip where the shape is DLRM-Criteo's; -1: tzr_mlp2_* / tzr_mlp_tail
+ *                       use their general LDS-tiled kernels for every shape (tests only)
+ *   linear_bwd_wg       0; > 0 caps the workgroups of tzr_linear_bwd_relu (many tiles per workgroup on small inputs; tests only)
+ *   gemm_rows_wg        0; > 0 caps the workgroups of tzr_linear_rows and tzr_linear_rows_wgrad (tests only) */
 int tzr_tune(const char* name, int value);
 
 /* ---- feature interaction ----------------------------------------------------------------- */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The D = 16 dot-interaction backward at the DLRM-Criteo shape (n = 27, B = 65 536) under its tzr_tune knobs: the plain
-kernel vs the software-pipelined one, and the number of workgroups (default: one per 4 samples, capped at 8 192).
+"""The D = 16 dot-interaction forward and backward at the DLRM-Criteo shape (n = 27, B = 65 536) under their tzr_tune knobs:
+the number of workgroups (default: one per 4 samples, capped at 8 192 forward / 3 072 backward).
 
     python scripts/bench_interaction_bwd_variants.py            # on an MI355X"""
 import os
@@ -52,8 +52,7 @@ def main():
         print(f"B={B} forward wgs={wgs or 'auto':>5}: {t:6.1f} us = {by_f / t / 1e6:4.2f} TB/s   same output: {bool(torch.equal(o2, out))}", flush=True)
     L.tzr_tune(b"ia_fwd_wgs", 0)
     ref = None
-    for plain, wgs in ((1, 0), (0, 0), (0, 8192), (0, 2048)):
-        L.tzr_tune(b"ia_bwd_plain", plain)
+    for wgs in (0, 8192, 2048):
         L.tzr_tune(b"ia_bwd_wgs", wgs)
         fb_out = dot_interaction(dense, sparse, D, True, True)
         fb_out.backward(go)
@@ -62,8 +61,7 @@ def main():
         if ref is None:
             ref = g
         t = timed(fb) - t_f
-        print(f"B={B} plain={plain} wgs={wgs or 'auto':>5}: bwd {t:6.1f} us = {by_b / t / 1e6:4.2f} TB/s   same grads: {bool(torch.equal(g, ref))}", flush=True)
-    L.tzr_tune(b"ia_bwd_plain", 0)
+        print(f"B={B} wgs={wgs or 'auto':>5}: bwd {t:6.1f} us = {by_b / t / 1e6:4.2f} TB/s   same grads: {bool(torch.equal(g, ref))}", flush=True)
     L.tzr_tune(b"ia_bwd_wgs", 0)
 
 

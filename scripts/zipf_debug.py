@@ -3,7 +3,7 @@
 B = 65536 (hundreds of heavy buckets, stitch groups sharing record lines), SGD so every row has a
 closed form; every iteration is checked on the device against index_add in fp64.
 
-    python scripts/zipf_debug.py [iterations] [bwd_debug ...]"""
+    python scripts/zipf_debug.py [iterations] [variant ...]      (variants: see run)"""
 import os
 import sys
 os.environ.setdefault("TZR_BWD_PLAN", "exact")  # (these scripts inspect the four-launch plan)
@@ -17,7 +17,7 @@ from torcheasyrec_amd.embedding import EmbeddingBagCollection, EmbeddingBagConfi
 from torcheasyrec_amd.sparse import KeyedJaggedTensor  # noqa: E402
 
 
-def run(iters, dbg, B=65536, seed=0, variant=0):
+def run(iters, B=65536, seed=0, variant=0):
     dev = torch.device("cuda", 0)
     rows = [12973, 11938, 39060, 17295, 7424, 20265, 7122, 2209, 3067956, 590152]
     keys = [f"c{i}" for i in range(len(rows))]
@@ -33,7 +33,7 @@ def run(iters, dbg, B=65536, seed=0, variant=0):
     for it in range(iters):
         if it < 3 or it % 10 == 0:
             torch.cuda.synchronize()
-            print(f"debug {dbg} variant {variant} iter {it} t={time.time() - t0:.1f}s", flush=True)
+            print(f"variant {variant} iter {it} t={time.time() - t0:.1f}s", flush=True)
         ids = np.stack([(np.minimum(rng.zipf(1.05, size=B).astype(np.int64) - 1, r - 1) * 2654435761 + 12345) % r for r in rows])
         kjt = KeyedJaggedTensor(keys, torch.from_numpy(ids.reshape(-1)), torch.ones(len(rows) * B, dtype=torch.int32),
                                 uniform_length=1).to(dev)
@@ -71,7 +71,7 @@ def run(iters, dbg, B=65536, seed=0, variant=0):
                 asc_ok = bool(((sp[1:] > sp[:-1]) | (k[1:] != k[:-1])).all())
                 if not (perm_ok and key_ok and runs == uniq and asc_ok):
                     bad += 1
-                    print(f"debug {dbg} variant {variant} iter {it} PLAN table {f} ({rows[f]} rows): perm {perm_ok} keys {key_ok} "
+                    print(f"variant {variant} iter {it} PLAN table {f} ({rows[f]} rows): perm {perm_ok} keys {key_ok} "
                           f"runs {runs} unique {uniq} ascending {asc_ok}", flush=True)
         for f, w in enumerate(ebc.table_weights().values()):
             # per-row gradient sums without atomics (index_add_ on 40k duplicates of one row takes seconds in
@@ -95,7 +95,7 @@ def run(iters, dbg, B=65536, seed=0, variant=0):
             if not bool((err <= bound).all()) or moved > uniq.numel():
                 bad += 1
                 r = int((err - bound).max(dim=1).values.argmax())
-                print(f"debug {dbg} iter {it} table {f} ({rows[f]} rows): row {int(uniq[r])} err {float(err[r].max()):.3g} "
+                print(f"variant {variant} iter {it} table {f} ({rows[f]} rows): row {int(uniq[r])} err {float(err[r].max()):.3g} "
                       f"lookups of that row {int((idt[f] == uniq[r]).sum())}; rows moved {moved} vs touched {uniq.numel()}", flush=True)
     return bad
 
@@ -103,6 +103,5 @@ def run(iters, dbg, B=65536, seed=0, variant=0):
 if __name__ == "__main__":
     _lib.use_native()
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    for a in sys.argv[2:] or ["0"]:  # "<bwd_debug>[:<variant>]"
-        dbg, variant = (int(x) for x in (a.split(":") + ["0"])[:2])
-        print("debug", dbg, "variant", variant, "failures", run(iters, dbg, variant=variant), "in", iters, "iterations", flush=True)
+    for variant in [int(a) for a in sys.argv[2:]] or [0]:
+        print("variant", variant, "failures", run(iters, variant=variant), "in", iters, "iterations", flush=True)

@@ -6,6 +6,7 @@ import ctypes as C
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -193,3 +194,52 @@ def test_export_segment_reduce_and_adam_argument_checks(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize()
     assert st.cpu().tolist()[:3] == [2.0, 0.75, 0.4375]
+
+
+def test_backward_entry_points_check_the_optimizer(dev):
+    """The optimizer arguments of the four fused-backward entry points: no learning rate -> INVALID, a kind nobody knows ->
+    UNSUPPORTED, a kind that reads the step state without d_adam -> INVALID; TZR_OPT_ACCUMULATE is taken by the three sparse
+    forms and refused by the dense update.  Everything else about each call is valid up to the check BEHIND the optimizer's
+    (no workspace -> WORKSPACE; the dense update: no rows -> OK), so an accepted optimizer shows as that code and nothing is
+    ever launched."""
+    L = _lib.lib()
+    p = _lib.ptr
+    B = 4
+    ht = np.zeros(1, dtype=_lib.TABLE_DT)
+    ht[0]["rows"], ht[0]["dim"], ht[0]["w_stride"], ht[0]["first_order"], ht[0]["n_feats"] = 10, 16, 16, 0, 1
+    hf = np.zeros(1, dtype=_lib.FEATURE_DT)
+    hf[0]["table"], hf[0]["key"], hf[0]["order"], hf[0]["n_dst"] = 0, 0, 0, 1
+    info = (C.c_int64 * 8)()
+    assert L.tzr_bwd_cells_geometry(ht.ctypes.data, 1, hf.ctypes.data, 1, B, 16, None, 0, info) == OK
+    img = np.zeros(int(info[0]), dtype=np.uint8)
+    assert L.tzr_bwd_cells_geometry(ht.ctypes.data, 1, hf.ctypes.data, 1, B, 16, img.ctypes.data, img.nbytes, info) == OK
+    d_geo = _lib.workspace(img.nbytes, dev)
+    tables, feats = _buf(dev, 48, torch.uint8), _buf(dev, 64, torch.uint8)
+    vals, rstart = _buf(dev, B, torch.int64), _buf(dev, 2, torch.int64)
+    grad, lr, adam = _buf(dev, B * 16), _buf(dev, 1), _buf(dev, 4)
+    g = (_lib.TzrDst * 1)()
+    g[0].ptr, g[0].stride = p(grad), 16
+
+    def calls(o):
+        return {
+            "apply": L.tzr_pooled_bwd_apply(p(tables), p(feats), 1, 1, 16, None, None, B, B, B, 1, 0, g, 1, C.byref(o), None, 0, None),
+            "cells": L.tzr_pooled_bwd_cells_apply(p(tables), p(feats), 1, 1, 16, None, B, B, 0, g, 1, C.byref(o), img.ctypes.data, p(d_geo),
+                                                  None, 0, None),
+            "direct": L.tzr_pooled_bwd_direct(p(tables), 1, p(feats), 1, 10, 16, p(vals), None, None, B, B, B, 1, 0, g, 1, C.byref(o), None, 0,
+                                              None),
+            "dense": L.tzr_dense_rows_update(p(tables), 1, p(rstart), 0, None, 16, C.byref(o), None),
+        }
+
+    def optim(kind, d_lr=p(lr), d_adam=0):
+        return _lib.TzrSparseOptim(kind=kind, weight_decay_mode=0, d_lr=d_lr, eps=1e-8, weight_decay=0.0, max_gradient=0.0,
+                                   gradient_clipping=0, beta1=0.9, beta2=0.999, d_adam=d_adam)
+
+    SGD, ACCUMULATE, ADAM = 0, 3, 4
+    accepted = {"apply": WORKSPACE, "cells": WORKSPACE, "direct": WORKSPACE, "dense": OK}
+    every = lambda code: {k: code for k in accepted}  # noqa: E731
+    assert calls(optim(SGD)) == accepted
+    assert calls(optim(ADAM, d_adam=p(adam))) == accepted
+    assert calls(optim(SGD, d_lr=0)) == every(INVALID)
+    assert calls(optim(99)) == every(UNSUPPORTED)
+    assert calls(optim(ACCUMULATE)) == dict(accepted, dense=UNSUPPORTED)
+    assert calls(optim(ADAM)) == every(INVALID)

@@ -118,88 +118,9 @@ __global__ __launch_bounds__(IA_THREADS) void tzr_dot_interaction_fwd_kernel(
 // 4-byte accesses everywhere and ran at 2.2 TB/s against the forward's 5.9 TB/s).
 //   A'[c][k] = X[k][c]  (lane: c = l&15, k = 4*ks + (l>>4))  read from an LDS image of X
 //   B'[k][i] = S[k][i]  (lane: k = 4*ks + (l>>4), i = l&15)  read from the LDS S matrix
-__global__ __launch_bounds__(IA_THREADS) void tzr_dot_interaction_bwd_kernel(
-    const float* __restrict__ dense, int64_t dense_stride, const float* __restrict__ sparse,
-    int64_t sparse_stride, int n, int hd, int64_t B, const float* __restrict__ gout,
-    int64_t gout_stride, int cat_dense, int cat_sparse, float* __restrict__ gdense,
-    int64_t gdense_stride, float* __restrict__ gsparse, int64_t gsparse_stride) {
-  // per wave: S 32 x 33 floats, X 32 x 17 floats (odd strides: conflict-free column reads)
-  __shared__ float S[IA_WAVES][IA_MAXN * (IA_MAXN + 1)];
-  __shared__ float Xs[IA_WAVES][IA_MAXN * (IA_D + 1)];
-  __shared__ unsigned short ij[IA_MAXP];  // idx -> (i << 8) | j
-  const int lane = threadIdx.x & (TZR_WAVE - 1);
-  const int wv = threadIdx.x / TZR_WAVE;
-  const int r = lane & 15, q = lane >> 4;
-  const int P = n * (n - 1) / 2;
-  for (int idx = threadIdx.x; idx < P; idx += IA_THREADS) {
-    int i = 0, rem = idx;
-    while (rem >= n - 1 - i) {
-      rem -= n - 1 - i;
-      ++i;
-    }
-    ij[idx] = (unsigned short)((i << 8) | (i + 1 + rem));
-  }
-  for (int k = threadIdx.x; k < IA_WAVES * IA_MAXN * (IA_MAXN + 1); k += IA_THREADS)
-    (&S[0][0])[k] = 0.f;
-  for (int k = threadIdx.x; k < IA_WAVES * IA_MAXN * (IA_D + 1); k += IA_THREADS)
-    (&Xs[0][0])[k] = 0.f;
-  __syncthreads();
-  const int pd = P;                                   // pass-through dense columns of gout
-  const int ps = P + ((cat_dense && hd) ? IA_D : 0);  // pass-through sparse columns
-  for (int64_t b0 = (int64_t)blockIdx.x * IA_WAVES; b0 < B; b0 += (int64_t)gridDim.x * IA_WAVES) {
-    const int64_t b = b0 + wv;
-    const bool on = b < B;
-    const bool row0 = on && r < n, row1 = on && 16 + r < n;
-    float4 p0 = tzr_zero4(), p1 = tzr_zero4();  // pass-through gradients of rows r / 16+r
-    if (on) {
-      const float* g = gout + b * gout_stride;
-      for (int idx = lane; idx < P; idx += TZR_WAVE) {
-        const float v = g[idx];
-        const int i = ij[idx] >> 8, j = ij[idx] & 255;
-        S[wv][i * (IA_MAXN + 1) + j] = v;
-        S[wv][j * (IA_MAXN + 1) + i] = v;
-      }
-      float4 a0 = tzr_zero4(), a1 = tzr_zero4();
-      if (row0) a0 = tzr_ld4(ia_row(dense, dense_stride, sparse, sparse_stride, b, r, hd) + 4 * q);
-      if (row1) a1 = tzr_ld4(ia_row(dense, dense_stride, sparse, sparse_stride, b, 16 + r, hd) + 4 * q);
-      float* xr0 = &Xs[wv][r * (IA_D + 1) + 4 * q];
-      float* xr1 = &Xs[wv][(16 + r) * (IA_D + 1) + 4 * q];
-      xr0[0] = a0.x; xr0[1] = a0.y; xr0[2] = a0.z; xr0[3] = a0.w;
-      xr1[0] = a1.x; xr1[1] = a1.y; xr1[2] = a1.z; xr1[3] = a1.w;
-      if (row0) {
-        if (hd && r == 0) { if (cat_dense) p0 = tzr_ld4_a4(g + pd + 4 * q); }
-        else if (cat_sparse) p0 = tzr_ld4_a4(g + ps + (r - hd) * IA_D + 4 * q);
-      }
-      if (row1 && cat_sparse) p1 = tzr_ld4_a4(g + ps + (16 + r - hd) * IA_D + 4 * q);
-    }
-    ia_wave_sync();  // S[wv] / Xs[wv] are private to this wave
-    f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
-#pragma unroll
-    for (int ks = 0; ks < IA_MAXN / 4; ++ks) {
-      const int k = 4 * ks + q;                       // contraction index = row of X / S
-      const float xa = Xs[wv][k * (IA_D + 1) + r];     // A'[c=r][k]
-      const float s0 = S[wv][k * (IA_MAXN + 1) + r];   // B'[k][i=r]
-      const float s1 = S[wv][k * (IA_MAXN + 1) + 16 + r];
-      d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, s0, d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, s1, d1, 0, 0, 0);
-    }
-    // accumulator reg of lane (r, q) = D'[row c = 4q+reg][col i = r] = dX[i = r][c = 4q+reg]
-    if (row0) {
-      const float4 v = make_float4(d0[0] + p0.x, d0[1] + p0.y, d0[2] + p0.z, d0[3] + p0.w);
-      if (hd && r == 0) tzr_st4(gdense + b * gdense_stride + 4 * q, v);
-      else tzr_st4(gsparse + b * gsparse_stride + (int64_t)(r - hd) * IA_D + 4 * q, v);
-    }
-    if (row1) {
-      const float4 v = make_float4(d1[0] + p1.x, d1[1] + p1.y, d1[2] + p1.z, d1[3] + p1.w);
-      tzr_st4(gsparse + b * gsparse_stride + (int64_t)(16 + r - hd) * IA_D + 4 * q, v);
-    }
-    ia_wave_sync();
-  }
-}
-
-// The same backward with the NEXT sample's global loads in flight while the current one is contracted: a wave walks
-// many samples (grid sized to the chip, not to the batch), so the prologue above is paid once per ~10 samples and the
-// dependent chain  load -> LDS -> MFMA -> store  of one sample overlaps the loads of the next.
+// The NEXT sample's global loads are in flight while the current one is contracted: a wave walks many samples (grid
+// sized to the chip, not to the batch), so the kernel's prologue is paid once per ~10 samples and the dependent chain
+// load -> LDS -> MFMA -> store  of one sample overlaps the loads of the next.
 struct IaBwdRegs {
   float gv[(IA_MAXP + TZR_WAVE - 1) / TZR_WAVE];  // pair gradients idx = lane + 64 k
   float4 a0, a1, p0, p1;                          // X rows r / 16+r, pass-through gradients of those rows
@@ -719,9 +640,8 @@ static unsigned iam_bwd_grid(int64_t B, int waves, int per_cu) {
 static unsigned iag_grid(int64_t B) { return (unsigned)(B < 1 ? 1 : (B > 16384 ? 16384 : B)); }
 
 int g_tzr_ia_fwd_wgs = 0;    // tzr_tune("ia_fwd_wgs"): workgroups of the D = 16 forward (0 = one per 4 samples, <= 8192)
-int g_tzr_ia_bwd_plain = 0;  // tzr_tune("ia_bwd_plain"): 1 = the backward without the software pipeline (A/B; D = 16, n <= 32)
-int g_tzr_ia_bwd_wgs = 0;    // tzr_tune("ia_bwd_wgs"): workgroups of that backward (0 = one per 4 samples, at most 3 072
-                             // pipelined / 8 192 plain -- profiles/r02x: 114.7 -> 91.5 us per forward + backward pair)
+int g_tzr_ia_bwd_wgs = 0;    // tzr_tune("ia_bwd_wgs"): workgroups of the D = 16 backward (0 = one per 4 samples, at most 3 072
+                             // -- profiles/r02x: 114.7 -> 91.5 us per forward + backward pair against 8 192 without the pipeline)
 
 static unsigned ia_grid(int64_t B) {
   const int64_t wg = (B + IA_WAVES - 1) / IA_WAVES;
@@ -819,20 +739,12 @@ extern "C" int tzr_dot_interaction_bwd(const float* d_dense, int64_t dense_strid
     return TZR_OK;
   }
   unsigned grid = ia_grid(B);
-  const unsigned cap = g_tzr_ia_bwd_wgs > 0 ? (unsigned)g_tzr_ia_bwd_wgs : (g_tzr_ia_bwd_plain ? grid : 3072u);
+  const unsigned cap = g_tzr_ia_bwd_wgs > 0 ? (unsigned)g_tzr_ia_bwd_wgs : 3072u;
   if (cap < grid) grid = cap;
-  if (!g_tzr_ia_bwd_plain) {
-    hipLaunchKernelGGL(tzr_dot_interaction_bwd_pipe_kernel, dim3(grid), dim3(IA_THREADS), 0,
-                       static_cast<hipStream_t>(stream), d_dense, dense_stride, d_sparse, sparse_stride, n, hd, B,
-                       d_grad_out, grad_out_stride, cat_dense, cat_sparse, d_grad_dense, grad_dense_stride,
-                       d_grad_sparse, grad_sparse_stride);
-    TZR_CHECK_LAUNCH();
-    return TZR_OK;
-  }
-  hipLaunchKernelGGL(tzr_dot_interaction_bwd_kernel, dim3(grid), dim3(IA_THREADS), 0,
-                     static_cast<hipStream_t>(stream), d_dense, dense_stride, d_sparse,
-                     sparse_stride, n, hd, B, d_grad_out, grad_out_stride, cat_dense, cat_sparse,
-                     d_grad_dense, grad_dense_stride, d_grad_sparse, grad_sparse_stride);
+  hipLaunchKernelGGL(tzr_dot_interaction_bwd_pipe_kernel, dim3(grid), dim3(IA_THREADS), 0,
+                     static_cast<hipStream_t>(stream), d_dense, dense_stride, d_sparse, sparse_stride, n, hd, B,
+                     d_grad_out, grad_out_stride, cat_dense, cat_sparse, d_grad_dense, grad_dense_stride,
+                     d_grad_sparse, grad_sparse_stride);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
 }

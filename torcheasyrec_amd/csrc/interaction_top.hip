@@ -96,13 +96,13 @@ __device__ __forceinline__ int it_real_col(int c, int P, int npb, int nblk) {
 // ---- backward ------------------------------------------------------------------------------------------------------
 // wave w owns column blocks w, w + 16, ... (at most 4: 4 x 16 B-operand registers per lane).  Per tile: every wave
 // multiplies the tile's g1 fragment with its blocks, scatters the accumulators into LDS, and behind a barrier contracts
-// ONE sample of the tile the way tzr_dot_interaction_bwd_kernel does.  HBM traffic: X in, dX out, g1 in (243 MB at
+// ONE sample of the tile the way tzr_dot_interaction_bwd_pipe_kernel does.  HBM traffic: X in, dX out, g1 in (243 MB at
 // B = 65 536) instead of 243 + 2 x 205 MB.
 struct ItBwdArgs {
   const float *dense, *sparse, *g1, *W1, *scale;
   float *gdense, *gsparse;
   int64_t dense_stride, sparse_stride, g1_stride, ldw, gdense_stride, gsparse_stride, B;
-  int n, hd, stagger;
+  int n, hd;
   uint64_t* prof;
 };
 
@@ -289,7 +289,7 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
   // Half of the waves (two of the four on every SIMD) run the product of the NEXT tile before they contract their sample
   // of this one, the other half behind it: in lockstep all sixteen would sit in the LDS-latency-bound contraction at
   // once with the MFMA pipe mostly idle, then all in the product.
-  const bool product_first_wave = a.stagger == 2 ? false : (((wv >> 2) & 1) != (a.stagger == 1));
+  const bool product_first_wave = ((wv >> 2) & 1) != 0;
   const bool v0 = r < n, v1 = 16 + r < n;
   IT_PROF_DECL;
   // tile t, its dz and g1 tiles in buffer CUR (XL: a constant of the code -- the loop is unrolled by two, and there is one loop
@@ -889,7 +889,6 @@ __device__ __forceinline__ void it_fwd_body(const ItFwdArgs& a) {
 __global__ __launch_bounds__(IT_THREADS) void tzr_ia_top_fwd_kernel(ItFwdArgs a) { it_fwd_body<false>(a); }
 __global__ __launch_bounds__(IT_THREADS) void tzr_ia_top_fwd_z_kernel(ItFwdArgs a) { it_fwd_body<true>(a); }
 
-int g_tzr_it_stagger = 0;  // tzr_tune("it_stagger"): which half of the waves runs the next product first (0 / 1), 2 = none (experiments)
 // tzr_tune("it_fwd_stagger"): forward, order of row building and product in a wave's turn: 0 / 1 = half of the waves each way
 // (two of the four on every SIMD), 2 / 3 = every wave row-first / row-second.  Half and half is the default for both
 // kernels: with the z stores it hides them behind the other half's product (111.6 vs 116-118 us, profiles/r04ap); without
@@ -931,7 +930,6 @@ extern "C" int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_s
   a.dense = d_dense; a.sparse = d_sparse; a.g1 = d_g1; a.W1 = d_W1; a.scale = d_scale; a.gdense = d_grad_dense; a.gsparse = d_grad_sparse;
   a.dense_stride = dense_stride; a.sparse_stride = sparse_stride; a.g1_stride = g1_stride; a.ldw = ldw;
   a.gdense_stride = grad_dense_stride; a.gsparse_stride = grad_sparse_stride; a.B = B; a.n = n; a.hd = hd;
-  a.stagger = g_tzr_it_stagger;
 #ifdef IT_PROF
   a.prof = g_tzr_it_prof;
 #else

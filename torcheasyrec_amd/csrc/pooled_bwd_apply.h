@@ -26,6 +26,43 @@ inline bool bwd_norm_kind(int kind) { return kind >= TZR_OPT_PARTIAL_ROWWISE_ADA
 // the kinds that read the step state d_adam (ticked by tzr_sparse_adam_tick)
 inline bool bwd_step_kind(int kind) { return kind == TZR_OPT_ADAM || (bwd_norm_kind(kind) && kind != TZR_OPT_LARS_SGD); }
 
+// The optimizer arguments of a backward entry point, checked and copied for the kernels.  TZR_ERR_INVALID: no learning rate, or
+// a kind that reads the step state without d_adam; TZR_ERR_UNSUPPORTED: a kind the row update does not have (TZR_OPT_ACCUMULATE
+// among them where the caller does not allow it: the dense update of replicated tables).  Every step kind is a supported
+// kind, so the order of the last two checks decides nothing.
+inline int bwd_opt_from(const TzrSparseOptim* h_optim, bool allow_accumulate, BwdOpt* opt) {
+  if (!h_optim->d_lr) return TZR_ERR_INVALID;
+  const int kind = h_optim->kind;
+  if (kind != TZR_OPT_SGD && kind != TZR_OPT_ADAGRAD && kind != TZR_OPT_ROWWISE_ADAGRAD && kind != TZR_OPT_ADAM &&
+      !(allow_accumulate && kind == TZR_OPT_ACCUMULATE) && !bwd_norm_kind(kind))
+    return TZR_ERR_UNSUPPORTED;
+  if (bwd_step_kind(kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
+  opt->kind = kind;
+  opt->wd_mode = h_optim->weight_decay_mode;
+  opt->clip = h_optim->gradient_clipping;
+  opt->lr = reinterpret_cast<const float*>(h_optim->d_lr);
+  opt->eps = h_optim->eps;
+  opt->wd = h_optim->weight_decay;
+  opt->max_grad = h_optim->max_gradient;
+  opt->beta1 = h_optim->beta1;
+  opt->beta2 = h_optim->beta2;
+  opt->adam = reinterpret_cast<const float*>(h_optim->d_adam);
+  return TZR_OK;
+}
+
+// ... and its gradient buffers: n_dst of them (1 .. TZR_MAX_DST, checked by the caller), the rest zero.
+inline int bwd_grads_from(const TzrDst* h_grads, int n_dst, BwdGrads* G) {
+  for (int i = 0; i < TZR_MAX_DST; ++i) {
+    G->d[i].ptr = 0;
+    G->d[i].stride = 0;
+  }
+  for (int i = 0; i < n_dst; ++i) {
+    if (!h_grads[i].ptr || (h_grads[i].stride & 3) || (h_grads[i].ptr & 15)) return TZR_ERR_INVALID;
+    G->d[i] = h_grads[i];
+  }
+  return TZR_OK;
+}
+
 // Gradient sources of one lookup (key -> table), resolved once per workgroup when the table is
 // read by a single key (the common case).
 // (scalar fields, no arrays: a runtime-indexed array in this struct lands in scratch memory and

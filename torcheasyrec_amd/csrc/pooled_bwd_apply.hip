@@ -382,20 +382,13 @@ __global__ __launch_bounds__(BWD_THREADS) void tzr_bwd_reduce_kernel(
   bwd_reduce_body<FAM>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
 }
 
-// the same body compiled for 7 / 8 waves per SIMD (72 / 64 VGPRs); tzr_tune("bwd_apply_waves") = 6 | 7 | 8, 0 = 7
+// the same body compiled for 7 waves per SIMD (72 VGPRs): why 7, see the launch
 __global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(7) void tzr_bwd_reduce_w7_kernel(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
     int grad_mode, BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {
   bwd_reduce_body<BWD_FAM_LEGACY>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
 }
-__global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(8) void tzr_bwd_reduce_w8_kernel(
-    const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
-    const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
-    int grad_mode, BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {
-  bwd_reduce_body<BWD_FAM_LEGACY>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);
-}
-int g_tzr_bwd_apply_waves = 0;
 
 // ---- the same unit through bwd_reduce_unit's FAST memory side (pooled_bwd_apply.h: bwd_apply_row_fast) ----------------------
 // Round 5.  The ISA of the loop above (profiles/r05ai/apply_w7_loop.s) runs a tile as a CHAIN: LDS keys -> FLAT gradient gather
@@ -404,8 +397,8 @@ int g_tzr_bwd_apply_waves = 0;
 // round trips per 16 lookups, 16 tiles per wave -- ~4.5 us per tile whatever the data's home (tables capped at 100 k rows, i.e.
 // cache resident: 78 vs 80 us; gradients cache resident: 77 vs 80, profiles/r05ah).  Units whose table is fp32, read by one key
 // with one gradient buffer take bwd_reduce_unit<.., FK>: global instructions only, nothing loaded conditionally, ONE round trip
-// per NT tiles; every other unit takes the general form of the same function.  Same arithmetic, same summation order.
-template <int FK, int NT>
+// per tile; every other unit takes the general form of the same function.  Same arithmetic, same summation order.
+template <int FK>
 __device__ __forceinline__ void bwd_reduce_body_fast(
     const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,
     const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform,
@@ -454,27 +447,22 @@ __device__ __forceinline__ void bwd_reduce_body_fast(
   };
   const bool fast = tb.w_dtype == TZR_DT_F32 && (grad_mode == 1 || (tb.n_feats == 1 && ft_dst == 1));  // (workgroup-uniform)
   if (fast)
-    bwd_reduce_unit<BWD_FAM_LEGACY, NT, FK>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
+    bwd_reduce_unit<BWD_FAM_LEGACY, 1, FK>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
   else
     bwd_reduce_unit<BWD_FAM_LEGACY, 1, 0>(tb, feats, P.feat_by_order, P.bag_of, offsets, weights, B, uniform, grad_mode, opt, U, sG, n, tail);
 }
 
-#define TZR_REDUCE_FAST_KERNEL(NAME, FK_, NT_, ATTR)                                                                  \
+#define TZR_REDUCE_FAST_KERNEL(NAME, FK_, ATTR)                                                                       \
   __global__ __launch_bounds__(BWD_THREADS) ATTR void NAME(                                                          \
       const TzrTable* __restrict__ tables, int T, const TzrFeature* __restrict__ feats,                              \
       const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t B, int uniform, int grad_mode, \
       BwdGrads G, BwdOpt opt, int max_dim, BwdPlan P) {                                                               \
-    bwd_reduce_body_fast<FK_, NT_>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);    \
+    bwd_reduce_body_fast<FK_>(tables, T, feats, offsets, weights, B, uniform, grad_mode, G, opt, max_dim, P);         \
   }
-// one tile per round trip at 7 waves per SIMD (the whole unit grid of a 65 536-sample Criteo step resident at once) ...
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_adagrad_kernel, TZR_OPT_ADAGRAD, 1, TZR_WAVES_PER_EU(7))
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_rowwise_kernel, TZR_OPT_ROWWISE_ADAGRAD, 1, TZR_WAVES_PER_EU(7))
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_sgd_kernel, TZR_OPT_SGD, 1, TZR_WAVES_PER_EU(7))
-// ... or two tiles per round trip, also at 7 (tzr_tune "bwd_apply_fast" = 2)
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast2_adagrad_kernel, TZR_OPT_ADAGRAD, 2, TZR_WAVES_PER_EU(7))
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast2_rowwise_kernel, TZR_OPT_ROWWISE_ADAGRAD, 2, TZR_WAVES_PER_EU(7))
-TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast2_sgd_kernel, TZR_OPT_SGD, 2, TZR_WAVES_PER_EU(7))
-int g_tzr_bwd_apply_fast = 0;  // tzr_tune("bwd_apply_fast"): 0 = one tile per round trip, 2 = two, -1 = the general loop only
+// one tile per round trip at 7 waves per SIMD (the whole unit grid of a 65 536-sample Criteo step resident at once)
+TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_adagrad_kernel, TZR_OPT_ADAGRAD, TZR_WAVES_PER_EU(7))
+TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_rowwise_kernel, TZR_OPT_ROWWISE_ADAGRAD, TZR_WAVES_PER_EU(7))
+TZR_REDUCE_FAST_KERNEL(tzr_bwd_reduce_fast_sgd_kernel, TZR_OPT_SGD, TZR_WAVES_PER_EU(7))
 
 extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* d_feats,
                                     int n_feats, int n_tables, int max_dim,
@@ -489,13 +477,8 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
     return TZR_ERR_INVALID;
   const bool uniform = uniform_bag_len == 1;
   if (!uniform && !d_offsets && grad_mode == 0) return TZR_ERR_INVALID;
-  if (!h_optim->d_lr) return TZR_ERR_INVALID;
-  if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD && h_optim->kind != TZR_OPT_ACCUMULATE &&
-      h_optim->kind != TZR_OPT_ADAM &&
-      !bwd_norm_kind(h_optim->kind))
-    return TZR_ERR_UNSUPPORTED;
-  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
+  BwdOpt opt;
+  if (const int rc = bwd_opt_from(h_optim, true, &opt)) return rc;
   if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TZR_ERR_WORKSPACE;
   if (n_positions < 0 || n_positions >= (1LL << 32)) return TZR_ERR_UNSUPPORTED;
   BwdPlan P;
@@ -503,25 +486,7 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
     return TZR_ERR_WORKSPACE;
   if (n_values == 0 || n_positions == 0 || B == 0) return TZR_OK;
   BwdGrads G;
-  for (int i = 0; i < TZR_MAX_DST; ++i) {
-    G.d[i].ptr = 0;
-    G.d[i].stride = 0;
-  }
-  for (int i = 0; i < n_dst; ++i) {
-    if (!h_grads[i].ptr || (h_grads[i].stride & 3) || (h_grads[i].ptr & 15)) return TZR_ERR_INVALID;
-    G.d[i] = h_grads[i];
-  }
-  BwdOpt opt;
-  opt.kind = h_optim->kind;
-  opt.wd_mode = h_optim->weight_decay_mode;
-  opt.clip = h_optim->gradient_clipping;
-  opt.lr = reinterpret_cast<const float*>(h_optim->d_lr);
-  opt.eps = h_optim->eps;
-  opt.wd = h_optim->weight_decay;
-  opt.max_grad = h_optim->max_gradient;
-  opt.beta1 = h_optim->beta1;
-  opt.beta2 = h_optim->beta2;
-  opt.adam = reinterpret_cast<const float*>(h_optim->d_adam);
+  if (const int rc = bwd_grads_from(h_grads, n_dst, &G)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned chunks = (unsigned)P.max_chunks;
 #define TZR_REDUCE_LAUNCH(K)                                                                       \
@@ -529,26 +494,19 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
                      d_weights, B, (int)uniform, grad_mode, G, opt, max_dim, P)
   // bags of one id with pooled gradients, or one gradient row per id (the sharded owners' and the sequence lookup's backward), no
   // per-sample weights: the shapes the fast memory side of the tile loop is written for
-  const bool fast_shape = ((grad_mode == 0 && uniform) || grad_mode == 1) && !d_weights && g_tzr_bwd_apply_fast >= 0 &&
-                          g_tzr_bwd_apply_waves == 0 &&
+  const bool fast_shape = ((grad_mode == 0 && uniform) || grad_mode == 1) && !d_weights &&
                           (opt.kind == TZR_OPT_ADAGRAD || opt.kind == TZR_OPT_ROWWISE_ADAGRAD || opt.kind == TZR_OPT_SGD);
   if (fast_shape) {
-    const bool two = g_tzr_bwd_apply_fast == 2;
-    if (opt.kind == TZR_OPT_ADAGRAD) {
-      if (two) TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast2_adagrad_kernel); else TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_adagrad_kernel);
-    } else if (opt.kind == TZR_OPT_ROWWISE_ADAGRAD) {
-      if (two) TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast2_rowwise_kernel); else TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_rowwise_kernel);
-    } else {
-      if (two) TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast2_sgd_kernel); else TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_sgd_kernel);
-    }
+    if (opt.kind == TZR_OPT_ADAGRAD)
+      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_adagrad_kernel);
+    else if (opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
+      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_rowwise_kernel);
+    else
+      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_sgd_kernel);
   } else if (opt.kind == TZR_OPT_ADAM) {
     TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ADAM>));  // Adam holds two state rows per lane: no registers for a second tile
   } else if (bwd_norm_kind(opt.kind)) {
     TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_NORM>));
-  } else if (g_tzr_bwd_apply_waves == 6) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_LEGACY>));
-  } else if (g_tzr_bwd_apply_waves == 8) {
-    TZR_REDUCE_LAUNCH(tzr_bwd_reduce_w8_kernel);
   } else {
     // 7 waves per SIMD = 1792 workgroups resident: the whole unit grid of a B = 65536 Criteo step (1691) runs in
     // one wave of workgroups.  At 6 (77 VGPRs, what the compiler picks unasked) the last 155 units waited for a
@@ -621,27 +579,12 @@ extern "C" int tzr_dense_rows_update_clear(const TzrTable* d_tables, int n_table
 
 static int dense_rows_update(const TzrTable* d_tables, int n_tables, const int64_t* d_row_start, int64_t total_rows,
                              float* d_acc, int dim, const TzrSparseOptim* h_optim, int clear, void* stream) {
-  if (!d_tables || n_tables <= 0 || !d_row_start || total_rows < 0 || !h_optim || !h_optim->d_lr ||
-      dim <= 0 || (dim & 3) || dim > BWD_MAXDIM)
+  if (!d_tables || n_tables <= 0 || !d_row_start || total_rows < 0 || !h_optim || dim <= 0 || (dim & 3) || dim > BWD_MAXDIM)
     return TZR_ERR_INVALID;
-  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
-  if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD && h_optim->kind != TZR_OPT_ADAM &&
-      !bwd_norm_kind(h_optim->kind))
-    return TZR_ERR_UNSUPPORTED;
+  BwdOpt opt;
+  if (const int rc = bwd_opt_from(h_optim, false, &opt)) return rc;  // (no TZR_OPT_ACCUMULATE: nothing to accumulate into)
   if (total_rows == 0) return TZR_OK;
   if (!d_acc || (reinterpret_cast<uintptr_t>(d_acc) & 15)) return TZR_ERR_INVALID;
-  BwdOpt opt;
-  opt.kind = h_optim->kind;
-  opt.wd_mode = h_optim->weight_decay_mode;
-  opt.clip = h_optim->gradient_clipping;
-  opt.lr = reinterpret_cast<const float*>(h_optim->d_lr);
-  opt.eps = h_optim->eps;
-  opt.wd = h_optim->weight_decay;
-  opt.max_grad = h_optim->max_gradient;
-  opt.beta1 = h_optim->beta1;
-  opt.beta2 = h_optim->beta2;
-  opt.adam = reinterpret_cast<const float*>(h_optim->d_adam);
   const int gpb = (TZR_WAVE / (dim >> 2)) * BWD_WAVES;
   const unsigned grid = (unsigned)std::min<int64_t>(4096, (total_rows + gpb - 1) / gpb);
   if (opt.kind == TZR_OPT_ADAM) {

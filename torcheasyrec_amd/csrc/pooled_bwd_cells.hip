@@ -377,7 +377,7 @@ struct FwdPlanArgs {
   const TzrTable* btables;
   uint2* slab;
   uint16_t* bnd;
-  int32_t ch, order;
+  int32_t ch;
 };
 
 // Residency: the two kinds of workgroup share ONE LDS area (the larger: 22.8 KB) and the forward keeps 4 gathers in flight per
@@ -400,22 +400,8 @@ __global__ __launch_bounds__(BWD_THREADS) TZR_WAVES_PER_EU(FWD_PLAN_WAVES) void 
                                                                                                           BwdCellsView V, BwdSrcArgs A) {
   __shared__ FwdPlanLds S;
   const uint32_t i = blockIdx.x;
-  const uint32_t both = 2u * min(a.n_fwd, a.n_part);
-  bool part;
-  uint32_t idx;
-  if (a.order == 1) {  // the plan's workgroups first
-    part = i < a.n_part;
-    idx = part ? i : i - a.n_part;
-  } else if (a.order == 2) {  // ... last
-    part = i >= a.n_fwd;
-    idx = part ? i - a.n_fwd : i;
-  } else if (i < both) {
-    part = (i & 1u) != 0u;
-    idx = i >> 1;
-  } else {
-    part = a.n_part > a.n_fwd;
-    idx = i - (both >> 1);
-  }
+  const bool part = i >= a.n_fwd;  // the plan's workgroups last (measured: see above)
+  const uint32_t idx = part ? i - a.n_fwd : i;
   if (part)  // (workgroup-uniform)
     bwd_cells_partition_body(V, a.btables, A, a.slab, a.bnd, a.ch, idx, S.p);
   else
@@ -984,7 +970,6 @@ extern "C" int tzr_pooled_bwd_cells_plan(const TzrTable* d_tables, int n_tables,
 // tzr_pooled_fwd (one id per bag, fp32 tables, unweighted: what tzr_pooled_fwd_ex sends to its LDS-ids kernel) and
 // tzr_pooled_bwd_cells_plan of the same batch as ONE launch.  TZR_ERR_UNSUPPORTED: not that case (the caller makes the two calls).
 extern int g_tzr_fwd_tile_b;
-int g_tzr_fwd_plan_order = 2;  // tzr_tune("fwd_plan_order"): 0 = alternating, 1 = the plan's workgroups first, 2 = last (measured: see the kernel)
 int g_tzr_fwd_plan = 1;  // tzr_tune("fwd_plan"): 0 = never (tzr_pooled_fwd_cells_plan_supported says no), 2 = at any batch size (tests)
 
 extern "C" int tzr_pooled_fwd_cells_plan_supported(int n_slots, int64_t B) {
@@ -1037,7 +1022,6 @@ extern "C" int tzr_pooled_fwd_cells_plan(const TzrTable* d_ftables, const TzrFea
   a.slab = P.ks[1];
   a.bnd = reinterpret_cast<uint16_t*>(P.hist);
   a.ch = (int)g.ch;
-  a.order = g_tzr_fwd_plan_order;
   hipLaunchKernelGGL(tzr_pooled_fwd_u1_cells_plan_kernel, dim3(a.n_fwd + a.n_part), dim3(BWD_THREADS), 0, static_cast<hipStream_t>(stream),
                      a, dsts, V, A);
   TZR_CHECK_LAUNCH();
@@ -1052,37 +1036,15 @@ extern "C" int tzr_pooled_bwd_cells_apply(const TzrTable* d_tables, const TzrFea
   if (!d_tables || !d_feats || !h_grads || !h_optim || n_tables <= 0 || n_feats <= 0 || n_values < 0 || B <= 0 || n_dst <= 0 ||
       n_dst > TZR_MAX_DST || max_dim <= 0 || max_dim > BWD_MAXDIM || (max_dim & 3) || (grad_mode != 0 && grad_mode != 1))
     return TZR_ERR_INVALID;
-  if (!h_optim->d_lr) return TZR_ERR_INVALID;
-  if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD && h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM &&
-      !bwd_norm_kind(h_optim->kind))
-    return TZR_ERR_UNSUPPORTED;
-  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
+  BwdOpt opt;
+  if (const int rc = bwd_opt_from(h_optim, true, &opt)) return rc;
   BwdCellsGeo g;
   BwdCellsView V;
   BwdPlan P;
   const int rc = cells_common(h_geo, d_geo, ws, ws_bytes, n_values, n_feats, n_tables, max_dim, &g, &V, &P);
   if (rc != TZR_OK) return rc;
   BwdGrads G;
-  for (int i = 0; i < TZR_MAX_DST; ++i) {
-    G.d[i].ptr = 0;
-    G.d[i].stride = 0;
-  }
-  for (int i = 0; i < n_dst; ++i) {
-    if (!h_grads[i].ptr || (h_grads[i].stride & 3) || (h_grads[i].ptr & 15)) return TZR_ERR_INVALID;
-    G.d[i] = h_grads[i];
-  }
-  BwdOpt opt;
-  opt.kind = h_optim->kind;
-  opt.wd_mode = h_optim->weight_decay_mode;
-  opt.clip = h_optim->gradient_clipping;
-  opt.lr = reinterpret_cast<const float*>(h_optim->d_lr);
-  opt.eps = h_optim->eps;
-  opt.wd = h_optim->weight_decay;
-  opt.max_grad = h_optim->max_gradient;
-  opt.beta1 = h_optim->beta1;
-  opt.beta2 = h_optim->beta2;
-  opt.adam = reinterpret_cast<const float*>(h_optim->d_adam);
+  if (const int rc = bwd_grads_from(h_grads, n_dst, &G)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define TZR_CELLS_LAUNCH(K)                                                                                               \
   hipLaunchKernelGGL(K, dim3((unsigned)g.n_units + BWD_CELLS_WORKERS), dim3(BWD_THREADS), 0, s, V, (int)g.n_units, d_feats, d_weights, \

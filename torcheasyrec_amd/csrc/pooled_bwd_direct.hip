@@ -273,8 +273,7 @@ __device__ __forceinline__ uint32_t bwd_direct_gather_waves(const BwdGeo& G, con
 template <int FAM, int NT, int FK = 0>
 __device__ __forceinline__ void bwd_direct_unit(const TzrTable& tb, const TzrFeature* __restrict__ feats,
                                                 const BwdSrcArgs& A, const float* __restrict__ weights, int grad_mode,
-                                                const BwdOpt& opt, BwdDirectLds& L, int n, bool regions = false,
-                                                bool sort_only = false) {
+                                                const BwdOpt& opt, BwdDirectLds& L, int n, bool regions = false) {
   if (n <= 0) return;  // workgroup-uniform
   const int lane = threadIdx.x & (TZR_WAVE - 1);
   const int wv = threadIdx.x / TZR_WAVE;
@@ -316,7 +315,6 @@ __device__ __forceinline__ void bwd_direct_unit(const TzrTable& tb, const TzrFea
   __syncthreads();  // smm is reused by the core
   bwd_sort_core<kRounds>(kreg, sreg, vmask, pw, rounds, kmin, max(1, bwd_bits(kmax - kmin)), true, L.S, dest);
   __syncthreads();  // the sort's LDS is dead: the unit's arrays take its place
-  if (sort_only) return;
 #pragma unroll
   for (int r = 0; r < kRounds; ++r)
     if ((vmask >> r) & 1u) {
@@ -431,7 +429,7 @@ __device__ __forceinline__ void bwd_direct_body(
     const float* __restrict__ weights, int grad_mode, const BwdGrads& Gr, const BwdOpt& opt, int ch,
     uint32_t* __restrict__ wcount, float* __restrict__ wpart, int max_dim) {
   __shared__ BwdDirectLds L;
-  const int dbg = (ch >> 16) & 0xFF;  // tzr_tune("bwd_direct_debug"): stop behind 1 = geometry, 2 = id walk, 3 = sort (timing experiments)
+  const int dbg = (ch >> 16) & 0xFF;  // tzr_tune("bwd_direct_debug"): 5 = only the row-split workgroups run (tests)
   const bool no_hot = (ch >> 24) & 1;  // no hot-row candidate: every hot row is streamed by its range's workgroup (the launcher: TZR_GRAD_HOT_ROWS / tzr_tune "bwd_direct_hot")
   ch &= 0xFFFF;
   // geometry (bwd_geometry of pooled_bwd_sort.h, with every global load of it -- lookups, their key lengths, table
@@ -470,7 +468,7 @@ __device__ __forceinline__ void bwd_direct_body(
     bwd_block_scan(L.G.tchunk, T, L.G.wtot);
   }
   const int cidx = blockIdx.x;
-  if (cidx >= (int)tzr_uni(L.G.tchunk[T]) || dbg == 1) return;
+  if (cidx >= (int)tzr_uni(L.G.tchunk[T])) return;
   int t = 0;
   {
     int lo = 0, hi = T;  // last t with tchunk[t] <= cidx (the non-empty table holding it)
@@ -490,9 +488,8 @@ __device__ __forceinline__ void bwd_direct_body(
   G.fkey = L.G.fkey;
   G.tchunk = reinterpret_cast<const int32_t*>(L.G.tchunk);
   const uint64_t rows = (uint64_t)tb.rows;
-  if (dbg == 5 && rows * 2 > (uint64_t)k) return;  // (timing experiments: 4 = no row-split workgroups, 5 = only them)
+  if (dbg == 5 && rows * 2 > (uint64_t)k) return;
   if (rows * 2 <= (uint64_t)k) {
-    if (dbg == 4) return;
     // ---- a tiny table (fewer rows than half its workgroups: 3 rows x 2 730 lookups each at 8 192 per rank): every row
     // is SPLIT over P = k / rows workgroups by position; each sums its slice's gradient rows, the last of a row's P
     // workgroups to arrive adds the P partial sums in slice order (write-through records, agent-scope counter:
@@ -551,7 +548,6 @@ __device__ __forceinline__ void bwd_direct_body(
   bool fits, has_c = false;
   uint32_t n_c = 0, crow = 0u;
   uint32_t total = bwd_direct_gather_waves(G, tb, A, ts, te, lo, hi, L, &fits, detect, &has_c, &crow, &n_c);
-  if (dbg == 2) return;
   const bool hot = has_c && n_c > (uint32_t)BWD_UMAX;  // the same in every workgroup of the table
   const bool has_x = hot && crow >= lo && crow < hi;   // this workgroup's range holds the hot row: gathered again without it
   if (has_x) {
@@ -559,7 +555,7 @@ __device__ __forceinline__ void bwd_direct_body(
     total = bwd_direct_gather_waves(G, tb, A, ts, te, lo, hi, L, &fits, false, nullptr, nullptr, nullptr, true, crow);
   }
   if (total != 0 && fits) {
-    bwd_direct_unit<FAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)total, true, dbg == 3);
+    bwd_direct_unit<FAM, NT, FK>(tb, feats, A, weights, grad_mode, opt, L, (int)total, true);
   } else if (total != 0) {
     __syncthreads();  // (S is reused by the walk below)
     // ---- more lookups than one LDS unit: piece by piece ----
@@ -621,7 +617,7 @@ __device__ __forceinline__ void bwd_direct_body(
       }
     }
   }
-  if (!hot || dbg == 3) return;
+  if (!hot) return;
   // ---- the hot row: this workgroup's slice of the table's positions, the last of the k arrivals applies ----
   {
     __syncthreads();
@@ -661,12 +657,11 @@ __device__ __forceinline__ void bwd_direct_body(
 BWD_DIRECT_KERNEL(tzr_bwd_direct_kernel, BWD_FAM_LEGACY, 4, 2, 0)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_adam_kernel, BWD_FAM_ADAM, 3, 2, 0)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_norm_kernel, BWD_FAM_NORM, 3, 2, 0)  // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS
-// the optimizer kind at compile time: units of fp32 single-key tables take the fast tile loop (tzr_tune "bwd_apply_fast" >= 0)
+// the optimizer kind at compile time: units of fp32 single-key tables take the fast tile loop
 BWD_DIRECT_KERNEL(tzr_bwd_direct_adagrad_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ADAGRAD)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_rowwise_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ROWWISE_ADAGRAD)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_sgd_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_SGD)
-extern int g_tzr_bwd_apply_fast;  // pooled_bwd_apply.hip
-int g_tzr_bwd_direct_debug = 0;  // tzr_tune("bwd_direct_debug"): timing experiments, see bwd_direct_body
+int g_tzr_bwd_direct_debug = 0;  // tzr_tune("bwd_direct_debug"): 5 = only the row-split workgroups run (tests), see bwd_direct_body
 int g_tzr_bwd_direct_hot = 1;    // tzr_tune("bwd_direct_hot"): hot rows shared among a table's workgroups 1 = when the caller sets TZR_GRAD_HOT_ROWS, 0 = never, 2 = always
 
 int g_tzr_bwd_direct_ch = 0;  // tzr_tune("bwd_direct_ch"): lookups per workgroup (0 = by problem size)
@@ -729,12 +724,8 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
   if (!uniform && !d_offsets) return TZR_ERR_INVALID;
   if (!bwd_direct_shape_ok(n_positions, n_feats, n_tables, uniform_bag_len, grad_mode)) return TZR_ERR_UNSUPPORTED;
   if (max_rows > (1LL << 32) || n_values >= (1LL << 32)) return TZR_ERR_UNSUPPORTED;  // row ids and positions travel as 32-bit
-  if (!h_optim->d_lr) return TZR_ERR_INVALID;
-  if (h_optim->kind != TZR_OPT_SGD && h_optim->kind != TZR_OPT_ADAGRAD && h_optim->kind != TZR_OPT_ROWWISE_ADAGRAD &&
-      h_optim->kind != TZR_OPT_ACCUMULATE && h_optim->kind != TZR_OPT_ADAM &&
-      !bwd_norm_kind(h_optim->kind))
-    return TZR_ERR_UNSUPPORTED;
-  if (bwd_step_kind(h_optim->kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
+  BwdOpt opt;
+  if (const int rc = bwd_opt_from(h_optim, true, &opt)) return rc;
   if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return TZR_ERR_WORKSPACE;
   uint32_t* wcount;
   float* wpart;
@@ -742,25 +733,7 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
   if (n_values == 0 || n_positions == 0 || B == 0) return TZR_OK;
   if (!d_values) return TZR_ERR_INVALID;
   BwdGrads G;
-  for (int i = 0; i < TZR_MAX_DST; ++i) {
-    G.d[i].ptr = 0;
-    G.d[i].stride = 0;
-  }
-  for (int i = 0; i < n_dst; ++i) {
-    if (!h_grads[i].ptr || (h_grads[i].stride & 3) || (h_grads[i].ptr & 15)) return TZR_ERR_INVALID;
-    G.d[i] = h_grads[i];
-  }
-  BwdOpt opt;
-  opt.kind = h_optim->kind;
-  opt.wd_mode = h_optim->weight_decay_mode;
-  opt.clip = h_optim->gradient_clipping;
-  opt.lr = reinterpret_cast<const float*>(h_optim->d_lr);
-  opt.eps = h_optim->eps;
-  opt.wd = h_optim->weight_decay;
-  opt.max_grad = h_optim->max_gradient;
-  opt.beta1 = h_optim->beta1;
-  opt.beta2 = h_optim->beta2;
-  opt.adam = reinterpret_cast<const float*>(h_optim->d_adam);
+  if (const int rc = bwd_grads_from(h_grads, n_dst, &G)) return rc;
   BwdSrcArgs A;
   A.feats = d_feats;
   A.values = d_values;
@@ -781,11 +754,11 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
                        n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
   else if (bwd_norm_kind(opt.kind))
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_norm_kernel);
-  else if (g_tzr_bwd_apply_fast >= 0 && !d_weights && opt.kind == TZR_OPT_ADAGRAD)
+  else if (!d_weights && opt.kind == TZR_OPT_ADAGRAD)
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_adagrad_kernel);
-  else if (g_tzr_bwd_apply_fast >= 0 && !d_weights && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
+  else if (!d_weights && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_rowwise_kernel);
-  else if (g_tzr_bwd_apply_fast >= 0 && !d_weights && opt.kind == TZR_OPT_SGD)
+  else if (!d_weights && opt.kind == TZR_OPT_SGD)
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_sgd_kernel);
   else
     hipLaunchKernelGGL(tzr_bwd_direct_kernel, dim3(grid), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats,
