@@ -78,6 +78,23 @@ extern "C" {
 #define TZR_OPT_LAMB 6
 #define TZR_OPT_PARTIAL_ROWWISE_LAMB 7
 #define TZR_OPT_LARS_SGD 8
+/* The two elementwise kinds without a step counter: "lazy" torch.optim.Adadelta / torch.optim.RMSprop (momentum 0, not
+ * centered), the relation the kinds above have to their dense namesakes: a row is updated only in a step that looks it up,
+ * a row nobody looked up keeps weights AND state (no decay of the running averages).  fbgemm has no public kernel for
+ * either, so these formulas are the definition.  Per touched row, g, w, lr and wd as above:
+ *   g = g + wd w                                          (L2 as torch, after clipping; weight_decay_mode is not read)
+ *   RMSPROP:   s = alpha s + (1-alpha) g^2,               w -= lr g / (sqrt(s) + eps)
+ *   ADADELTA:  s = rho s + (1-rho) g^2,  d = sqrt(a + eps) / sqrt(s + eps) g,  a = rho a + (1-rho) d^2,  w -= lr d
+ * rho / alpha = TzrSparseOptim.beta1 (beta2 is not read), eps = TzrSparseOptim.eps and must be > 0 (TZR_ERR_INVALID
+ * otherwise: with g = 0 both updates are 0 / eps-terms, exactly 0, so a touched row with a zero gradient does not move).
+ * Neither kind has a step: d_adam must be 0 and tzr_sparse_adam_tick is not called.  A call that passes a step state asks
+ * for a stepped (bias-corrected) variant this build has no kernel for: TZR_ERR_UNSUPPORTED, which is also what such a call
+ * got from version 15 before these kinds existed.  State rows, fp32, zero at the start:
+ *   9:  [s(D) | a(D)], m_stride >= 2 D (Adam's layout)      10: [s(D)], m_stride >= D (Adagrad's split layout)
+ * Kinds 9 and 10 are new VALUES of an existing field: no struct, entry point or meaning of an older value changes, so the
+ * ABI version stays 15 (a library of version 15 built before them answers TZR_ERR_UNSUPPORTED).                      */
+#define TZR_OPT_ADADELTA 9
+#define TZR_OPT_RMSPROP 10
 
 #define TZR_WD_NONE 0
 #define TZR_WD_L2 1
@@ -147,12 +164,14 @@ typedef struct TzrSparseOptim {
   int32_t weight_decay_mode; /* TZR_WD_* (rowwise adagrad only)                                 */
   uint64_t d_lr;             /* const float* DEVICE scalar: schedulers mutate it per step
                                 (tzrec/main.py:877-879); graph-replay safe                      */
-  float eps;                 /* fbgemm default 1e-8 [upstream]; not configurable from tzrec     */
+  float eps;                 /* fbgemm default 1e-8 [upstream]; not configurable from tzrec --
+                                except kinds 9, 10: their proto field (1e-6 / 1e-8), must be > 0  */
   float weight_decay;
   float max_gradient;        /* used when gradient_clipping != 0                                */
   int32_t gradient_clipping;
   float beta1;               /* TZR_OPT_ADAM and kinds 5-7 (protos/optimizer.proto:89-96);
-                                TZR_OPT_LARS_SGD: the momentum mu                               */
+                                TZR_OPT_LARS_SGD: the momentum mu; TZR_OPT_ADADELTA: rho;
+                                TZR_OPT_RMSPROP: alpha                                          */
   float beta2;               /* TZR_OPT_LARS_SGD: the trust coefficient eta (fbgemm default 0.001) */
   uint64_t d_adam;           /* TZR_OPT_ADAM, kinds 5-7: float[4] DEVICE state {step, 1 - beta1^step,
                                 1 - beta2^step, -}, advanced once per training step by

@@ -39,7 +39,9 @@ class Timers:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--opt", default="adagrad")
+    ap.add_argument("--opt", default="adagrad",
+                    choices=["sgd", "adagrad", "rowwise_adagrad", "adam", "partial_rowwise_adam", "lamb", "partial_rowwise_lamb", "lars_sgd",
+                             "adadelta", "rmsprop"])
     ap.add_argument("--B", default="65536")
     ap.add_argument("--dist", default="uniform")
     ap.add_argument("--iters", type=int, default=20)

@@ -176,11 +176,23 @@ def _num_embeddings(f: Msg, name: str) -> int:
 
 def sparse_optimizer_from_config(opt: Msg) -> SparseOptimizerConfig:
     """create_sparse_optimizer mapping (tzrec/optim/optimizer_builder.py:30-97) for the kinds this
-    library fuses; field defaults from protos/optimizer.proto:76-139."""
+    library fuses (all ten of the oneof); field defaults from protos/optimizer.proto:76-157."""
     table = {"sgd_optimizer": "sgd", "adagrad_optimizer": "adagrad", "rowwise_adagrad_optimizer": "rowwise_adagrad",
              "adam_optimizer": "adam", "partial_rowwise_adam_optimizer": "partial_rowwise_adam",
              "lamb_optimizer": "lamb", "partial_rowwise_lamb_optimizer": "partial_rowwise_lamb",
              "lars_sgd_optimizer": "lars_sgd"}
+    # the two kinds with hyper-parameters of their own (protos/optimizer.proto:141-157): eps IS a field of theirs
+    if opt.has("adadelta_optimizer") or opt.has("rmsprop_optimizer"):
+        kind = "adadelta" if opt.has("adadelta_optimizer") else "rmsprop"
+        m = opt.one(f"{kind}_optimizer")
+        eps = float(m.one("eps", 1e-6 if kind == "adadelta" else 1e-8))
+        if not eps > 0.0:
+            raise ValueError(f"{kind}_optimizer: eps must be > 0 (got {eps})")
+        return SparseOptimizerConfig(
+            kind=kind, lr=float(m.one("lr", 0.002)), eps=eps, weight_decay=float(m.one("weight_decay", 0.0)),
+            gradient_clipping=bool(m.one("gradient_clipping", False)), max_gradient=float(m.one("max_gradient", 1.0)),
+            rho=float(m.one("rho", 0.95)), alpha=float(m.one("alpha", 0.99)),
+        )
     for key, kind in table.items():
         if opt.has(key):
             m = opt.one(key)

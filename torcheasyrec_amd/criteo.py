@@ -82,7 +82,8 @@ def algorithmic_bytes(kjt_values: np.ndarray, B: int, rows: List[int], dim: int 
     bwd rowwise = 4*sumD*B + 8N + (8D+8)*U, with U = distinct (table,row) pairs in the batch.
     The norm kinds (weights and the state they update, read and written once per touched row):
     bwd lamb = 4*sumD*B + 8N + 24D*U; partial row-wise adam / lamb = 4*sumD*B + 8N + (16D+8)*U;
-    lars_sgd = 4*sumD*B + 8N + 16D*U."""
+    lars_sgd = 4*sumD*B + 8N + 16D*U.  The elementwise kinds without a step: rmsprop = 4*sumD*B + 8N + 16D*U
+    (Adagrad's bytes), adadelta = 4*sumD*B + 8N + 24D*U (weights and two state rows)."""
     F = len(rows)
     N = len(kjt_values)
     U = 0
@@ -100,6 +101,10 @@ def algorithmic_bytes(kjt_values: np.ndarray, B: int, rows: List[int], dim: int 
         bwd = 4 * sumD * B + 8 * N + (16 * dim + 8) * U
     elif optimizer == "lars_sgd":
         bwd = 4 * sumD * B + 8 * N + 16 * dim * U
+    elif optimizer == "rmsprop":
+        bwd = 4 * sumD * B + 8 * N + 16 * dim * U
+    elif optimizer == "adadelta":
+        bwd = 4 * sumD * B + 8 * N + 24 * dim * U
     else:
         bwd = 4 * sumD * B + 8 * N + 8 * dim * U
     return {"N": N, "U": U, "fwd": float(fwd), "bwd": float(bwd)}

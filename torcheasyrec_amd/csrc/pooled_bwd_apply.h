@@ -21,22 +21,27 @@ struct BwdOpt {
 #define BWD_FAM_LEGACY 0  // SGD, Adagrad, row-wise Adagrad, accumulate (the code that was there before Adam)
 #define BWD_FAM_ADAM 1    // TZR_OPT_ADAM
 #define BWD_FAM_NORM 2    // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS-SGD: row norms / a row's second moment
+#define BWD_FAM_ELEM 3    // Adadelta, RMSprop: elementwise running averages, no step state, no row norm
 
 inline bool bwd_norm_kind(int kind) { return kind >= TZR_OPT_PARTIAL_ROWWISE_ADAM && kind <= TZR_OPT_LARS_SGD; }
+inline bool bwd_elem_kind(int kind) { return kind == TZR_OPT_ADADELTA || kind == TZR_OPT_RMSPROP; }
 // the kinds that read the step state d_adam (ticked by tzr_sparse_adam_tick)
 inline bool bwd_step_kind(int kind) { return kind == TZR_OPT_ADAM || (bwd_norm_kind(kind) && kind != TZR_OPT_LARS_SGD); }
 
-// The optimizer arguments of a backward entry point, checked and copied for the kernels.  TZR_ERR_INVALID: no learning rate, or
-// a kind that reads the step state without d_adam; TZR_ERR_UNSUPPORTED: a kind the row update does not have (TZR_OPT_ACCUMULATE
+// The optimizer arguments of a backward entry point, checked and copied for the kernels.  TZR_ERR_INVALID: no learning rate,
+// a kind that reads the step state without d_adam, or Adadelta / RMSprop with eps <= 0; TZR_ERR_UNSUPPORTED: Adadelta / RMSprop
+// WITH a step state (a stepped variant nobody built; what kinds 9 and 10 answered to such a call before they existed), or: a kind the row update does not have (TZR_OPT_ACCUMULATE
 // among them where the caller does not allow it: the dense update of replicated tables).  Every step kind is a supported
 // kind, so the order of the last two checks decides nothing.
 inline int bwd_opt_from(const TzrSparseOptim* h_optim, bool allow_accumulate, BwdOpt* opt) {
   if (!h_optim->d_lr) return TZR_ERR_INVALID;
   const int kind = h_optim->kind;
   if (kind != TZR_OPT_SGD && kind != TZR_OPT_ADAGRAD && kind != TZR_OPT_ROWWISE_ADAGRAD && kind != TZR_OPT_ADAM &&
-      !(allow_accumulate && kind == TZR_OPT_ACCUMULATE) && !bwd_norm_kind(kind))
+      !(allow_accumulate && kind == TZR_OPT_ACCUMULATE) && !bwd_norm_kind(kind) && !bwd_elem_kind(kind))
     return TZR_ERR_UNSUPPORTED;
   if (bwd_step_kind(kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
+  if (bwd_elem_kind(kind) && h_optim->d_adam) return TZR_ERR_UNSUPPORTED;
+  if (bwd_elem_kind(kind) && !(h_optim->eps > 0.f)) return TZR_ERR_INVALID;  // (a zero-gradient row would compute 0 / 0)
   opt->kind = kind;
   opt->wd_mode = h_optim->weight_decay_mode;
   opt->clip = h_optim->gradient_clipping;
@@ -207,12 +212,57 @@ __device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const Bwd
   }
 }
 
+// One element of the row update of BWD_FAM_ELEM (formulas: include/tzrec_hip.h at TZR_OPT_ADADELTA): s = the running average
+// of g^2, a = Adadelta's running average of the squared steps (not read under RMSprop); returns the new weight.  Every
+// multiply that feeds an add is written as fmaf, so -ffp-contract has nothing left to decide: the planned, the cells and the
+// direct kernel and the replicated-table update round every element the same way, whatever surrounds the inlined code.
+template <bool ADADELTA>
+__device__ __forceinline__ float bwd_elem1(float g, float w, float& s, float& a, float lr, float rho, float eps, float wd) {
+  g = fmaf(wd, w, g);
+  s = fmaf(rho, s, ((1.0f - rho) * g) * g);
+  if constexpr (ADADELTA) {
+    const float d = (sqrtf(a + eps) / sqrtf(s + eps)) * g;
+    a = fmaf(rho, a, ((1.0f - rho) * d) * d);
+    return fmaf(-lr, d, w);
+  } else {
+    return w - (lr * g) / (sqrtf(s) + eps);
+  }
+}
+
+// The row update of BWD_FAM_ELEM.  `s4` = the row's s chunk (bwd_load_state), g already clipped.  Nothing is shared between
+// lanes; Adadelta's second state chunk a(D) sits D floats behind s, as Adam's exp_avg_sq behind exp_avg, and is loaded here.
+__device__ __forceinline__ void bwd_apply_row_elem(const TzrTable& tb, const BwdOpt& opt, float lr, int64_t row, int c, float4 g,
+                                                   float4 w4, float4 s4, bool active) {
+  if (!active) return;
+  float* const sp = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c;
+  const float rho = opt.beta1, eps = opt.eps, wd = opt.wd;
+  if (opt.kind == TZR_OPT_ADADELTA) {  // (kernel-uniform)
+    float* const ap = sp + tb.dim;
+    float4 a4 = tzr_ld4(ap);
+    w4.x = bwd_elem1<true>(g.x, w4.x, s4.x, a4.x, lr, rho, eps, wd);
+    w4.y = bwd_elem1<true>(g.y, w4.y, s4.y, a4.y, lr, rho, eps, wd);
+    w4.z = bwd_elem1<true>(g.z, w4.z, s4.z, a4.z, lr, rho, eps, wd);
+    w4.w = bwd_elem1<true>(g.w, w4.w, s4.w, a4.w, lr, rho, eps, wd);
+    tzr_st4(sp, s4);
+    tzr_st4(ap, a4);
+  } else {  // RMSprop
+    float unused = 0.f;
+    w4.x = bwd_elem1<false>(g.x, w4.x, s4.x, unused, lr, rho, eps, wd);
+    w4.y = bwd_elem1<false>(g.y, w4.y, s4.y, unused, lr, rho, eps, wd);
+    w4.z = bwd_elem1<false>(g.z, w4.z, s4.z, unused, lr, rho, eps, wd);
+    w4.w = bwd_elem1<false>(g.w, w4.w, s4.w, unused, lr, rho, eps, wd);
+    tzr_st4(sp, s4);
+  }
+  tzr_stw4(reinterpret_cast<void*>(tb.w), tb.w_dtype, row * (int64_t)tb.w_stride + 4 * c, w4);
+}
+
 // Prefetch of the elementwise optimizer state of (row, chunk c): issued together with the weight
 // load, before the reduction, so the update itself waits on no memory.
 // (The family FAM is a template parameter of everything below: with the Adam arithmetic as one more run-time
 // branch of the row update the reduce kernel needed 99 instead of 78 VGPRs, one wave per SIMD less,
 // and the DLRM-Criteo Adagrad step lost 17 us -- profiles/r01k.  The BWD_FAM_LEGACY instantiations are the
-// code that was there before.  Every kind of BWD_FAM_NORM keeps exp_avg / momentum m(D) at the front of its state row.)
+// code that was there before.  Every kind of BWD_FAM_NORM keeps exp_avg / momentum m(D) at the front of its state row,
+// both kinds of BWD_FAM_ELEM the running average s(D).)
 template <int FAM>
 __device__ __forceinline__ float4 bwd_load_state(const TzrTable& tb, const BwdOpt& opt, int64_t row,
                                                  int c, bool active) {
@@ -255,6 +305,10 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
   const int64_t woff = row * (int64_t)tb.w_stride + 4 * c;
   if constexpr (FAM == BWD_FAM_NORM) {
     bwd_apply_row_norm(tb, opt, lr, row, c, g, w4, m4, active, lg, lane_in_group, lane);
+    return;
+  }
+  if constexpr (FAM == BWD_FAM_ELEM) {
+    bwd_apply_row_elem(tb, opt, lr, row, c, g, w4, m4, active);
     return;
   }
   if constexpr (FAM == BWD_FAM_ADAM) {

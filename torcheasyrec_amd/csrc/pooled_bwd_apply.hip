@@ -507,6 +507,8 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
     TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ADAM>));  // Adam holds two state rows per lane: no registers for a second tile
   } else if (bwd_norm_kind(opt.kind)) {
     TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_NORM>));
+  } else if (bwd_elem_kind(opt.kind)) {
+    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ELEM>));
   } else {
     // 7 waves per SIMD = 1792 workgroups resident: the whole unit grid of a B = 65536 Criteo step (1691) runs in
     // one wave of workgroups.  At 6 (77 VGPRs, what the compiler picks unasked) the last 155 units waited for a
@@ -593,6 +595,10 @@ static int dense_rows_update(const TzrTable* d_tables, int n_tables, const int64
                        d_acc, dim, opt, clear);
   } else if (bwd_norm_kind(opt.kind)) {
     hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_NORM>), dim3(grid), dim3(BWD_THREADS), 0,
+                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
+                       d_acc, dim, opt, clear);
+  } else if (bwd_elem_kind(opt.kind)) {
+    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_ELEM>), dim3(grid), dim3(BWD_THREADS), 0,
                        static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
                        d_acc, dim, opt, clear);
   } else {

@@ -925,6 +925,7 @@ TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_sgd_kernel, BWD_FAM_LEGACY, TZR_OPT_S
 TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_general_kernel, BWD_FAM_LEGACY, 0, TZR_WAVES_PER_EU(7))
 TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_adam_kernel, BWD_FAM_ADAM, 0, )
 TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_norm_kernel, BWD_FAM_NORM, 0, )  // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS
+TZR_CELLS_APPLY_KERNEL(tzr_bwd_cells_apply_elem_kernel, BWD_FAM_ELEM, 0, )  // Adadelta, RMSprop
 
 // ------------------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -1054,6 +1055,8 @@ extern "C" int tzr_pooled_bwd_cells_apply(const TzrTable* d_tables, const TzrFea
     TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_adam_kernel);
   } else if (bwd_norm_kind(opt.kind)) {
     TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_norm_kernel);
+  } else if (bwd_elem_kind(opt.kind)) {
+    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_elem_kernel);
   } else if (!fast_shape) {
     TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_general_kernel);
   } else if (opt.kind == TZR_OPT_ADAGRAD) {

@@ -657,6 +657,7 @@ __device__ __forceinline__ void bwd_direct_body(
 BWD_DIRECT_KERNEL(tzr_bwd_direct_kernel, BWD_FAM_LEGACY, 4, 2, 0)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_adam_kernel, BWD_FAM_ADAM, 3, 2, 0)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_norm_kernel, BWD_FAM_NORM, 3, 2, 0)  // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS
+BWD_DIRECT_KERNEL(tzr_bwd_direct_elem_kernel, BWD_FAM_ELEM, 3, 2, 0)  // Adadelta, RMSprop
 // the optimizer kind at compile time: units of fp32 single-key tables take the fast tile loop
 BWD_DIRECT_KERNEL(tzr_bwd_direct_adagrad_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ADAGRAD)
 BWD_DIRECT_KERNEL(tzr_bwd_direct_rowwise_kernel, BWD_FAM_LEGACY, 4, 2, TZR_OPT_ROWWISE_ADAGRAD)
@@ -754,6 +755,8 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
                        n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
   else if (bwd_norm_kind(opt.kind))
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_norm_kernel);
+  else if (bwd_elem_kind(opt.kind))
+    BWD_DIRECT_LAUNCH(tzr_bwd_direct_elem_kernel);
   else if (!d_weights && opt.kind == TZR_OPT_ADAGRAD)
     BWD_DIRECT_LAUNCH(tzr_bwd_direct_adagrad_kernel);
   else if (!d_weights && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)

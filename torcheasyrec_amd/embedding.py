@@ -60,7 +60,10 @@ class SparseOptimizerConfig:
     optimizer, bias-corrected as fbgemm's split Adam), ``partial_rowwise_adam_optimizer`` ->
     "partial_rowwise_adam" and ``partial_rowwise_lamb_optimizer`` -> "partial_rowwise_lamb" (state
     [rows, D + 4]: exp_avg | one exp_avg_sq | 3 floats of padding), ``lamb_optimizer`` -> "lamb"
-    (state [rows, 2 D] as Adam), ``lars_sgd_optimizer`` -> "lars_sgd" (state [rows, D]: momentum).
+    (state [rows, 2 D] as Adam), ``lars_sgd_optimizer`` -> "lars_sgd" (state [rows, D]: momentum),
+    ``adadelta_optimizer`` -> "adadelta" (state [rows, 2 D]: square_avg | acc_delta) and
+    ``rmsprop_optimizer`` -> "rmsprop" (state [rows, D]: square_avg): lazy torch.optim.Adadelta / RMSprop
+    (momentum 0, not centered), no step counter, ``eps`` as configured (it must be > 0).
     The Adam-family kinds share Adam's step counter; formulas in include/tzrec_hip.h."""
 
     kind: str = "adagrad"
@@ -75,20 +78,29 @@ class SparseOptimizerConfig:
     beta2: float = 0.999
     momentum: float = 0.9  # lars_sgd: mu
     eta: float = 0.001  # lars_sgd: trust coefficient (fbgemm default [upstream]; tzrec does not expose it)
+    rho: float = 0.95  # adadelta: decay of both running averages (protos/optimizer.proto:141-148)
+    alpha: float = 0.99  # rmsprop: decay of the running average of g^2 (protos/optimizer.proto:150-157)
 
 
 _OPT_KIND = {"sgd": _lib.OPT_SGD, "adagrad": _lib.OPT_ADAGRAD, "rowwise_adagrad": _lib.OPT_ROWWISE_ADAGRAD,
              "adam": _lib.OPT_ADAM, "partial_rowwise_adam": _lib.OPT_PARTIAL_ROWWISE_ADAM, "lamb": _lib.OPT_LAMB,
-             "partial_rowwise_lamb": _lib.OPT_PARTIAL_ROWWISE_LAMB, "lars_sgd": _lib.OPT_LARS_SGD}
+             "partial_rowwise_lamb": _lib.OPT_PARTIAL_ROWWISE_LAMB, "lars_sgd": _lib.OPT_LARS_SGD,
+             "adadelta": _lib.OPT_ADADELTA, "rmsprop": _lib.OPT_RMSPROP}
 _WD_MODE = {"none": _lib.WD_NONE, "l2": _lib.WD_L2, "decouple": _lib.WD_DECOUPLE}
 # the kinds that read the device step state {step, 1 - b1^step, 1 - b2^step}, advanced once per step (begin_step)
 TICKING_KINDS = frozenset({"adam", "partial_rowwise_adam", "lamb", "partial_rowwise_lamb"})
+# the kinds whose eps comes from the config and divides by itself alone on a zero-gradient row: it must be positive
+CONFIGURED_EPS_KINDS = frozenset({"adadelta", "rmsprop"})
 
 
 def _state_shape(kind: Optional[str], rows: int, D: int) -> Optional[Tuple[int, int]]:
     """[rows, width] of the separate fp32 state tensor of the kinds that always have one (include/tzrec_hip.h)"""
     if kind in ("adam", "lamb"):  # [exp_avg | exp_avg_sq]
         return (rows, 2 * D)
+    if kind == "adadelta":  # [square_avg | acc_delta]
+        return (rows, 2 * D)
+    if kind == "rmsprop":  # [square_avg]
+        return (rows, D)
     if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):  # [exp_avg | exp_avg_sq | pad(3)]: float4 aligned
         return (rows, D + 4)
     if kind == "lars_sgd":  # [momentum]
@@ -101,9 +113,9 @@ def check_state_stride(kind: Optional[str], D: int, m_stride: int) -> None:
     array and cannot check it; a stride too small would put one row's state into the next row's."""
     if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):
         ok = m_stride >= D + 1 and m_stride % 4 == 0
-    elif kind == "lamb":
+    elif kind in ("lamb", "adadelta"):
         ok = m_stride >= 2 * D
-    elif kind == "lars_sgd":
+    elif kind in ("lars_sgd", "rmsprop"):
         ok = m_stride >= D
     else:
         return
@@ -118,6 +130,12 @@ class FusedSparseOptimizer:
     captured hipGraph sees new learning rates without re-capture."""
 
     def __init__(self, cfg: SparseOptimizerConfig, ebc: "EmbeddingBagCollection") -> None:
+        if cfg.kind in CONFIGURED_EPS_KINDS:
+            if not cfg.eps > 0.0:
+                raise ValueError(f"{cfg.kind}: eps must be > 0 (got {cfg.eps}): a touched row with a zero gradient divides by it alone")
+            decay = cfg.rho if cfg.kind == "adadelta" else cfg.alpha
+            if not 0.0 <= decay < 1.0:
+                raise ValueError(f"{cfg.kind}: {'rho' if cfg.kind == 'adadelta' else 'alpha'} must be in [0, 1) (got {decay})")
         self.cfg = cfg
         self._ebc = ebc
         self.param_groups = [{"lr": float(cfg.lr), "params": list(ebc.table_weights().values())}]
@@ -148,6 +166,8 @@ class FusedSparseOptimizer:
         opt.eps, opt.weight_decay, opt.max_gradient = cfg.eps, cfg.weight_decay, cfg.max_gradient
         opt.gradient_clipping = 1 if cfg.gradient_clipping else 0
         opt.beta1, opt.beta2 = (cfg.momentum, cfg.eta) if cfg.kind == "lars_sgd" else (cfg.beta1, cfg.beta2)
+        if cfg.kind in CONFIGURED_EPS_KINDS:  # rho / alpha travel in the beta1 slot (include/tzrec_hip.h); beta2 is not read
+            opt.beta1 = cfg.rho if cfg.kind == "adadelta" else cfg.alpha
         opt.d_adam = _lib.ptr(self.adam_state(device)) if cfg.kind in TICKING_KINDS else 0
         return opt
 

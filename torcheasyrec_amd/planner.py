@@ -35,7 +35,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 GB = 1 << 30
-_NORM_KINDS = ("partial_rowwise_adam", "lamb", "partial_rowwise_lamb", "lars_sgd")  # their state is priced by _state_bytes_dim
+_NORM_KINDS = ("partial_rowwise_adam", "lamb", "partial_rowwise_lamb", "lars_sgd", "adadelta", "rmsprop")  # their state is priced by _state_bytes_dim
 
 
 class PlannerError(RuntimeError):
@@ -121,7 +121,7 @@ class TableSpec:
     embedding_dim: int
     feature_names: Sequence[str] = ()
     pooling_factor: float = 1.0  # ids per bag
-    optimizer: str = "adagrad"  # adagrad | rowwise_adagrad | sgd | adam | partial_rowwise_adam | lamb | partial_rowwise_lamb | lars_sgd
+    optimizer: str = "adagrad"  # adagrad | rowwise_adagrad | sgd | adam | partial_rowwise_adam | lamb | partial_rowwise_lamb | lars_sgd | adadelta | rmsprop
     bytes_per_element: int = 4
     # storage layout of the collection the plan is for (EmbeddingBagCollection(row_layout=...), default "interleaved"):
     # interleaved fp32 rows are [w(D) | state] with a 2 D row stride -- ALSO for row-wise Adagrad, whose one scalar per
@@ -146,11 +146,11 @@ class EmbeddingEnumerator:
         if t.optimizer == "rowwise_adagrad":
             padded = t.row_layout == "interleaved" and t.bytes_per_element == 4  # (FP16 tables are never interleaved)
             return rows * dim * 4 if padded else rows * 4
-        if t.optimizer in ("adam", "lamb"):
+        if t.optimizer in ("adam", "lamb", "adadelta"):
             return rows * dim * 8
         if t.optimizer in ("partial_rowwise_adam", "partial_rowwise_lamb"):
             return rows * (dim + 4) * 4
-        if t.optimizer == "lars_sgd":
+        if t.optimizer in ("lars_sgd", "rmsprop"):
             return rows * dim * 4
         return 0
 
