@@ -8,6 +8,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import opt_kinds
 from .embedding import EmbeddingBagConfig
 from .sparse import KeyedJaggedTensor
 
@@ -91,20 +92,5 @@ def algorithmic_bytes(kjt_values: np.ndarray, B: int, rows: List[int], dim: int 
         U += len(np.unique(kjt_values[t * B:(t + 1) * B]))
     sumD = F * dim
     fwd = 8 * N + 4 * F * B + 4 * dim * U + 4 * sumD * B
-    if optimizer == "adagrad":
-        bwd = 4 * sumD * B + 8 * N + 16 * dim * U
-    elif optimizer == "rowwise_adagrad":
-        bwd = 4 * sumD * B + 8 * N + (8 * dim + 8) * U
-    elif optimizer == "lamb":
-        bwd = 4 * sumD * B + 8 * N + 24 * dim * U
-    elif optimizer in ("partial_rowwise_adam", "partial_rowwise_lamb"):
-        bwd = 4 * sumD * B + 8 * N + (16 * dim + 8) * U
-    elif optimizer == "lars_sgd":
-        bwd = 4 * sumD * B + 8 * N + 16 * dim * U
-    elif optimizer == "rmsprop":
-        bwd = 4 * sumD * B + 8 * N + 16 * dim * U
-    elif optimizer == "adadelta":
-        bwd = 4 * sumD * B + 8 * N + 24 * dim * U
-    else:
-        bwd = 4 * sumD * B + 8 * N + 8 * dim * U
+    bwd = 4 * sumD * B + 8 * N + opt_kinds.of(optimizer).bwd_row_bytes(dim) * U
     return {"N": N, "U": U, "fwd": float(fwd), "bwd": float(bwd)}

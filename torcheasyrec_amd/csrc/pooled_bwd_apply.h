@@ -22,11 +22,41 @@ struct BwdOpt {
 #define BWD_FAM_ADAM 1    // TZR_OPT_ADAM
 #define BWD_FAM_NORM 2    // partial row-wise Adam, LAMB, partial row-wise LAMB, LARS-SGD: row norms / a row's second moment
 #define BWD_FAM_ELEM 3    // Adadelta, RMSprop: elementwise running averages, no step state, no row norm
+#define BWD_FAM_NONE (-1)  // not a kind the row update has
 
-inline bool bwd_norm_kind(int kind) { return kind >= TZR_OPT_PARTIAL_ROWWISE_ADAM && kind <= TZR_OPT_LARS_SGD; }
-inline bool bwd_elem_kind(int kind) { return kind == TZR_OPT_ADADELTA || kind == TZR_OPT_RMSPROP; }
-// the kinds that read the step state d_adam (ticked by tzr_sparse_adam_tick)
+// THE kind table of the host side.  Everything else the entry points know about a kind (the predicates below, the kernel
+// variant a launch takes) is derived from it.
+inline int bwd_family(int kind, bool allow_accumulate) {
+  switch (kind) {
+    case TZR_OPT_SGD: case TZR_OPT_ADAGRAD: case TZR_OPT_ROWWISE_ADAGRAD: return BWD_FAM_LEGACY;
+    case TZR_OPT_ACCUMULATE: return allow_accumulate ? BWD_FAM_LEGACY : BWD_FAM_NONE;
+    case TZR_OPT_ADAM: return BWD_FAM_ADAM;
+    case TZR_OPT_PARTIAL_ROWWISE_ADAM: case TZR_OPT_LAMB: case TZR_OPT_PARTIAL_ROWWISE_LAMB: case TZR_OPT_LARS_SGD: return BWD_FAM_NORM;
+    case TZR_OPT_ADADELTA: case TZR_OPT_RMSPROP: return BWD_FAM_ELEM;
+  }
+  return BWD_FAM_NONE;
+}
+inline bool bwd_norm_kind(int kind) { return bwd_family(kind, false) == BWD_FAM_NORM; }
+inline bool bwd_elem_kind(int kind) { return bwd_family(kind, false) == BWD_FAM_ELEM; }
+// the kinds that read the step state d_adam (ticked by tzr_sparse_adam_tick): the ones that keep Adam's moments -- Adam and
+// the norm family but for LARS-SGD, whose state is a momentum
 inline bool bwd_step_kind(int kind) { return kind == TZR_OPT_ADAM || (bwd_norm_kind(kind) && kind != TZR_OPT_LARS_SGD); }
+
+// The kernel variants of a backward entry point: one per family, and for the legacy family the three kinds that have a
+// compile-time fast form (bwd_apply_row_fast) next to the general one.  An entry point holds one kernel per variant, in
+// this order, and computes `fast_shape` (the conditions differ: what its fast memory side is written for) itself.
+enum { BWD_VAR_GENERAL, BWD_VAR_FAST_SGD, BWD_VAR_FAST_ADAGRAD, BWD_VAR_FAST_ROWWISE, BWD_VAR_ADAM, BWD_VAR_NORM, BWD_VAR_ELEM, BWD_VAR_COUNT };
+inline int bwd_variant(int kind, bool fast_shape) {  // (kind: one bwd_opt_from accepted)
+  switch (bwd_family(kind, true)) {
+    case BWD_FAM_ADAM: return BWD_VAR_ADAM;
+    case BWD_FAM_NORM: return BWD_VAR_NORM;
+    case BWD_FAM_ELEM: return BWD_VAR_ELEM;
+  }
+  if (fast_shape && kind == TZR_OPT_SGD) return BWD_VAR_FAST_SGD;
+  if (fast_shape && kind == TZR_OPT_ADAGRAD) return BWD_VAR_FAST_ADAGRAD;
+  if (fast_shape && kind == TZR_OPT_ROWWISE_ADAGRAD) return BWD_VAR_FAST_ROWWISE;
+  return BWD_VAR_GENERAL;
+}
 
 // The optimizer arguments of a backward entry point, checked and copied for the kernels.  TZR_ERR_INVALID: no learning rate,
 // a kind that reads the step state without d_adam, or Adadelta / RMSprop with eps <= 0; TZR_ERR_UNSUPPORTED: Adadelta / RMSprop
@@ -36,9 +66,7 @@ inline bool bwd_step_kind(int kind) { return kind == TZR_OPT_ADAM || (bwd_norm_k
 inline int bwd_opt_from(const TzrSparseOptim* h_optim, bool allow_accumulate, BwdOpt* opt) {
   if (!h_optim->d_lr) return TZR_ERR_INVALID;
   const int kind = h_optim->kind;
-  if (kind != TZR_OPT_SGD && kind != TZR_OPT_ADAGRAD && kind != TZR_OPT_ROWWISE_ADAGRAD && kind != TZR_OPT_ADAM &&
-      !(allow_accumulate && kind == TZR_OPT_ACCUMULATE) && !bwd_norm_kind(kind) && !bwd_elem_kind(kind))
-    return TZR_ERR_UNSUPPORTED;
+  if (bwd_family(kind, allow_accumulate) == BWD_FAM_NONE) return TZR_ERR_UNSUPPORTED;
   if (bwd_step_kind(kind) && !h_optim->d_adam) return TZR_ERR_INVALID;
   if (bwd_elem_kind(kind) && h_optim->d_adam) return TZR_ERR_UNSUPPORTED;
   if (bwd_elem_kind(kind) && !(h_optim->eps > 0.f)) return TZR_ERR_INVALID;  // (a zero-gradient row would compute 0 / 0)
@@ -149,6 +177,56 @@ __device__ __forceinline__ float bwd_group_sum(float v, int lg, int lane_in_grou
 
 __device__ __forceinline__ float bwd_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
+// ---- the row arithmetic every form of the update shares (the loads and stores stay with the callers) ----
+__device__ __forceinline__ float4 bwd_clip(const BwdOpt& opt, float4 g) {
+  if (opt.clip) {
+    g.x = fminf(fmaxf(g.x, -opt.max_grad), opt.max_grad);
+    g.y = fminf(fmaxf(g.y, -opt.max_grad), opt.max_grad);
+    g.z = fminf(fmaxf(g.z, -opt.max_grad), opt.max_grad);
+    g.w = fminf(fmaxf(g.w, -opt.max_grad), opt.max_grad);
+  }
+  return g;
+}
+
+// Adam's moments: m = b1 m + (1-b1) g (every kind that ticks), v = b2 v + (1-b2) g^2 (Adam, LAMB: the elementwise v)
+__device__ __forceinline__ void bwd_adam_m(float4 g, float b1, float4& m4) {
+  m4.x = b1 * m4.x + (1.0f - b1) * g.x; m4.y = b1 * m4.y + (1.0f - b1) * g.y;
+  m4.z = b1 * m4.z + (1.0f - b1) * g.z; m4.w = b1 * m4.w + (1.0f - b1) * g.w;
+}
+__device__ __forceinline__ void bwd_adam_v(float4 g, float b2, float4& v4) {
+  v4.x = b2 * v4.x + (1.0f - b2) * g.x * g.x; v4.y = b2 * v4.y + (1.0f - b2) * g.y * g.y;
+  v4.z = b2 * v4.z + (1.0f - b2) * g.z * g.z; v4.w = b2 * v4.w + (1.0f - b2) * g.w * g.w;
+}
+
+// Adagrad: m += g^2, then (the callers store m in between, as they always did) w -= lr g / (sqrt(m) + eps)
+__device__ __forceinline__ void bwd_adagrad_m(float4 g, float4& m4) {
+  m4.x += g.x * g.x; m4.y += g.y * g.y; m4.z += g.z * g.z; m4.w += g.w * g.w;
+}
+__device__ __forceinline__ void bwd_adagrad_w(const BwdOpt& opt, float lr, float4 g, float4 m4, float4& w4) {
+  w4.x -= lr * g.x / (sqrtf(m4.x) + opt.eps);
+  w4.y -= lr * g.y / (sqrtf(m4.y) + opt.eps);
+  w4.z -= lr * g.z / (sqrtf(m4.z) + opt.eps);
+  w4.w -= lr * g.w / (sqrtf(m4.w) + opt.eps);
+}
+
+// Row-wise Adagrad: the row's new scalar (returned) out of its old one `mold` and the row's sum of squares, and the new weights
+__device__ __forceinline__ float bwd_rowwise_step(const BwdOpt& opt, float lr, int dim, float mold, float ss, float4 g, float4& w4) {
+  const float mnew = mold + ss / (float)dim;
+  const float mult = lr / (sqrtf(mnew) + opt.eps);
+  float corr = 1.0f;
+  if (opt.wd_mode == TZR_WD_L2) corr = 1.0f - mult * opt.wd;
+  else if (opt.wd_mode == TZR_WD_DECOUPLE) corr = 1.0f - lr * opt.wd;
+  w4.x = corr * w4.x - mult * g.x;
+  w4.y = corr * w4.y - mult * g.y;
+  w4.z = corr * w4.z - mult * g.z;
+  w4.w = corr * w4.w - mult * g.w;
+  return mnew;
+}
+
+__device__ __forceinline__ void bwd_sgd_step(float4 g, float lr, float4& w4) {
+  w4.x -= lr * g.x; w4.y -= lr * g.y; w4.z -= lr * g.z; w4.w -= lr * g.w;
+}
+
 // The row update of BWD_FAM_NORM (formulas: include/tzrec_hip.h at TZR_OPT_PARTIAL_ROWWISE_ADAM).  `m4` = the row's m
 // chunk (bwd_load_state), g already clipped.  All 64 lanes call: the row norms and the partial row-wise second moment are
 // sums over the row's `lg` lanes (inactive lanes add 0); the partial row-wise v is read and written by the group's first
@@ -176,15 +254,13 @@ __device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const Bwd
   }
   const float b1 = opt.beta1, b2 = opt.beta2;
   const float c1 = opt.adam[1], c2 = opt.adam[2];
-  m4.x = b1 * m4.x + (1.0f - b1) * g.x; m4.y = b1 * m4.y + (1.0f - b1) * g.y;
-  m4.z = b1 * m4.z + (1.0f - b1) * g.z; m4.w = b1 * m4.w + (1.0f - b1) * g.w;
+  bwd_adam_m(g, b1, m4);
   float4 v4;
   float* const vrow = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + tb.dim;  // the partial row-wise v
   float vnew = 0.f;
   if (kind == TZR_OPT_LAMB) {
     v4 = active ? tzr_ld4(mp + tb.dim) : tzr_zero4();
-    v4.x = b2 * v4.x + (1.0f - b2) * g.x * g.x; v4.y = b2 * v4.y + (1.0f - b2) * g.y * g.y;
-    v4.z = b2 * v4.z + (1.0f - b2) * g.z * g.z; v4.w = b2 * v4.w + (1.0f - b2) * g.w * g.w;
+    bwd_adam_v(g, b2, v4);
   } else {  // partial row-wise: one v per row, the mean of g^2 over the row's columns
     const float ss = bwd_group_sum(active ? bwd_dot4(g, g) : 0.f, lg, lane_in_group, lane);
     float vold = (active && lane_in_group == 0) ? *vrow : 0.f;
@@ -295,12 +371,7 @@ template <int FAM>
 __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& opt, float lr,
                                               int64_t row, int c, float4 g, float4 w4, float4 m4,
                                               bool active, int lg, int lane_in_group, int lane) {
-  if (opt.clip) {
-    g.x = fminf(fmaxf(g.x, -opt.max_grad), opt.max_grad);
-    g.y = fminf(fmaxf(g.y, -opt.max_grad), opt.max_grad);
-    g.z = fminf(fmaxf(g.z, -opt.max_grad), opt.max_grad);
-    g.w = fminf(fmaxf(g.w, -opt.max_grad), opt.max_grad);
-  }
+  g = bwd_clip(opt, g);
   void* const wbase = reinterpret_cast<void*>(tb.w);
   const int64_t woff = row * (int64_t)tb.w_stride + 4 * c;
   if constexpr (FAM == BWD_FAM_NORM) {
@@ -320,10 +391,8 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
       float4 v4 = tzr_ld4(vp);
       const float b1 = opt.beta1, b2 = opt.beta2;
       const float c1 = opt.adam[1], c2 = opt.adam[2];
-      m4.x = b1 * m4.x + (1.0f - b1) * g.x; m4.y = b1 * m4.y + (1.0f - b1) * g.y;
-      m4.z = b1 * m4.z + (1.0f - b1) * g.z; m4.w = b1 * m4.w + (1.0f - b1) * g.w;
-      v4.x = b2 * v4.x + (1.0f - b2) * g.x * g.x; v4.y = b2 * v4.y + (1.0f - b2) * g.y * g.y;
-      v4.z = b2 * v4.z + (1.0f - b2) * g.z * g.z; v4.w = b2 * v4.w + (1.0f - b2) * g.w * g.w;
+      bwd_adam_m(g, b1, m4);
+      bwd_adam_v(g, b2, v4);
       tzr_st4(mp, m4);
       tzr_st4(vp, v4);
       w4.x -= lr * ((m4.x / c1) / (sqrtf(v4.x / c2) + opt.eps) + opt.wd * w4.x);
@@ -337,12 +406,9 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
   if (opt.kind == TZR_OPT_ADAGRAD) {
     if (active) {
       float* mp = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c;
-      m4.x += g.x * g.x; m4.y += g.y * g.y; m4.z += g.z * g.z; m4.w += g.w * g.w;
+      bwd_adagrad_m(g, m4);
       tzr_st4(mp, m4);
-      w4.x -= lr * g.x / (sqrtf(m4.x) + opt.eps);
-      w4.y -= lr * g.y / (sqrtf(m4.y) + opt.eps);
-      w4.z -= lr * g.z / (sqrtf(m4.z) + opt.eps);
-      w4.w -= lr * g.w / (sqrtf(m4.w) + opt.eps);
+      bwd_adagrad_w(opt, lr, g, m4, w4);
       tzr_stw4(wbase, tb.w_dtype, woff, w4);
     }
   } else if (opt.kind == TZR_OPT_ROWWISE_ADAGRAD) {
@@ -356,15 +422,7 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
     float mold = (active && lane_in_group == 0) ? m4.x : 0.f;  // loaded by bwd_load_state
     mold = __shfl(mold, lane - lane_in_group, 64);
     if (active) {
-      const float mnew = mold + ss / (float)tb.dim;
-      const float mult = lr / (sqrtf(mnew) + opt.eps);
-      float corr = 1.0f;
-      if (opt.wd_mode == TZR_WD_L2) corr = 1.0f - mult * opt.wd;
-      else if (opt.wd_mode == TZR_WD_DECOUPLE) corr = 1.0f - lr * opt.wd;
-      w4.x = corr * w4.x - mult * g.x;
-      w4.y = corr * w4.y - mult * g.y;
-      w4.z = corr * w4.z - mult * g.z;
-      w4.w = corr * w4.w - mult * g.w;
+      const float mnew = bwd_rowwise_step(opt, lr, tb.dim, mold, ss, g, w4);
       tzr_stw4(wbase, tb.w_dtype, woff, w4);
       if (lane_in_group == 0) *mp = mnew;
     }
@@ -373,7 +431,7 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
     if (active) tzr_st4(reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c, g);
   } else {  // SGD
     if (active) {
-      w4.x -= lr * g.x; w4.y -= lr * g.y; w4.z -= lr * g.z; w4.w -= lr * g.w;
+      bwd_sgd_step(g, lr, w4);
       tzr_stw4(wbase, tb.w_dtype, woff, w4);
     }
   }
@@ -389,21 +447,13 @@ __device__ __forceinline__ void bwd_apply_row(const TzrTable& tb, const BwdOpt& 
 template <int FK>
 __device__ __forceinline__ void bwd_apply_row_fast(const TzrTable& tb, const BwdOpt& opt, float lr, int64_t row, int c, float4 g,
                                                    float4 w4, float4 m4, bool active, int lg, int lane_in_group, int lane) {
-  if (opt.clip) {
-    g.x = fminf(fmaxf(g.x, -opt.max_grad), opt.max_grad);
-    g.y = fminf(fmaxf(g.y, -opt.max_grad), opt.max_grad);
-    g.z = fminf(fmaxf(g.z, -opt.max_grad), opt.max_grad);
-    g.w = fminf(fmaxf(g.w, -opt.max_grad), opt.max_grad);
-  }
+  g = bwd_clip(opt, g);
   float* const wp = reinterpret_cast<float*>(tb.w) + row * (int64_t)tb.w_stride + 4 * c;
   if constexpr (FK == TZR_OPT_ADAGRAD) {
     if (active) {
-      m4.x += g.x * g.x; m4.y += g.y * g.y; m4.z += g.z * g.z; m4.w += g.w * g.w;
+      bwd_adagrad_m(g, m4);
       tzr_stg4(reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c, m4);
-      w4.x -= lr * g.x / (sqrtf(m4.x) + opt.eps);
-      w4.y -= lr * g.y / (sqrtf(m4.y) + opt.eps);
-      w4.z -= lr * g.z / (sqrtf(m4.z) + opt.eps);
-      w4.w -= lr * g.w / (sqrtf(m4.w) + opt.eps);
+      bwd_adagrad_w(opt, lr, g, m4, w4);
       tzr_stg4(wp, w4);
     }
   } else if constexpr (FK == TZR_OPT_ROWWISE_ADAGRAD) {
@@ -412,21 +462,13 @@ __device__ __forceinline__ void bwd_apply_row_fast(const TzrTable& tb, const Bwd
     float ss = active ? (gl.x * gl.x + gl.y * gl.y + gl.z * gl.z + gl.w * gl.w) : 0.f;
     ss = bwd_group_sum(ss, lg, lane_in_group, lane);
     if (active) {  // (every lane of the group loaded the row's scalar itself: m4.x)
-      const float mnew = m4.x + ss / (float)tb.dim;
-      const float mult = lr / (sqrtf(mnew) + opt.eps);
-      float corr = 1.0f;
-      if (opt.wd_mode == TZR_WD_L2) corr = 1.0f - mult * opt.wd;
-      else if (opt.wd_mode == TZR_WD_DECOUPLE) corr = 1.0f - lr * opt.wd;
-      w4.x = corr * w4.x - mult * g.x;
-      w4.y = corr * w4.y - mult * g.y;
-      w4.z = corr * w4.z - mult * g.z;
-      w4.w = corr * w4.w - mult * g.w;
+      const float mnew = bwd_rowwise_step(opt, lr, tb.dim, m4.x, ss, g, w4);
       tzr_stg4(wp, w4);
       if (lane_in_group == 0) tzr_stg(reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride, mnew);
     }
   } else {  // SGD
     if (active) {
-      w4.x -= lr * g.x; w4.y -= lr * g.y; w4.z -= lr * g.z; w4.w -= lr * g.w;
+      bwd_sgd_step(g, lr, w4);
       tzr_stg4(wp, w4);
     }
   }

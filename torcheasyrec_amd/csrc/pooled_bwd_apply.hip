@@ -489,34 +489,19 @@ extern "C" int tzr_pooled_bwd_apply(const TzrTable* d_tables, const TzrFeature* 
   if (const int rc = bwd_grads_from(h_grads, n_dst, &G)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned chunks = (unsigned)P.max_chunks;
-#define TZR_REDUCE_LAUNCH(K)                                                                       \
-  hipLaunchKernelGGL(K, dim3(chunks), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats, d_offsets, \
-                     d_weights, B, (int)uniform, grad_mode, G, opt, max_dim, P)
   // bags of one id with pooled gradients, or one gradient row per id (the sharded owners' and the sequence lookup's backward), no
   // per-sample weights: the shapes the fast memory side of the tile loop is written for
-  const bool fast_shape = ((grad_mode == 0 && uniform) || grad_mode == 1) && !d_weights &&
-                          (opt.kind == TZR_OPT_ADAGRAD || opt.kind == TZR_OPT_ROWWISE_ADAGRAD || opt.kind == TZR_OPT_SGD);
-  if (fast_shape) {
-    if (opt.kind == TZR_OPT_ADAGRAD)
-      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_adagrad_kernel);
-    else if (opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
-      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_rowwise_kernel);
-    else
-      TZR_REDUCE_LAUNCH(tzr_bwd_reduce_fast_sgd_kernel);
-  } else if (opt.kind == TZR_OPT_ADAM) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ADAM>));  // Adam holds two state rows per lane: no registers for a second tile
-  } else if (bwd_norm_kind(opt.kind)) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_NORM>));
-  } else if (bwd_elem_kind(opt.kind)) {
-    TZR_REDUCE_LAUNCH((tzr_bwd_reduce_kernel<BWD_FAM_ELEM>));
-  } else {
-    // 7 waves per SIMD = 1792 workgroups resident: the whole unit grid of a B = 65536 Criteo step (1691) runs in
-    // one wave of workgroups.  At 6 (77 VGPRs, what the compiler picks unasked) the last 155 units waited for a
-    // free slot and finished a full workgroup time after the rest: 88.4 -> 78.9 us (row-wise Adagrad 92.9 -> 78.6),
-    // profiles/r03n.  8 waves (64 VGPRs) spills: 88.0 us.
-    TZR_REDUCE_LAUNCH(tzr_bwd_reduce_w7_kernel);
-  }
-#undef TZR_REDUCE_LAUNCH
+  const bool fast_shape = ((grad_mode == 0 && uniform) || grad_mode == 1) && !d_weights;
+  // by BWD_VAR_*.  General: 7 waves per SIMD = 1792 workgroups resident: the whole unit grid of a B = 65536 Criteo step
+  // (1691) runs in one wave of workgroups.  At 6 (77 VGPRs, what the compiler picks unasked) the last 155 units waited for
+  // a free slot and finished a full workgroup time after the rest: 88.4 -> 78.9 us (row-wise Adagrad 92.9 -> 78.6),
+  // profiles/r03n.  8 waves (64 VGPRs) spills: 88.0 us.  Adam holds two state rows per lane: no registers for a second tile.
+  static constexpr decltype(&tzr_bwd_reduce_w7_kernel) kernels[BWD_VAR_COUNT] = {
+      tzr_bwd_reduce_w7_kernel,           tzr_bwd_reduce_fast_sgd_kernel,      tzr_bwd_reduce_fast_adagrad_kernel,
+      tzr_bwd_reduce_fast_rowwise_kernel, tzr_bwd_reduce_kernel<BWD_FAM_ADAM>, tzr_bwd_reduce_kernel<BWD_FAM_NORM>,
+      tzr_bwd_reduce_kernel<BWD_FAM_ELEM>};
+  hipLaunchKernelGGL(kernels[bwd_variant(opt.kind, fast_shape)], dim3(chunks), dim3(BWD_THREADS), 0, s, d_tables, n_tables,
+                     d_feats, d_offsets, d_weights, B, (int)uniform, grad_mode, G, opt, max_dim, P);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
 }
@@ -589,23 +574,11 @@ static int dense_rows_update(const TzrTable* d_tables, int n_tables, const int64
   if (!d_acc || (reinterpret_cast<uintptr_t>(d_acc) & 15)) return TZR_ERR_INVALID;
   const int gpb = (TZR_WAVE / (dim >> 2)) * BWD_WAVES;
   const unsigned grid = (unsigned)std::min<int64_t>(4096, (total_rows + gpb - 1) / gpb);
-  if (opt.kind == TZR_OPT_ADAM) {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_ADAM>), dim3(grid), dim3(BWD_THREADS), 0,
-                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
-                       d_acc, dim, opt, clear);
-  } else if (bwd_norm_kind(opt.kind)) {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_NORM>), dim3(grid), dim3(BWD_THREADS), 0,
-                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
-                       d_acc, dim, opt, clear);
-  } else if (bwd_elem_kind(opt.kind)) {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_ELEM>), dim3(grid), dim3(BWD_THREADS), 0,
-                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
-                       d_acc, dim, opt, clear);
-  } else {
-    hipLaunchKernelGGL((tzr_dense_rows_update_kernel<BWD_FAM_LEGACY>), dim3(grid), dim3(BWD_THREADS), 0,
-                       static_cast<hipStream_t>(stream), d_tables, n_tables, d_row_start, total_rows,
-                       d_acc, dim, opt, clear);
-  }
+  static constexpr decltype(&tzr_dense_rows_update_kernel<BWD_FAM_LEGACY>) kernels[] = {  // by BWD_FAM_*: no fast variants here
+      tzr_dense_rows_update_kernel<BWD_FAM_LEGACY>, tzr_dense_rows_update_kernel<BWD_FAM_ADAM>,
+      tzr_dense_rows_update_kernel<BWD_FAM_NORM>, tzr_dense_rows_update_kernel<BWD_FAM_ELEM>};
+  hipLaunchKernelGGL(kernels[bwd_family(opt.kind, false)], dim3(grid), dim3(BWD_THREADS), 0, static_cast<hipStream_t>(stream),
+                     d_tables, n_tables, d_row_start, total_rows, d_acc, dim, opt, clear);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
 }

@@ -1047,26 +1047,13 @@ extern "C" int tzr_pooled_bwd_cells_apply(const TzrTable* d_tables, const TzrFea
   BwdGrads G;
   if (const int rc = bwd_grads_from(h_grads, n_dst, &G)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define TZR_CELLS_LAUNCH(K)                                                                                               \
-  hipLaunchKernelGGL(K, dim3((unsigned)g.n_units + BWD_CELLS_WORKERS), dim3(BWD_THREADS), 0, s, V, (int)g.n_units, d_feats, d_weights, \
-                     B, grad_mode, G, opt, max_dim, (const uint2*)P.ks[1], (const uint16_t*)reinterpret_cast<uint16_t*>(P.hist), (int)g.ch)
-  const bool fast_shape = !d_weights && (opt.kind == TZR_OPT_ADAGRAD || opt.kind == TZR_OPT_ROWWISE_ADAGRAD || opt.kind == TZR_OPT_SGD);
-  if (opt.kind == TZR_OPT_ADAM) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_adam_kernel);
-  } else if (bwd_norm_kind(opt.kind)) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_norm_kernel);
-  } else if (bwd_elem_kind(opt.kind)) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_elem_kernel);
-  } else if (!fast_shape) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_general_kernel);
-  } else if (opt.kind == TZR_OPT_ADAGRAD) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_adagrad_kernel);
-  } else if (opt.kind == TZR_OPT_ROWWISE_ADAGRAD) {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_rowwise_kernel);
-  } else {
-    TZR_CELLS_LAUNCH(tzr_bwd_cells_apply_sgd_kernel);
-  }
-#undef TZR_CELLS_LAUNCH
+  static constexpr decltype(&tzr_bwd_cells_apply_general_kernel) kernels[BWD_VAR_COUNT] = {  // by BWD_VAR_*
+      tzr_bwd_cells_apply_general_kernel, tzr_bwd_cells_apply_sgd_kernel,  tzr_bwd_cells_apply_adagrad_kernel,
+      tzr_bwd_cells_apply_rowwise_kernel, tzr_bwd_cells_apply_adam_kernel, tzr_bwd_cells_apply_norm_kernel,
+      tzr_bwd_cells_apply_elem_kernel};
+  hipLaunchKernelGGL(kernels[bwd_variant(opt.kind, /*fast_shape=*/!d_weights)], dim3((unsigned)g.n_units + BWD_CELLS_WORKERS),
+                     dim3(BWD_THREADS), 0, s, V, (int)g.n_units, d_feats, d_weights, B, grad_mode, G, opt, max_dim,
+                     (const uint2*)P.ks[1], (const uint16_t*)reinterpret_cast<uint16_t*>(P.hist), (int)g.ch);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
 }

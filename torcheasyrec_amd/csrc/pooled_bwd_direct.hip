@@ -747,25 +747,11 @@ extern "C" int tzr_pooled_bwd_direct(const TzrTable* d_tables, int n_tables, con
   const bool look = g_tzr_bwd_direct_hot == 2 || (g_tzr_bwd_direct_hot == 1 && hot_rows);
   const int ch = ch0 | ((g_tzr_bwd_direct_debug & 0xFF) << 16) | (look ? 0 : 1 << 24);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define BWD_DIRECT_LAUNCH(K)                                                                                              \
-  hipLaunchKernelGGL(K, dim3(grid), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats, n_feats, A, d_weights, grad_mode, G, opt, ch, \
-                     wcount, wpart, max_dim)
-  if (opt.kind == TZR_OPT_ADAM)
-    hipLaunchKernelGGL(tzr_bwd_direct_adam_kernel, dim3(grid), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats,
-                       n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
-  else if (bwd_norm_kind(opt.kind))
-    BWD_DIRECT_LAUNCH(tzr_bwd_direct_norm_kernel);
-  else if (bwd_elem_kind(opt.kind))
-    BWD_DIRECT_LAUNCH(tzr_bwd_direct_elem_kernel);
-  else if (!d_weights && opt.kind == TZR_OPT_ADAGRAD)
-    BWD_DIRECT_LAUNCH(tzr_bwd_direct_adagrad_kernel);
-  else if (!d_weights && opt.kind == TZR_OPT_ROWWISE_ADAGRAD)
-    BWD_DIRECT_LAUNCH(tzr_bwd_direct_rowwise_kernel);
-  else if (!d_weights && opt.kind == TZR_OPT_SGD)
-    BWD_DIRECT_LAUNCH(tzr_bwd_direct_sgd_kernel);
-  else
-    hipLaunchKernelGGL(tzr_bwd_direct_kernel, dim3(grid), dim3(BWD_THREADS), 0, s, d_tables, n_tables, d_feats,
-                       n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
+  static constexpr decltype(&tzr_bwd_direct_kernel) kernels[BWD_VAR_COUNT] = {  // by BWD_VAR_*
+      tzr_bwd_direct_kernel,         tzr_bwd_direct_sgd_kernel,  tzr_bwd_direct_adagrad_kernel, tzr_bwd_direct_rowwise_kernel,
+      tzr_bwd_direct_adam_kernel,    tzr_bwd_direct_norm_kernel, tzr_bwd_direct_elem_kernel};
+  hipLaunchKernelGGL(kernels[bwd_variant(opt.kind, /*fast_shape=*/!d_weights)], dim3(grid), dim3(BWD_THREADS), 0, s, d_tables,
+                     n_tables, d_feats, n_feats, A, d_weights, grad_mode, G, opt, ch, wcount, wpart, max_dim);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
 }

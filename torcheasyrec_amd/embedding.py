@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, opt_kinds
 from .sparse import KeyedJaggedTensor, KeyedTensor
 
 
@@ -82,44 +82,27 @@ class SparseOptimizerConfig:
     alpha: float = 0.99  # rmsprop: decay of the running average of g^2 (protos/optimizer.proto:150-157)
 
 
-_OPT_KIND = {"sgd": _lib.OPT_SGD, "adagrad": _lib.OPT_ADAGRAD, "rowwise_adagrad": _lib.OPT_ROWWISE_ADAGRAD,
-             "adam": _lib.OPT_ADAM, "partial_rowwise_adam": _lib.OPT_PARTIAL_ROWWISE_ADAM, "lamb": _lib.OPT_LAMB,
-             "partial_rowwise_lamb": _lib.OPT_PARTIAL_ROWWISE_LAMB, "lars_sgd": _lib.OPT_LARS_SGD,
-             "adadelta": _lib.OPT_ADADELTA, "rmsprop": _lib.OPT_RMSPROP}
+_OPT_KIND = {name: k.code for name, k in opt_kinds.KINDS.items()}
 _WD_MODE = {"none": _lib.WD_NONE, "l2": _lib.WD_L2, "decouple": _lib.WD_DECOUPLE}
 # the kinds that read the device step state {step, 1 - b1^step, 1 - b2^step}, advanced once per step (begin_step)
-TICKING_KINDS = frozenset({"adam", "partial_rowwise_adam", "lamb", "partial_rowwise_lamb"})
+TICKING_KINDS = frozenset(name for name, k in opt_kinds.KINDS.items() if k.ticks)
 # the kinds whose eps comes from the config and divides by itself alone on a zero-gradient row: it must be positive
-CONFIGURED_EPS_KINDS = frozenset({"adadelta", "rmsprop"})
+CONFIGURED_EPS_KINDS = frozenset(name for name, k in opt_kinds.KINDS.items() if k.configured_eps)
 
 
 def _state_shape(kind: Optional[str], rows: int, D: int) -> Optional[Tuple[int, int]]:
     """[rows, width] of the separate fp32 state tensor of the kinds that always have one (include/tzrec_hip.h)"""
-    if kind in ("adam", "lamb"):  # [exp_avg | exp_avg_sq]
-        return (rows, 2 * D)
-    if kind == "adadelta":  # [square_avg | acc_delta]
-        return (rows, 2 * D)
-    if kind == "rmsprop":  # [square_avg]
-        return (rows, D)
-    if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):  # [exp_avg | exp_avg_sq | pad(3)]: float4 aligned
-        return (rows, D + 4)
-    if kind == "lars_sgd":  # [momentum]
-        return (rows, D)
-    return None
+    k = opt_kinds.of(kind)
+    return (rows, k.state_width(D)) if k.separate_state else None
 
 
 def check_state_stride(kind: Optional[str], D: int, m_stride: int) -> None:
     """The state row stride a norm kind needs (include/tzrec_hip.h).  The C entry points take the table records as a device
     array and cannot check it; a stride too small would put one row's state into the next row's."""
-    if kind in ("partial_rowwise_adam", "partial_rowwise_lamb"):
-        ok = m_stride >= D + 1 and m_stride % 4 == 0
-    elif kind in ("lamb", "adadelta"):
-        ok = m_stride >= 2 * D
-    elif kind in ("lars_sgd", "rmsprop"):
-        ok = m_stride >= D
-    else:
+    k = opt_kinds.of(kind)
+    if not (k.separate_state and k.stride_checked):
         return
-    if not ok:
+    if m_stride < k.state_width(D) - k.state_pad or (k.state_pad and m_stride % 4):
         raise ValueError(f"{kind}: state row stride {m_stride} does not fit a row of dim {D}")
 
 
@@ -133,9 +116,9 @@ class FusedSparseOptimizer:
         if cfg.kind in CONFIGURED_EPS_KINDS:
             if not cfg.eps > 0.0:
                 raise ValueError(f"{cfg.kind}: eps must be > 0 (got {cfg.eps}): a touched row with a zero gradient divides by it alone")
-            decay = cfg.rho if cfg.kind == "adadelta" else cfg.alpha
-            if not 0.0 <= decay < 1.0:
-                raise ValueError(f"{cfg.kind}: {'rho' if cfg.kind == 'adadelta' else 'alpha'} must be in [0, 1) (got {decay})")
+            name = opt_kinds.of(cfg.kind).slots[0]  # rho / alpha
+            if not 0.0 <= getattr(cfg, name) < 1.0:
+                raise ValueError(f"{cfg.kind}: {name} must be in [0, 1) (got {getattr(cfg, name)})")
         self.cfg = cfg
         self._ebc = ebc
         self.param_groups = [{"lr": float(cfg.lr), "params": list(ebc.table_weights().values())}]
@@ -165,9 +148,7 @@ class FusedSparseOptimizer:
         opt.d_lr = _lib.ptr(self.lr_device(device))
         opt.eps, opt.weight_decay, opt.max_gradient = cfg.eps, cfg.weight_decay, cfg.max_gradient
         opt.gradient_clipping = 1 if cfg.gradient_clipping else 0
-        opt.beta1, opt.beta2 = (cfg.momentum, cfg.eta) if cfg.kind == "lars_sgd" else (cfg.beta1, cfg.beta2)
-        if cfg.kind in CONFIGURED_EPS_KINDS:  # rho / alpha travel in the beta1 slot (include/tzrec_hip.h); beta2 is not read
-            opt.beta1 = cfg.rho if cfg.kind == "adadelta" else cfg.alpha
+        opt.beta1, opt.beta2 = (getattr(cfg, name) for name in opt_kinds.of(cfg.kind).slots)
         opt.d_adam = _lib.ptr(self.adam_state(device)) if cfg.kind in TICKING_KINDS else 0
         return opt
 

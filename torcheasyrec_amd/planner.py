@@ -34,8 +34,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import opt_kinds
+
 GB = 1 << 30
-_NORM_KINDS = ("partial_rowwise_adam", "lamb", "partial_rowwise_lamb", "lars_sgd", "adadelta", "rmsprop")  # their state is priced by _state_bytes_dim
 
 
 class PlannerError(RuntimeError):
@@ -141,18 +142,13 @@ class EmbeddingEnumerator:
     def _state_bytes_dim(t: TableSpec, rows: int, dim: int) -> int:
         """optimizer-state bytes of `rows` rows of `dim` columns AS ALLOCATED (the planner priced row-wise
         Adagrad at 4 bytes per row while the default interleaved layout allocates a second D-wide half per row)"""
-        if t.optimizer == "adagrad":
-            return rows * dim * 4
-        if t.optimizer == "rowwise_adagrad":
-            padded = t.row_layout == "interleaved" and t.bytes_per_element == 4  # (FP16 tables are never interleaved)
-            return rows * dim * 4 if padded else rows * 4
-        if t.optimizer in ("adam", "lamb", "adadelta"):
-            return rows * dim * 8
-        if t.optimizer in ("partial_rowwise_adam", "partial_rowwise_lamb"):
-            return rows * (dim + 4) * 4
-        if t.optimizer in ("lars_sgd", "rmsprop"):
-            return rows * dim * 4
-        return 0
+        k = opt_kinds.of(t.optimizer)
+        width = k.state_width(dim)
+        # state kept in the row layout: an interleaved fp32 row is [w(D) | state] with a 2 D stride, whatever the state's own
+        # width (row-wise Adagrad's one scalar); FP16 tables are never interleaved
+        if width and not k.separate_state and t.row_layout == "interleaved" and t.bytes_per_element == 4:
+            width = dim
+        return rows * width * 4
 
     def _state_bytes(self, t: TableSpec, rows: int) -> int:
         return self._state_bytes_dim(t, rows, t.embedding_dim)
@@ -223,8 +219,8 @@ class EmbeddingEnumerator:
             d = D // k
             n = ids * W
             piece_b = d * eb
-            piece_rmw = 2 * piece_b + 2 * (d * 4 if t.optimizer == "adagrad" else 4 if t.optimizer == "rowwise_adagrad"
-                                           else self._state_bytes_dim(t, 1, d) if t.optimizer in _NORM_KINDS else 0)
+            k_opt = opt_kinds.of(t.optimizer)
+            piece_rmw = 2 * piece_b + 2 * (4 * k_opt.state_width(d) if k_opt.column_priced else 0)
             wire = (n * (8 + 2 * piece_b) * (W - 1) / W) / top.a2a_bw
             perf = n * piece_b / top.hbm_gather_bw + n * piece_rmw / top.hbm_rmw_bw + wire + 3 * top.collective_latency
             st = t.num_embeddings * piece_b + self._state_bytes_dim(t, t.num_embeddings, d)
