@@ -15,7 +15,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from torcheasyrec_amd import _lib  # noqa: E402
 from torcheasyrec_amd.config import load_pipeline_spec  # noqa: E402
-from torcheasyrec_amd.dense import FusedDenseAdam  # noqa: E402
+from torcheasyrec_amd.dense_optim import build_dense_optimizer, create_dense_schedulers, named_dense_parameters  # noqa: E402
 from torcheasyrec_amd.embedding_group import BASE_DATA_GROUP, Batch, TrainPipeline  # noqa: E402
 from torcheasyrec_amd.lr_scheduler import create_scheduler  # noqa: E402
 from torcheasyrec_amd.rank_model import build_rank_model  # noqa: E402
@@ -41,10 +41,12 @@ def main(path):
     dev = torch.device("cuda", 0)
     spec = load_pipeline_spec(open(path).read())
     model = build_rank_model(spec, device=dev)
-    opt = FusedDenseAdam(list(model.dense_parameters()), lr=spec.dense_lr)
-    # the `learning_rate` oneof of the two optimizer blocks (tzrec/main.py:877-882); stepped per step
+    # train_config.dense_optimizer: its kind with every field, its part_optimizers as groups of the same one-launch step
+    # (tzrec/optim/optimizer_builder.py:100-260)
+    opt = build_dense_optimizer(named_dense_parameters(model), spec.dense_optimizer)
+    # the `learning_rate` oneof of the two optimizer blocks and of every part (tzrec/main.py:877-882); stepped per step
     # unless by_epoch (main.py:542-544)
-    schedulers = [create_scheduler(model.fused_optimizer, spec.sparse_optimizer_block), create_scheduler(opt, spec.dense_optimizer_block)]
+    schedulers = [create_scheduler(model.fused_optimizer, spec.sparse_optimizer_block)] + create_dense_schedulers(opt, spec.dense_optimizer)
     # train_config.grad_clipping / gradient_accumulation_steps around the dense optimizer (tzrec/main.py:848-876)
     from torcheasyrec_amd.optimizer import build_train_optimizer
 

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from examples.train_from_config import synthetic_batches  # noqa: E402
 from torcheasyrec_amd import _lib  # noqa: E402
 from torcheasyrec_amd.config import load_pipeline_spec  # noqa: E402
-from torcheasyrec_amd.dense import FusedDenseAdam  # noqa: E402
+from torcheasyrec_amd.dense_optim import build_dense_optimizer, create_dense_schedulers, named_dense_parameters  # noqa: E402
 from torcheasyrec_amd.embedding_group import TrainPipeline  # noqa: E402
 from torcheasyrec_amd.planner import plan_to_json  # noqa: E402
 from torcheasyrec_amd.rank_model import build_rank_model  # noqa: E402
@@ -40,7 +40,8 @@ def main(path, exchange="exact"):
     ebc = model.embedding_group.ebc
     if rank == 0 and ebc is not None and world > 1:
         print(plan_to_json(ebc.sharding_plan() if hasattr(ebc, "sharding_plan") else ebc.plan()))
-    opt = FusedDenseAdam(list(model.dense_parameters()), lr=spec.dense_lr)
+    opt = build_dense_optimizer(named_dense_parameters(model), spec.dense_optimizer)
+    schedulers = create_dense_schedulers(opt, spec.dense_optimizer)
     pipe = TrainPipeline(model, opt, dev, model.loss)
     it = iter(synthetic_batches(spec, 20 * bs, bs, seed=rank))
     step = 0
@@ -50,6 +51,9 @@ def main(path, exchange="exact"):
         except StopIteration:
             break
         step += 1
+        for sch in schedulers:
+            if not sch.by_epoch:
+                sch.step()
         if rank == 0 and step % 5 == 0:
             print(f"step {step}: " + ", ".join(f"{k}={float(v.detach()):.4f}" for k, v in losses.items()), flush=True)
     dist.barrier()

@@ -593,7 +593,13 @@ int tzr_dense_adam(const TzrAdamTensor* h_tensors, int n_tensors, const float* d
  * element i of the tensor = sum over the G rows of parts[g * P + col + i], added in tzr_mlp2_bwd's own finish order), or the
  * batch slices of tzr_dot_interaction_top_wgrad_parts (TZR_ADAM_SRC_WGRAD, at most one per call: *h_wgrad).  The column-sum
  * finish launches and the slice reduction of the DLRM step (tzrec/models/dlrm.py:101-135 behind tzrec/optim/optimizer.py:56-68)
- * disappear into the optimizer's launch; sums and updates are bit-identical to the separate launches.
+ * disappear into the optimizer's launch.  The sums are bit-identical to the separate launches where the order of additions is
+ * theirs: tzr_mlp2_bwd's finish (16 contiguous ranges of the G rows, then the 16 range sums) and the slice reduction of
+ * tzr_dot_interaction_top_wgrad.  Partial rows that tzr_colsum_finish_kernel would finish (tzr_relu_bwd_colsum_parts,
+ * tzr_skinny_linear_bwd_parts) are added in THIS order too, not in that kernel's interleaved slices: equal to it up to fp32
+ * rounding, and equal between every consumer of this summation (tzr_dense_adam_fused, tzr_dense_optim_fused, store-only calls).
+ * Refused: TZR_ERR_UNSUPPORTED for a source that would need more than 1024 workgroups (the arrival counters of a state row);
+ * TZR_ERR_INVALID for param == 0 && grad == 0 (nowhere to write).
  * TzrAdamTensor.state here: float[TZR_ADAM_FUSED_STATE]: [0] step count, [1 ..] arrival counters (ZERO between launches: the
  * tensor's workgroups arrive in groups of 32, the last one moves the step on and clears them) -- not interchangeable with
  * tzr_dense_adam's float[3] on the same tensor.
@@ -614,6 +620,47 @@ typedef struct TzrWgradParts { uint64_t opaque[24]; } TzrWgradParts; /* filled b
 int tzr_dense_adam_fused(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
                          const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
                          float weight_decay, void* stream);
+/* The dense optimizer step of every kind `train_config.dense_optimizer` and its `part_optimizers` can name
+ * (tzrec/optim/optimizer_builder.py:100-260 -> torch.optim.SGD / Adagrad / Adam / AdamW / Adadelta / RMSprop), over every
+ * dense tensor of the step in ONE launch per TZR_ADAM_MAX_TENSORS tensors, whatever mix of kinds (csrc/dense_optim_fused.hip).
+ * A tensor names its group; a group holds the kind, the learning rate (read from d_lr when non-zero, so a captured hipGraph
+ * follows a scheduler; else `lr`) and the hyper-parameters.  Per element, torch.optim's single-tensor path in fp32, g the
+ * gradient, p the parameter, wd = weight_decay:
+ *   SGD       g += wd p;  state0 (momentum_buffer, only when hp0 = momentum != 0): buf = g on the tensor's first step (step
+ *             count 0), else buf = momentum buf + (1 - hp1 = dampening) g;  TZR_DENSE_OPT_NESTEROV: g += momentum buf, else
+ *             g = buf;  p -= lr g
+ *   ADAGRAD   g += wd p;  state0 (sum, filled with initial_accumulator_value by the caller) += g^2;  p -= lr g / (sqrt(sum) + eps)
+ *   ADAM      as tzr_dense_adam_fused: hp0 = beta1, hp1 = beta2, state0 = exp_avg, state1 = exp_avg_sq, L2 weight decay
+ *   ADAMW     p *= 1 - lr wd, then ADAM without the L2 term
+ *   ADADELTA  g += wd p;  state0 (square_avg) = rho sq + (1 - rho) g^2 (hp0 = rho);  d = sqrt(acc + eps) / sqrt(sq + eps) g;
+ *             state1 (acc_delta) = rho acc + (1 - rho) d^2;  p -= lr d
+ *   RMSPROP   g += wd p;  state0 (square_avg) = alpha sq + (1 - alpha) g^2 (hp0 = alpha);  p -= lr g / (sqrt(sq) + eps)
+ * (no amsgrad, no lr_decay, no momentum / centered RMSprop: protos/optimizer.proto:159-208 has no such fields, or the caller
+ * refuses them.)  `state`: float[TZR_ADAM_FUSED_STATE] as for tzr_dense_adam_fused: [0] the tensor's step count, moved on
+ * by the last of its workgroups, [1 ..] arrival counters, zero between launches.  Gradient sources, store-only tensors
+ * (param == 0; `group` is not read) and refusals as for tzr_dense_adam_fused: the summation is the same code.  Also refused,
+ * before anything is launched: n_groups > TZR_DENSE_OPT_MAX_GROUPS (TZR_ERR_UNSUPPORTED); an unknown kind, a group index out
+ * of range, a null state tensor that the kind needs, a null `state` (TZR_ERR_INVALID). */
+#define TZR_DENSE_OPT_SGD 0
+#define TZR_DENSE_OPT_ADAGRAD 1
+#define TZR_DENSE_OPT_ADAM 2
+#define TZR_DENSE_OPT_ADAMW 3
+#define TZR_DENSE_OPT_ADADELTA 4
+#define TZR_DENSE_OPT_RMSPROP 5
+#define TZR_DENSE_OPT_MAX_GROUPS 8
+#define TZR_DENSE_OPT_NESTEROV 1 /* TzrDenseOptGroup.flags */
+typedef struct TzrDenseOptTensor { /* device addresses, float32 */
+  uint64_t param, grad, state0, state1, state;
+  int64_t numel;
+  int32_t group, reserved;
+} TzrDenseOptTensor; /* 56 bytes */
+typedef struct TzrDenseOptGroup {
+  int32_t kind, flags;
+  uint64_t d_lr; /* const float* device address, or 0: `lr` */
+  float lr, weight_decay, eps, hp0, hp1, reserved;
+} TzrDenseOptGroup; /* 40 bytes */
+int tzr_dense_optim_fused(const TzrDenseOptTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
+                          const TzrDenseOptGroup* h_groups, int n_groups, const TzrWgradParts* h_wgrad, void* stream);
 /* tzr_mlp2_bwd / tzr_dot_interaction_top_wgrad without their finishing launch (same arguments, same workspace, which stays the
  * caller's until tzr_dense_adam_fused has consumed it): *out_G rows of *out_P floats, columns [dWb: H2 x H1 | dbb: H2 |
  * dWa: H1 x K0 | dba: H1]; *h_out for TZR_ADAM_SRC_WGRAD (B > 0). */

@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtzrec_hip.so")
 
 TZR_OK = 0
+TZR_ERR_INVALID, TZR_ERR_UNSUPPORTED = -1, -4
 TZR_MAX_DST = 8
 TZR_MAX_FEAT_DST = 4
 POOL_SUM, POOL_MEAN = 0, 1
@@ -98,6 +99,20 @@ class TzrWgradParts(C.Structure):
 ADAM_SRC_TENSOR, ADAM_SRC_ROWS, ADAM_SRC_WGRAD = 0, 1, 2
 
 
+class TzrDenseOptTensor(C.Structure):
+    _fields_ = [("param", C.c_uint64), ("grad", C.c_uint64), ("state0", C.c_uint64), ("state1", C.c_uint64), ("state", C.c_uint64),
+                ("numel", C.c_int64), ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TzrDenseOptGroup(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("d_lr", C.c_uint64), ("lr", C.c_float), ("weight_decay", C.c_float),
+                ("eps", C.c_float), ("hp0", C.c_float), ("hp1", C.c_float), ("reserved", C.c_float)]
+
+
+DENSE_OPT_MAX_GROUPS = 8
+DENSE_OPT_NESTEROV = 1
+
+
 class TzrZchModule(C.Structure):
     _fields_ = [("keys", C.c_uint64), ("rows", C.c_uint64), ("counts", C.c_uint64), ("last_iter", C.c_uint64),
                 ("capacity", C.c_int64), ("zch_size", C.c_int64), ("reserved", C.c_int64 * 2)]
@@ -166,6 +181,8 @@ _SIGNATURES = {
                                           C.POINTER(TzrSparseOptim), _vp, _vp, _vp, _sz, _vp]),
     "tzr_dense_adam_fused": (_i32, [C.POINTER(TzrAdamTensor), C.POINTER(TzrAdamSource), _i32, C.POINTER(TzrWgradParts), _vp, C.c_float,
                                     C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "tzr_dense_optim_fused": (_i32, [C.POINTER(TzrDenseOptTensor), C.POINTER(TzrAdamSource), _i32, C.POINTER(TzrDenseOptGroup), _i32,
+                                     C.POINTER(TzrWgradParts), _vp]),
     "tzr_mlp2_bwd_parts": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _sz, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), _vp]),
     "tzr_dot_interaction_top_wgrad_parts": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i64,

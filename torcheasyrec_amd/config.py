@@ -13,6 +13,7 @@ import re
 from dataclasses import dataclass, field
 from typing import Any, List, Optional
 
+from .dense_opt_kinds import DENSE_KINDS, group_options
 from .embedding import SparseOptimizerConfig
 
 _TOKEN = re.compile(r'\s*(?:(#[^\n]*)|("(?:\\.|[^"\\])*")|([{}\[\]:,;<>])|([^\s{}\[\]:,;<>"]+))')
@@ -137,6 +138,17 @@ class FeatureGroupSpec:
 
 
 @dataclass
+class DenseOptimizerConfig:
+    """`train_config.dense_optimizer`, or one of its `part_optimizers` (protos/optimizer.proto:31-68)"""
+
+    kind: str  # a key of dense_opt_kinds.DENSE_KINDS
+    fields: dict = field(default_factory=dict)  # every field of the kind's message, the proto's defaults filled in
+    learning_rate: Optional[Msg] = None  # the block itself: its `learning_rate` oneof is lr_scheduler.create_scheduler's to read
+    regex_pattern: Optional[str] = None  # a part: the parameter names it takes (re.fullmatch)
+    parts: List["DenseOptimizerConfig"] = field(default_factory=list)
+
+
+@dataclass
 class PipelineSpec:
     features: List[FeatureSpec] = field(default_factory=list)
     feature_groups: List[FeatureGroupSpec] = field(default_factory=list)
@@ -147,6 +159,7 @@ class PipelineSpec:
     batch_size: int = 0
     sparse_optimizer: Optional[SparseOptimizerConfig] = None
     dense_lr: float = 1e-3
+    dense_optimizer: Optional[DenseOptimizerConfig] = None
     label_fields: List[str] = field(default_factory=list)
     # the raw optimizer blocks (learning-rate schedules: lr_scheduler.create_scheduler)
     sparse_optimizer_block: Optional[Msg] = None
@@ -206,6 +219,31 @@ def sparse_optimizer_from_config(opt: Msg) -> SparseOptimizerConfig:
                 momentum=float(m.one("momentum", 0.9)),
             )
     raise ValueError(f"Unknown optimizer: {[k for k in opt.keys()]}")
+
+
+def dense_optimizer_from_config(opt: Msg) -> DenseOptimizerConfig:
+    """create_dense_optimizer / create_part_optimizer (tzrec/optim/optimizer_builder.py:100-151): the member of the `optimizer`
+    oneof with every field of its message, defaults from protos/optimizer.proto:159-208, and the same for each of the
+    block's `part_optimizers`.  `fields` keeps the config's names (beta1, beta2); `fused` selects torch's implementation and
+    is dropped; `amsgrad: true` and fields the message does not have are refused by name."""
+    members = [k for k in opt.keys() if k.endswith("_optimizer")]
+    known = [k for k in members if k[:-len("_optimizer")] in DENSE_KINDS]
+    if len(known) != 1 or len(members) != 1:
+        raise ValueError(f"Unknown optimizer: {members[0] if len(members) == 1 else (members or None)}")
+    kind = known[0][:-len("_optimizer")]
+    given = {f: v[-1] for f, v in opt.one(known[0]).items()}
+    group_options(kind, given)  # (refusals)
+    fields = {f: (type(d)(given[f]) if f in given and not isinstance(d, bool) else given.get(f, d)) for f, d in DENSE_KINDS[kind].fields.items()}
+    fields.pop("amsgrad", None)
+    cfg = DenseOptimizerConfig(kind=kind, fields=fields, learning_rate=opt)
+    if opt.has("regex_pattern"):
+        cfg.regex_pattern = str(opt.one("regex_pattern"))
+    for part in opt.many("part_optimizers"):
+        sub = dense_optimizer_from_config(part)
+        if sub.regex_pattern is None:
+            raise ValueError("part_optimizers: regex_pattern is required")
+        cfg.parts.append(sub)
+    return cfg
 
 
 def load_pipeline_spec(text: str) -> PipelineSpec:
@@ -268,6 +306,7 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
         spec.sparse_optimizer_block = tc.one("sparse_optimizer")
     if tc.has("dense_optimizer"):
         spec.dense_optimizer_block = tc.one("dense_optimizer")
+        spec.dense_optimizer = dense_optimizer_from_config(spec.dense_optimizer_block)
         for _, v in tc.one("dense_optimizer").items():
             if isinstance(v[-1], Msg) and v[-1].has("lr"):
                 spec.dense_lr = float(v[-1].one("lr"))

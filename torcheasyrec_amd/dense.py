@@ -361,10 +361,11 @@ def _loss_is_root(gl: Optional[torch.Tensor] = None) -> bool:
 
 
 # ---- gradients left as partial sums for the optimizer's own launch (tzr_dense_adam_fused) ------------------------------------
-# With FusedDenseAdam(fuse_finish=True) as the dense optimizer the bottom MLP's backward and the first top-MLP layer's weight
+# With FusedDenseAdam(fuse_finish=True) (or dense_optim.FusedDenseOptimizer, which shares all of this) as the dense optimizer the bottom MLP's backward and the first top-MLP layer's weight
 # gradient do not run their finishing launches: the tensors they return to autograd are UNWRITTEN, and what they stand for is
 # noted here under the tensor's address; `FusedDenseAdam.step` adds the partial sums up on its way to the parameter update
-# (same order of additions: bit-identical) and anything left over is written out by `materialize_pending`.  Who else reads such a
+# (the order of additions of tzr_mlp2_bwd's finish and of the slice reduction: bit-identical to those; column sums that
+# tzr_colsum_finish_kernel would finish differ from it by fp32 rounding) and anything left over is written out by `materialize_pending`.  Who else reads such a
 # gradient before the optimizer has run -- clipping, a collective, gradient accumulation -- calls `materialize_pending()` first;
 # the flag is the caller's statement that nothing does.
 FUSE_FINISH = False
@@ -417,10 +418,14 @@ def _defer_finish(dev: torch.device, params=()) -> bool:
     return True
 
 
-def _adam_tables(rows):
-    """rows: (param | None, grad, exp_avg | None, exp_avg_sq | None, state | None) -> the C arrays of tzr_dense_adam_fused"""
+def _adam_tables(rows, tensor_type=None):
+    """rows: (param | None, grad, exp_avg | None, exp_avg_sq | None, state | None) -> the C arrays of tzr_dense_adam_fused; with
+    `tensor_type` = _lib.TzrDenseOptTensor those of tzr_dense_optim_fused (the two optimizer-state tensors of a row are then
+    the kind's state0 / state1, and a row goes on with (key tensor, group index))"""
     n = len(rows)
-    tab = (_lib.TzrAdamTensor * n)()
+    T = tensor_type or _lib.TzrAdamTensor
+    s0, s1 = ("exp_avg", "exp_avg_sq") if T is _lib.TzrAdamTensor else ("state0", "state1")
+    tab = (T * n)()
     src = (_lib.TzrAdamSource * n)()
     wg = None
     keep = []
@@ -429,10 +434,12 @@ def _adam_tables(rows):
         key = row[5] if len(row) > 5 else gr  # the tensor autograd returned (what _PENDING knows); `gr` = where the gradient goes / lies
         tab[i].param = _lib.ptr(p) if p is not None else 0
         tab[i].grad = _lib.ptr(gr)
-        tab[i].exp_avg = _lib.ptr(m) if m is not None else 0
-        tab[i].exp_avg_sq = _lib.ptr(v) if v is not None else 0
+        setattr(tab[i], s0, _lib.ptr(m) if m is not None else 0)
+        setattr(tab[i], s1, _lib.ptr(v) if v is not None else 0)
         tab[i].state = _lib.ptr(st) if st is not None else 0
         tab[i].numel = gr.numel()
+        if len(row) > 6:
+            tab[i].group = row[6]
         pend = _PENDING.pop(key.data_ptr(), None)
         if pend is None:
             src[i].kind = _lib.ADAM_SRC_TENSOR
@@ -793,6 +800,76 @@ def interaction_top_loss(dense, sparse, D, l1, l2, out_linear, labels):
                                        out_linear.bias, labels)
 
 
+def _register_fused(opt, fuse_finish: bool) -> torch.device:
+    """what a one-launch dense optimizer (FusedDenseAdam, dense_optim.FusedDenseOptimizer) does with its `params` at
+    construction: checked, known to `materialize_pending`, and -- `fuse_finish` -- owner of their deferred gradients"""
+    if fuse_finish:
+        global FUSE_FINISH
+        FUSE_FINISH = True
+    name = type(opt).__name__
+    if not opt.params:
+        raise ValueError("no parameters")
+    _OPTIMIZERS.add(opt)
+    if fuse_finish:
+        me = weakref.ref(opt)
+        for k in [k for k, e in _FUSED_OWNER.items() if e[0]() is None or e[1]() is None]:
+            del _FUSED_OWNER[k]
+        for p in opt.params:
+            _FUSED_OWNER[id(p)] = (weakref.ref(p), me)
+    dev = opt.params[0].device
+    for p in opt.params:
+        if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+            raise ValueError(f"{name} needs contiguous float32 parameters on one device")
+    return dev
+
+
+def _zero_grad(params, set_to_none: bool = True) -> None:
+    for p in params:
+        _DEFERRED.pop(id(p), None)
+    for p in params:
+        if set_to_none:
+            p.grad = None
+        elif p.grad is not None:
+            p.grad.zero_()
+
+
+def _check_lr_synced(opt, stale: bool) -> None:
+    """`step` mirrors the learning rates itself outside a graph capture; inside one a changed rate is an error"""
+    if not (opt.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+        opt.sync_lr()
+    elif stale:  # (ADVICE r3) a capture would freeze the stale rate into the graph
+        raise RuntimeError("learning rate changed since the last sync and a hipGraph capture is open: call "
+                           "dense.sync_learning_rates(model, optimizer) before capturing / replaying (INTEGRATION.md)")
+
+
+def _launch_fused(rows, tables, launch) -> None:
+    """`rows` in launches of <= 32: tables(rows) -> (tab, src, wg, keep), launch(tab, src, wg)"""
+    for base in range(0, len(rows), 32):
+        part = rows[base:base + 32]
+        tab, src, wg, keep = tables(part)
+        if any(src[i].kind < 0 for i in range(len(tab))):  # (a second slice set in one launch: written out first)
+            materialize_pending([r[1] for r in part])
+            tab, src, wg, keep = tables(part)
+        launch(tab, src, wg)
+        del keep
+
+
+def _after_fused_step(opt) -> None:
+    name = type(opt).__name__
+    for p in opt.params:
+        _DEFERRED.pop(id(p), None)
+    if any(len(e) > 4 and e[4] == id(opt) and e[3] == _GENERATION[0] for e in _PENDING.values()):
+        # a backward left a gradient of one of THIS optimizer's parameters as partial sums and the tensor that reached `.grad` is
+        # another one (autograd copied it): its parameter was just stepped with unwritten memory.  Never silently.
+        raise RuntimeError(f"{name}(fuse_finish=True): a gradient left as partial sums did not reach its parameter's .grad "
+                           "as the tensor the backward returned (it was copied on the way); construct the optimizer with "
+                           "fuse_finish=False for this model")
+    if _PENDING:  # (entries of tensors that are gone -- a gradient autograd dropped: unclaimed two steps later)
+        _GENERATION[0] += 1
+        for ptr in [q for q, e in _PENDING.items() if e[3] < _GENERATION[0] - 2]:
+            del _PENDING[ptr]
+
+
 class FusedDenseAdam:
     """torch.optim.Adam (amsgrad off) for the dense parameters, ONE launch per step regardless of the
     number of tensors (tzr_dense_adam_fused: a tensor's step count is moved on by the last of its workgroups).  `param_groups[0]["lr"]` may be changed between steps (it is mirrored into a
@@ -804,23 +881,8 @@ class FusedDenseAdam:
         them up inside its own launch (dense.FUSE_FINISH: three launches of the DLRM step fewer).  The caller's statement that
         nothing reads a dense gradient between `loss.backward()` and `step()` (or calls `dense.materialize_pending()` first) and
         that gradients are not accumulated over several backward passes."""
-        if fuse_finish:
-            global FUSE_FINISH
-            FUSE_FINISH = True
         self.params: List[torch.nn.Parameter] = [p for p in params]
-        if not self.params:
-            raise ValueError("no parameters")
-        _OPTIMIZERS.add(self)
-        if fuse_finish:
-            me = weakref.ref(self)
-            for k in [k for k, e in _FUSED_OWNER.items() if e[0]() is None or e[1]() is None]:
-                del _FUSED_OWNER[k]
-            for p in self.params:
-                _FUSED_OWNER[id(p)] = (weakref.ref(p), me)
-        dev = self.params[0].device
-        for p in self.params:
-            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise ValueError("FusedDenseAdam needs contiguous float32 parameters on one device")
+        dev = _register_fused(self, fuse_finish)
         self.param_groups = [{"lr": float(lr), "betas": tuple(betas), "eps": float(eps), "weight_decay": float(weight_decay),
                               "params": self.params}]
         self.device = dev
@@ -832,13 +894,7 @@ class FusedDenseAdam:
         self._lr_host = float(lr)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
-        for p in self.params:
-            _DEFERRED.pop(id(p), None)
-        for p in self.params:
-            if set_to_none:
-                p.grad = None
-            elif p.grad is not None:
-                p.grad.zero_()
+        _zero_grad(self.params, set_to_none)
 
     def sync_lr(self) -> None:
         """Mirror ``param_groups[0]["lr"]`` into the device scalar the kernel reads.  `step` does it itself outside a
@@ -850,11 +906,7 @@ class FusedDenseAdam:
 
     def step(self, grads: Optional[List[torch.Tensor]] = None) -> None:
         g = self.param_groups[0]
-        if not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-            self.sync_lr()
-        elif g["lr"] != self._lr_host:  #  a capture would freeze the stale rate into the graph
-            raise RuntimeError("learning rate changed since the last sync and a hipGraph capture is open: call "
-                               "dense.sync_learning_rates(model, optimizer) before capturing / replaying (INTEGRATION.md)")
+        _check_lr_synced(self, g["lr"] != self._lr_host)
         rows = []
         for i, p in enumerate(self.params):
             gr = p.grad if grads is None else grads[i]
@@ -866,27 +918,12 @@ class FusedDenseAdam:
         if not rows:
             return
         b1, b2 = g["betas"]
-        for base in range(0, len(rows), 32):
-            tab, src, wg, keep = _adam_tables([(p.data, gr, m, v, st) for p, gr, m, v, st in rows[base:base + 32]])
-            if any(src[i].kind < 0 for i in range(len(tab))):  # (a second slice set in one launch: written out first)
-                materialize_pending([gr for _, gr, _, _, _ in rows[base:base + 32]])
-                tab, src, wg, keep = _adam_tables([(p.data, gr, m, v, st) for p, gr, m, v, st in rows[base:base + 32]])
-            _lib.check(_lib.lib().tzr_dense_adam_fused(tab, src, len(tab), C.byref(wg) if wg is not None else None, _lib.ptr(self._lr_dev),
-                                                       g["lr"], b1, b2, g["eps"], g["weight_decay"], _lib.stream_ptr(self.device)),
-                       "tzr_dense_adam_fused")
-            del keep
-        for p in self.params:
-            _DEFERRED.pop(id(p), None)
-        if any(len(e) > 4 and e[4] == id(self) and e[3] == _GENERATION[0] for e in _PENDING.values()):
-            # a backward left a gradient of one of THIS optimizer's parameters as partial sums and the tensor that reached `.grad` is
-            # another one (autograd copied it): its parameter was just stepped with unwritten memory.  Never silently.
-            raise RuntimeError("FusedDenseAdam(fuse_finish=True): a gradient left as partial sums did not reach its parameter's .grad "
-                               "as the tensor the backward returned (it was copied on the way); construct the optimizer with "
-                               "fuse_finish=False for this model")
-        if _PENDING:  # (entries of tensors that are gone -- a gradient autograd dropped: unclaimed two steps later)
-            _GENERATION[0] += 1
-            for ptr in [q for q, e in _PENDING.items() if e[3] < _GENERATION[0] - 2]:
-                del _PENDING[ptr]
+        _launch_fused(
+            [(p.data, gr, m, v, st) for p, gr, m, v, st in rows], _adam_tables,
+            lambda tab, src, wg: _lib.check(_lib.lib().tzr_dense_adam_fused(
+                tab, src, len(tab), C.byref(wg) if wg is not None else None, _lib.ptr(self._lr_dev), g["lr"], b1, b2, g["eps"],
+                g["weight_decay"], _lib.stream_ptr(self.device)), "tzr_dense_adam_fused"))
+        _after_fused_step(self)
 
     def state_dict(self) -> dict:
         return {"state": {i: {"step": self._state[i, 0].clone(), "exp_avg": m, "exp_avg_sq": v}

@@ -177,6 +177,11 @@ def _as(kind, v):
     return kind(v)
 
 
+def has_learning_rate(optimizer_block) -> bool:
+    """does the block set its `learning_rate` oneof?  (a `part_optimizers` entry without one follows the main block's)"""
+    return optimizer_block is not None and any(optimizer_block.has(name) for name in _BLOCKS)
+
+
 def create_scheduler(optimizer, optimizer_block) -> BaseLR:
     """The `learning_rate` oneof of a parsed `sparse_optimizer {...}` / `dense_optimizer {...}` block
     (config.Msg) -> schedule; field defaults from protos/optimizer.proto:211-268.  A block without
