@@ -3,6 +3,7 @@
 fused sparse optimizer from the config) -> train on synthetic Criteo-shaped batches.
 
     python examples/train_from_config.py tests/golden/deepfm_mini.config
+    python examples/train_from_config.py tests/golden/mmoe_seq_mini.config     (a click history inside the DEEP group)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""
@@ -28,12 +29,18 @@ def synthetic_batches(spec, n_rows, batch_size, seed=0):
     dense = [f for f in spec.features if not f.is_sparse]
     for s in range(0, n_rows, batch_size):
         b = min(batch_size, n_rows - s)
-        ids = np.concatenate([rng.integers(0, f.num_embeddings, size=b) for f in sparse]).astype(np.int64)
-        kjt = KeyedJaggedTensor([f.name for f in sparse], torch.from_numpy(ids), torch.ones(len(sparse) * b, dtype=torch.int32),
-                                uniform_length=1)
+        # one id per sample, except the sub-features of a `sequence_feature` block: a history of 0 .. sequence_length ids, the
+        # same lengths for every sub-feature of one block
+        seq_lens = {}
+        lens = [seq_lens.setdefault(f.name.split("__")[0], rng.integers(0, (f.sequence_length or 8) + 1, size=b).astype(np.int32))
+                if f.is_sequence else np.ones(b, np.int32) for f in sparse]
+        ids = np.concatenate([rng.integers(0, f.num_embeddings, size=int(ln.sum())) for f, ln in zip(sparse, lens)]).astype(np.int64)
+        kjt = KeyedJaggedTensor([f.name for f in sparse], torch.from_numpy(ids), torch.from_numpy(np.concatenate(lens)),
+                                uniform_length=None if seq_lens else 1)
         kt = KeyedTensor([f.name for f in dense], [f.value_dim for f in dense],
                          torch.from_numpy(rng.random((b, sum(f.value_dim for f in dense)), dtype=np.float32)))
-        yield Batch({BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt}, {spec.label_fields[0]: torch.from_numpy((rng.random(b) < 0.25).astype(np.int64))})
+        yield Batch({BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt},
+                    {name: torch.from_numpy((rng.random(b) < 0.25).astype(np.int64)) for name in spec.label_fields})
 
 
 def main(path):

@@ -834,6 +834,38 @@ int tzr_din_attn_bwd(const float* d_grad_out, int64_t grad_out_stride, const flo
                      int64_t kv_stride, int D, const int64_t* d_offsets, int64_t B, int64_t max_len, float* d_ds,
                      float* d_dkv, int64_t dkv_stride, void* stream);
 
+/* The two cheap encoders of a DEEP group's `sequence_encoders`, over the same jagged rows: replace SimpleAttention.forward and
+ * PoolingEncoder.forward on padded [B, L, D] tensors (tzrec/modules/sequence.py:131-218).  Conventions of tzr_din_attn_*: rows
+ * [N, D], offsets int64[B+1], a position at index >= max_len inside a sample does not exist for the encoder; D a multiple of 4
+ * and at most 256 (one lane per float4 piece of a row), strides in floats (multiples of 4), 16-byte aligned pointers;
+ * TZR_ERR_UNSUPPORTED for a D, stride or max_len outside these limits, TZR_ERR_INVALID for a null or misaligned pointer;
+ * B == 0 is TZR_OK without a launch, N == 0 needs no row pointer.  One wave per sample, fixed summation order, no atomics:
+ * bit-reproducible.  csrc/jagged_encoders.hip.
+ *   tzr_jagged_dot_attn_fwd  s_n = k_n . q_b; p = softmax of s over sample b's positions; out[b] = sum_n p_n k_n; d_p [N] is
+ *                            written for the backward (0 for positions at or behind max_len).  max_len <= 2048 (a sample's
+ *                            scores live in LDS).  The rows are read once where a wave holds them (16 * (64 / P) positions,
+ *                            P = D / 4 rounded up to a power of two), twice for a longer sample.
+ *   tzr_jagged_dot_attn_bwd  t_n = g_b . k_n; ds_n = p_n (t_n - sum_m p_m t_m); d_dkv[n] = p_n g_b + ds_n q_b (zero rows at or
+ *                            behind max_len); d_dq[b] = sum_n ds_n k_n.
+ *                            A sample with no position: out[b] = 0 and d_dq[b] = 0 (the reference's uniform softmax over zero
+ *                            padding rows gives the same).
+ *   tzr_jagged_pool_fwd      out[b] = sum of the first min(len, max_len) rows; mode TZR_POOL_MEAN divides by
+ *                            max(min(len, max_len), 1).  Any max_len >= 0.
+ *   tzr_jagged_pool_bwd      d_dkv[n] = g_b (mean: / the same count) for those rows, zero rows for positions at or behind
+ *                            max_len (as tzr_padded_dense_to_jagged).  tzr_segment_reduce_* has no max_len and stays as it is.
+ * Entry points only, no struct or constant changes: the ABI version stays 15. */
+int tzr_jagged_dot_attn_fwd(const float* d_kv, int64_t kv_stride, const float* d_q, int64_t q_stride, int D,
+                            const int64_t* d_offsets, int64_t B, int64_t N, int64_t max_len, float* d_out,
+                            int64_t out_stride, float* d_p, void* stream);
+int tzr_jagged_dot_attn_bwd(const float* d_grad_out, int64_t grad_out_stride, const float* d_p, const float* d_kv,
+                            int64_t kv_stride, const float* d_q, int64_t q_stride, int D, const int64_t* d_offsets,
+                            int64_t B, int64_t N, int64_t max_len, float* d_dkv, int64_t dkv_stride, float* d_dq,
+                            int64_t dq_stride, void* stream);
+int tzr_jagged_pool_fwd(const float* d_kv, int64_t kv_stride, int D, const int64_t* d_offsets, int64_t B, int64_t N,
+                        int64_t max_len, int mode, float* d_out, int64_t out_stride, void* stream);
+int tzr_jagged_pool_bwd(const float* d_grad_out, int64_t grad_out_stride, int D, const int64_t* d_offsets, int64_t B,
+                        int64_t N, int64_t max_len, int mode, float* d_dkv, int64_t dkv_stride, void* stream);
+
 /* ---- native step driver (csrc/step_driver.hip) ------------------------------------------------------------------
  * Replaces the host side of a steady-state train step of tzrec's pipeline (tzrec/utils/dist_util.py:221-303: Python +
  * torch.distributed calls per collective) for a sharded step that was cut into captured hipGraphs: ONE call queues the

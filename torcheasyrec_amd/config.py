@@ -130,11 +130,38 @@ class FeatureSpec:
 
 
 @dataclass
+class SeqGroupSpec:
+    """One `sequence_groups` entry of a DEEP feature group (protos/model.proto:21-27)"""
+
+    group_name: str
+    feature_names: List[str]
+    embedding_name_suffix: Optional[str] = None
+
+
+SEQ_ENCODER_KINDS = ("din_encoder", "simple_attention", "pooling_encoder")  # of protos/seq_encoder.proto:63-71, the ones built
+
+
+@dataclass
+class SeqEncoderSpec:
+    """One `sequence_encoders` entry (protos/seq_encoder.proto:6-35)"""
+
+    kind: str  # one of SEQ_ENCODER_KINDS
+    input: str  # the sequence group it reads
+    max_seq_length: int = 0
+    attn_mlp: Optional[dict] = None  # din_encoder: {"hidden_units": [...]}
+    pooling_type: str = "mean"  # pooling_encoder: sum | mean
+
+
+@dataclass
 class FeatureGroupSpec:
     group_name: str
     feature_names: List[str]
     group_type: str = "DEEP"  # DEEP | WIDE | SEQUENCE
     embedding_name_suffix: Optional[str] = None
+    # a DEEP group's nested sequences: every encoder reduces its group's [B, L, D] to [B, D'], and the group's tensor is
+    # cat(own features, encoder 0, encoder 1, ...) (tzrec/modules/embedding.py:196-306, 529-536)
+    sequence_groups: List[SeqGroupSpec] = field(default_factory=list)
+    sequence_encoders: List[SeqEncoderSpec] = field(default_factory=list)
 
 
 @dataclass
@@ -246,6 +273,68 @@ def dense_optimizer_from_config(opt: Msg) -> DenseOptimizerConfig:
     return cfg
 
 
+def _sequence_blocks(g: Msg, seen_seq_names: List[str]):
+    """The `sequence_groups` / `sequence_encoders` of one feature group, supplemented and validated as the reference's
+    EmbeddingGroup._inspect_and_supplement_feature_group does (tzrec/modules/embedding.py:313-383): a single unnamed sequence
+    group takes the parent's name, an encoder without `input` the only group; the parent's `embedding_name_suffix` is
+    inherited (:240-250)."""
+    name = g.one("group_name")
+    sgs, encs = g.many("sequence_groups"), g.many("sequence_encoders")
+    if not sgs and not encs:
+        return [], []
+    if str(g.one("group_type", "DEEP")) != "DEEP":
+        raise ValueError(f"feature group {name}: sequence_groups and sequence_encoders belong in a DEEP group, this one is "
+                         f"{g.one('group_type')}")
+    if not encs:
+        raise ValueError(f"feature group {name} has sequence_groups but no sequence_encoders")
+    if not sgs:
+        raise ValueError(f"feature group {name} has sequence_encoders but no sequence_groups")
+    if len(sgs) > 1 and not all(sg.has("group_name") for sg in sgs):
+        raise ValueError(f"feature group {name} has {len(sgs)} sequence_groups: every one of them needs a group_name")
+    groups = []
+    for sg in sgs:
+        sname = str(sg.one("group_name", name))
+        if sname in seen_seq_names:
+            raise ValueError(f"sequence group name {sname} is used twice")
+        seen_seq_names.append(sname)
+        groups.append(SeqGroupSpec(sname, [str(f) for f in sg.many("feature_names")],
+                                   sg.one("embedding_name_suffix") or g.one("embedding_name_suffix")))
+    has_encoder = {sg.group_name: False for sg in groups}
+    encoders = []
+    for enc in encs:
+        if len(enc) != 1:
+            raise ValueError(f"feature group {name}: a sequence_encoders entry holds exactly one encoder, got {sorted(enc)}")
+        (kind, body), = enc.items()
+        if kind not in SEQ_ENCODER_KINDS:
+            raise NotImplementedError(f"feature group {name}: sequence encoder {kind!r} is not built (built: {', '.join(SEQ_ENCODER_KINDS)})")
+        m = body[-1]
+        inp = m.one("input")
+        if inp is None:
+            if len(groups) != 1:
+                raise ValueError(f"feature group {name} has {len(groups)} sequence_groups: its {kind} needs an `input`")
+            inp = groups[0].group_name
+        if inp not in has_encoder:
+            raise ValueError(f"feature group {name}: {kind} reads {inp!r}, which is none of its sequence_groups {sorted(has_encoder)}")
+        has_encoder[inp] = True
+        spec = SeqEncoderSpec(kind=kind, input=str(inp), max_seq_length=int(m.one("max_seq_length", 0)))
+        if kind == "din_encoder":
+            if not m.has("attn_mlp"):
+                raise ValueError(f"feature group {name}: din_encoder needs attn_mlp")
+            other = sorted(k for k in m.one("attn_mlp") if k != "hidden_units")
+            if other:  # (DINEncoder's attention MLP is the plain Linear + ReLU stack: nothing is dropped silently)
+                raise NotImplementedError(f"feature group {name}: din_encoder attn_mlp fields {other}")
+            spec.attn_mlp = {"hidden_units": [int(x) for x in m.one("attn_mlp").many("hidden_units")]}
+        if kind == "pooling_encoder":
+            spec.pooling_type = str(m.one("pooling_type", "mean"))
+            if spec.pooling_type not in ("sum", "mean"):
+                raise ValueError(f"feature group {name}: pooling_encoder pooling_type {spec.pooling_type!r}: sum | mean")
+        encoders.append(spec)
+    for sname, ok in has_encoder.items():
+        if not ok:
+            raise ValueError(f"feature group {name}: sequence group {sname} has no sequence encoder")
+    return groups, encoders
+
+
 def load_pipeline_spec(text: str) -> PipelineSpec:
     cfg = parse_text_proto(text)
     spec = PipelineSpec()
@@ -289,10 +378,13 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
         else:
             spec.features.append(one_feature(kind, f))
     mc = cfg.one("model_config", Msg())
+    seq_names: List[str] = []
     for g in mc.many("feature_groups"):
+        seq_groups, seq_encoders = _sequence_blocks(g, seq_names)
         spec.feature_groups.append(FeatureGroupSpec(
             group_name=g.one("group_name"), feature_names=list(g.many("feature_names")),
-            group_type=str(g.one("group_type", "DEEP")), embedding_name_suffix=g.one("embedding_name_suffix")))
+            group_type=str(g.one("group_type", "DEEP")), embedding_name_suffix=g.one("embedding_name_suffix"),
+            sequence_groups=seq_groups, sequence_encoders=seq_encoders))
     skip = {"feature_groups", "metrics", "losses", "num_class", "train_metrics", "variational_dropout",
             "kd", "use_pareto_loss_weight", "pareto"}
     for k, v in mc.items():

@@ -144,7 +144,7 @@ class EmbeddingGroup(nn.Module):
         self._table_sharding_types: Dict[str, List[str]] = {}
         self._global_sharding_types = list(global_sharding_types)
         feat_group_table: Dict[str, Dict[str, str]] = {}
-        self._seq_groups = [g for g in feature_groups if g.group_type == "SEQUENCE"]
+        self._seq_groups = [g for g in feature_groups if g.group_type == "SEQUENCE"] + self._nested_sequence_groups(feature_groups)
         feature_groups = [g for g in feature_groups if g.group_type != "SEQUENCE"]
         self._init_sequence_groups(name_to_feature, device, sparse_optimizer, row_layout)
         for g in feature_groups:
@@ -194,6 +194,7 @@ class EmbeddingGroup(nn.Module):
             self._group_feature_names[g.group_name] = list(g.feature_names)
             self._group_blocks[g.group_name] = blocks
             self._group_dims[g.group_name] = dims
+        self._init_sequence_encoders(feature_groups, device)
         self._dense_dims = OrderedDict((f.name, f.value_dim) for f in features if not f.is_sparse)
         self.has_sparse = len(configs) > 0
         # the lookup writes, per group, the contiguous run(s) of sparse blocks; groups that mix dense
@@ -263,6 +264,67 @@ class EmbeddingGroup(nn.Module):
             from .zch import ManagedCollisionEmbeddingBagCollection, zch_config_from_msg
 
             self.mc = ManagedCollisionEmbeddingBagCollection(self.ebc, {t: zch_config_from_msg(z) for t, z in zch_blocks.items()})
+
+    # -- `sequence_groups` / `sequence_encoders` of a DEEP group (tzrec/modules/embedding.py:196-306, 529-536) ----------------
+    # A nested sequence group is a sequence group like any other -- own name, own unpooled tables, `<g>.query` / `<g>.sequence`
+    # in the output dict -- and every encoder of the parent reduces one of them to [B, D']; the parent's tensor becomes
+    # cat(own features, encoder 0, encoder 1, ...).
+    def _nested_sequence_groups(self, feature_groups: Sequence[FeatureGroupSpec]) -> List[FeatureGroupSpec]:
+        self._nested_parent: Dict[str, str] = {}  # nested sequence group -> the DEEP group that carries it
+        nested: List[FeatureGroupSpec] = []
+        for g in feature_groups:
+            sgs, encs = list(getattr(g, "sequence_groups", None) or []), list(getattr(g, "sequence_encoders", None) or [])
+            if not sgs and not encs:
+                continue
+            if g.group_type != "DEEP":
+                raise ValueError(f"feature group {g.group_name}: sequence_groups and sequence_encoders belong in a DEEP group, "
+                                 f"this one is {g.group_type}")
+            if not sgs or not encs:
+                raise ValueError(f"feature group {g.group_name} needs both sequence_groups and sequence_encoders")
+            for sg in sgs:
+                if sg.group_name in self._nested_parent or any(o.group_name == sg.group_name and o is not g for o in feature_groups):
+                    raise ValueError(f"sequence group name {sg.group_name} of feature group {g.group_name} is the name of another group")
+                self._nested_parent[sg.group_name] = g.group_name
+                nested.append(FeatureGroupSpec(sg.group_name, list(sg.feature_names), "SEQUENCE",
+                                               sg.embedding_name_suffix or g.embedding_name_suffix))
+            for e in encs:
+                if e.input not in {sg.group_name for sg in sgs}:
+                    raise ValueError(f"feature group {g.group_name}: {e.kind} reads {e.input!r}, which is none of its sequence_groups")
+            for sg in sgs:
+                if not any(e.input == sg.group_name for e in encs):
+                    raise ValueError(f"feature group {g.group_name}: sequence group {sg.group_name} has no sequence encoder")
+        return nested
+
+    def nested_sequence_groups(self) -> List[str]:
+        """names of the sequence groups that DEEP groups carry in `sequence_groups`"""
+        return list(self._nested_parent)
+
+    def _init_sequence_encoders(self, feature_groups: Sequence[FeatureGroupSpec], device) -> None:
+        from .sequence import create_seq_encoder, encoder_jagged_limit
+
+        seq_dims = {f"{g}.{part}": info[f"{part}_dim"] for g, info in self._seq_info.items() for part in ("query", "sequence")}
+        self._group_name_to_seq_encoders = nn.ModuleDict()
+        for g in feature_groups:
+            specs = list(getattr(g, "sequence_encoders", None) or [])
+            if not specs:
+                continue
+            encs = nn.ModuleList([create_seq_encoder(e, seq_dims) for e in specs])
+            if device is not None:
+                encs.to(device)
+            self._group_name_to_seq_encoders[g.group_name] = encs
+            for i, enc in enumerate(encs):
+                self._group_dims[g.group_name][f"{g.group_name}_seq_encoder_{i}"] = enc.output_dim()
+        # a nested group goes to its encoders as ROWS (nothing padded, no read-back of the batch's longest sequence) when its
+        # features configure `sequence_length`, share one set of lengths (one sequence_feature block, one id per step) and every
+        # encoder that reads it evaluates the jagged form; a model that reads the padded `<g>.sequence` itself takes the group
+        # out of the set again (rank_model.ConfigMultiTowerDIN)
+        for sg in self._nested_parent:
+            info = self._seq_info[sg]
+            readers = [enc for encs in self._group_name_to_seq_encoders.values() for enc in encs if enc.input() == sg]
+            if info["max_len"] and len({f.name.split("__")[0] for f in info["sequence"]}) == 1 \
+                    and not any(getattr(f, "value_dim", 1) not in (0, 1) for f in info["sequence"]) \
+                    and all(encoder_jagged_limit(enc, int(info["max_len"])) is None for enc in readers):
+                self.jagged_sequence_groups.add(sg)
 
     # -- SEQUENCE groups (SequenceEmbeddingGroupImpl, tzrec/modules/embedding.py:993-1498) ---------------
     # Every sparse feature of a sequence group is looked up UNPOOLED through its own tables (an
@@ -469,6 +531,8 @@ class EmbeddingGroup(nn.Module):
             out.update(self._forward_sequence_groups(batch.sparse_features.get(BASE_DATA_GROUP), dense_cols,
                                                      batch.sequence_mulval_lengths.get(BASE_DATA_GROUP),
                                                      batch.sequence_dense_features))
+        for g, encs in self._group_name_to_seq_encoders.items():
+            out[g] = torch.cat([out[g]] + [enc(out) for enc in encs], dim=1)
         return out
 
 

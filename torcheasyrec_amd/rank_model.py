@@ -77,7 +77,8 @@ class RankModel(nn.Module):
 
     def dense_parameters(self):
         for n, p in self.named_parameters():
-            if not n.startswith("embedding_group."):
+            # (the sequence encoders of a DEEP group live inside the embedding group, as in the reference: dense all the same)
+            if not n.startswith("embedding_group.") or n.startswith("embedding_group._group_name_to_seq_encoders."):
                 yield p
 
     @property
@@ -198,7 +199,10 @@ class ConfigMultiTowerDIN(RankModel):
                 # (a group without a configured sequence_length pads to the batch's longest sequence in the reference: nothing
                 # is truncated there, and the jagged kernels keep at most DIN_JAGGED_MAX_LEN positions of a sample -- such
                 # groups stay on the padded form)
-                eg.jagged_sequence_groups.add(g)
+                if g not in eg.nested_sequence_groups() or g in eg.jagged_sequence_groups:  # (a nested group: only with its encoders)
+                    eg.jagged_sequence_groups.add(g)
+            else:
+                eg.jagged_sequence_groups.discard(g)  # (a nested group of a DEEP group: this tower reads its padded tensor)
         self.final_mlp = None
         if m.has("final"):
             self.final_mlp = mlp_from_msg(total, m.one("final"))

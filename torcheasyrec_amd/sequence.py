@@ -547,6 +547,7 @@ class DINEncoder(nn.Module):
         super().__init__()
         if query_dim > sequence_dim:
             raise ValueError("query_dim > sequence_dim not supported yet.")
+        self._input = input
         self._query_dim, self._sequence_dim, self._max_seq_length = query_dim, sequence_dim, max_seq_length
         self.mlp = MLP(sequence_dim * 4, list(attn_mlp["hidden_units"]))
         self.linear = nn.Linear(self.mlp.hidden_units[-1], 1)
@@ -555,6 +556,9 @@ class DINEncoder(nn.Module):
         self._sequence_length_name = f"{input}.sequence_length"
         self.split_first_layer = True  # see forward; False = the reference's literal [q, k, q - k, q * k] input
         self.row_bucket = None  # forward_jagged: rows of the attention MLP's input = N rounded up to a multiple of this (None: 16384 on a GPU, 1 elsewhere)
+
+    def input(self) -> str:
+        return self._input
 
     def output_dim(self) -> int:
         return self._sequence_dim
@@ -637,3 +641,220 @@ class DINEncoder(nn.Module):
             a = self.linear(self.mlp(torch.cat([q, sequence, q - sequence, q * sequence], dim=-1))).transpose(1, 2)
         scores = torch.where(mask.unsqueeze(1), a, torch.ones_like(a) * (-(2 ** 31) + 1))
         return torch.matmul(torch.softmax(scores, dim=-1), sequence).squeeze(1)
+
+
+# ---- simple attention and pooling on the jagged positions (csrc/jagged_encoders.hip) ---------------------------------
+JAGGED_ENCODER_MAX_LEN = 2048  # (JE_MAXLEN: tzr_jagged_dot_attn_* keep a sample's scores in LDS)
+JAGGED_ENCODER_MAX_DIM = 256  # (JE_MAXDIM: one lane per float4 piece of a row)
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """[n, D] rows as the kernels take them: unit column stride, row stride a multiple of 4 floats, 16-byte aligned (a column
+    slice of a wider tensor passes as it is), else a contiguous copy"""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+class _JaggedDotAttnFn(torch.autograd.Function):
+    """out_b = sum_n softmax_n(k_n . q_b) k_n over sample b's rows, one node: tzr_jagged_dot_attn_fwd / _bwd"""
+
+    @staticmethod
+    def forward(ctx, values, query, offsets, max_len):
+        values, query = _rows(values), _rows(query)
+        N, D = values.shape
+        B = offsets.numel() - 1
+        dev = values.device
+        out = torch.empty(max(B, 1), D, dtype=torch.float32, device=dev)
+        p = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().tzr_jagged_dot_attn_fwd(_lib.ptr(values), values.stride(0) if N else D, _lib.ptr(query),
+                                                      query.stride(0) if B else D, D, _lib.ptr(offsets), B, N, max_len, _lib.ptr(out),
+                                                      out.stride(0), _lib.ptr(p), _lib.stream_ptr(dev)), "tzr_jagged_dot_attn_fwd")
+        ctx.save_for_backward(values, query, offsets, p)
+        ctx.max_len = max_len
+        return out[:B]
+
+    @staticmethod
+    def backward(ctx, gout):
+        values, query, offsets, p = ctx.saved_tensors
+        N, D = values.shape
+        B = offsets.numel() - 1
+        dev = values.device
+        gout = _rows(gout)
+        dkv = torch.empty(max(N, 1), D, dtype=torch.float32, device=dev)
+        dq = torch.empty(max(B, 1), D, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().tzr_jagged_dot_attn_bwd(_lib.ptr(gout), gout.stride(0) if B else D, _lib.ptr(p), _lib.ptr(values),
+                                                      values.stride(0) if N else D, _lib.ptr(query), query.stride(0) if B else D, D,
+                                                      _lib.ptr(offsets), B, N, ctx.max_len, _lib.ptr(dkv), dkv.stride(0), _lib.ptr(dq),
+                                                      dq.stride(0), _lib.stream_ptr(dev)), "tzr_jagged_dot_attn_bwd")
+        return dkv[:N], dq[:B], None, None
+
+
+class _JaggedPoolFn(torch.autograd.Function):
+    """sum / mean of the first min(len, max_len) rows of every sample: tzr_jagged_pool_fwd / _bwd"""
+
+    @staticmethod
+    def forward(ctx, values, offsets, max_len, mode):
+        values = _rows(values)
+        N, D = values.shape
+        B = offsets.numel() - 1
+        out = torch.empty(max(B, 1), D, dtype=torch.float32, device=values.device)
+        _lib.check(_lib.lib().tzr_jagged_pool_fwd(_lib.ptr(values), values.stride(0) if N else D, D, _lib.ptr(offsets), B, N, max_len, mode,
+                                                  _lib.ptr(out), out.stride(0), _lib.stream_ptr(values.device)), "tzr_jagged_pool_fwd")
+        ctx.save_for_backward(offsets)
+        ctx.cfg = (N, D, max_len, mode)
+        return out[:B]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (offsets,) = ctx.saved_tensors
+        N, D, max_len, mode = ctx.cfg
+        gout = _rows(gout)
+        B = offsets.numel() - 1
+        dkv = torch.empty(max(N, 1), D, dtype=torch.float32, device=gout.device)
+        _lib.check(_lib.lib().tzr_jagged_pool_bwd(_lib.ptr(gout), gout.stride(0) if B else D, D, _lib.ptr(offsets), B, N, max_len, mode,
+                                                  _lib.ptr(dkv), dkv.stride(0), _lib.stream_ptr(gout.device)), "tzr_jagged_pool_bwd")
+        return dkv[:N], None, None, None
+
+
+def jagged_dot_attention(values: torch.Tensor, query: torch.Tensor, offsets: torch.Tensor, max_len: int) -> torch.Tensor:
+    """values [N, D] rows, query [B, D], offsets int64 [B + 1] -> [B, D]; positions at index >= max_len inside a sample do not
+    take part; a sample without a position gives a zero row"""
+    return _JaggedDotAttnFn.apply(values, query, offsets, int(max_len))
+
+
+def jagged_pool(values: torch.Tensor, offsets: torch.Tensor, max_len: int, pooling: str = "mean") -> torch.Tensor:
+    """values [N, D] rows, offsets int64 [B + 1] -> [B, D]: sum or mean (over max(count, 1)) of every sample's first
+    min(len, max_len) rows"""
+    if pooling not in ("sum", "mean"):
+        raise ValueError(f"jagged_pool pooling {pooling!r}: sum | mean")
+    return _JaggedPoolFn.apply(values, offsets, int(max_len), _lib.POOL_MEAN if pooling == "mean" else _lib.POOL_SUM)
+
+
+def _jagged_dim_limit(what: str, D: int) -> Optional[str]:
+    if D % 4:
+        return f"{what}: sequence_dim {D} must be a multiple of 4"
+    if D > JAGGED_ENCODER_MAX_DIM:
+        return f"{what}: sequence_dim {D} must be at most {JAGGED_ENCODER_MAX_DIM}"
+    return None
+
+
+class SimpleAttention(nn.Module):
+    """Dot-product attention of the query over the sequence (the reference's SimpleAttention, constructor and forward contract
+    of tzrec/modules/sequence.py:131-171): scores = sequence . query -> masked softmax -> weighted sum.  Evaluated on the padded
+    `<input>.sequence` [B, L, D] as the reference does, or -- when the dict carries `<input>.sequence_jagged`, `_offsets` and
+    `_max_len` -- on the jagged rows (csrc/jagged_encoders.hip).  The reference multiplies [B, L, sequence_dim] by
+    [B, query_dim, 1] and fails inside matmul when the two dims differ; here that is an error at construction."""
+
+    def __init__(self, sequence_dim: int, query_dim: int, input: str, max_seq_length: int = 0, **kwargs) -> None:
+        super().__init__()
+        if query_dim != sequence_dim:
+            raise ValueError(f"simple_attention on {input!r}: query_dim {query_dim} must equal sequence_dim {sequence_dim}")
+        self._input = input
+        self._sequence_dim, self._query_dim, self._max_seq_length = sequence_dim, query_dim, max_seq_length
+        self._query_name = f"{input}.query"
+        self._sequence_name = f"{input}.sequence"
+        self._sequence_length_name = f"{input}.sequence_length"
+
+    def input(self) -> str:
+        return self._input
+
+    def output_dim(self) -> int:
+        return self._sequence_dim
+
+    def jagged_limit(self, max_len: int = 0) -> Optional[str]:
+        """None when the jagged kernels evaluate this encoder on sequences padded / truncated to `max_len`, else the limit missed"""
+        lim = _jagged_dim_limit("simple_attention", self._sequence_dim)
+        if lim is None and (min(max_len, self._max_seq_length) if self._max_seq_length > 0 else max_len) > JAGGED_ENCODER_MAX_LEN:
+            lim = f"simple_attention: max_len {max_len} must be at most {JAGGED_ENCODER_MAX_LEN}"
+        return lim
+
+    def forward(self, sequence_embedded: Dict[str, torch.Tensor]) -> torch.Tensor:
+        query = sequence_embedded[self._query_name]
+        jag = sequence_embedded.get(self._sequence_name + "_jagged")
+        if jag is not None:
+            max_len = int(sequence_embedded[self._sequence_name + "_max_len"])
+            limit = self.jagged_limit(max_len)
+            if limit is not None:
+                raise ValueError(f"{limit} (use the padded form)")
+            if self._max_seq_length > 0:
+                max_len = min(max_len, self._max_seq_length)
+            return jagged_dot_attention(jag, query, sequence_embedded[self._sequence_name + "_offsets"], max_len)
+        sequence = sequence_embedded[self._sequence_name]
+        sequence_length = sequence_embedded[self._sequence_length_name]
+        if self._max_seq_length > 0:
+            sequence_length = torch.clamp_max(sequence_length, self._max_seq_length)
+            sequence = sequence[:, : self._max_seq_length, :]
+        mask = torch.arange(sequence.size(1), device=sequence_length.device).unsqueeze(0) < sequence_length.unsqueeze(1)
+        a = torch.matmul(sequence, query.unsqueeze(2)).squeeze(2)
+        scores = torch.softmax(torch.where(mask, a, torch.ones_like(a) * (-(2 ** 31) + 1)), dim=-1)
+        return torch.matmul(scores.unsqueeze(1), sequence).squeeze(1)
+
+
+class PoolingEncoder(nn.Module):
+    """Sum / mean of the sequence (the reference's PoolingEncoder, tzrec/modules/sequence.py:174-218; the mean divides by
+    max(length, 1)), on the padded `<input>.sequence` or on the jagged rows like `SimpleAttention`."""
+
+    def __init__(self, sequence_dim: int, input: str, pooling_type: str = "mean", max_seq_length: int = 0, **kwargs) -> None:
+        super().__init__()
+        assert pooling_type in ["sum", "mean"], "only sum|mean pooling type supported now."
+        self._input = input
+        self._sequence_dim, self._pooling_type, self._max_seq_length = sequence_dim, pooling_type, max_seq_length
+        self._sequence_name = f"{input}.sequence"
+        self._sequence_length_name = f"{input}.sequence_length"
+
+    def input(self) -> str:
+        return self._input
+
+    def output_dim(self) -> int:
+        return self._sequence_dim
+
+    def jagged_limit(self, max_len: int = 0) -> Optional[str]:
+        return _jagged_dim_limit("pooling_encoder", self._sequence_dim)
+
+    def forward(self, sequence_embedded: Dict[str, torch.Tensor]) -> torch.Tensor:
+        jag = sequence_embedded.get(self._sequence_name + "_jagged")
+        if jag is not None:
+            limit = self.jagged_limit()
+            if limit is not None:
+                raise ValueError(f"{limit} (use the padded form)")
+            max_len = int(sequence_embedded[self._sequence_name + "_max_len"])
+            if self._max_seq_length > 0:
+                max_len = min(max_len, self._max_seq_length)
+            return jagged_pool(jag, sequence_embedded[self._sequence_name + "_offsets"], max_len, self._pooling_type)
+        sequence = sequence_embedded[self._sequence_name]
+        if self._max_seq_length > 0:
+            sequence = sequence[:, : self._max_seq_length, :]
+        feature = torch.sum(sequence, dim=1)
+        if self._pooling_type == "mean":
+            sequence_length = sequence_embedded[self._sequence_length_name]
+            if self._max_seq_length > 0:
+                sequence_length = torch.clamp_max(sequence_length, self._max_seq_length)
+            # (a count is never more than the positions the tensor holds: the reference pads to the batch's longest sequence, so
+            # there the clamp changes nothing; a group padded to its configured `sequence_length` truncates longer samples)
+            feature = feature / torch.clamp(sequence_length, 1, max(sequence.size(1), 1)).unsqueeze(1)
+        return feature
+
+
+def encoder_jagged_limit(enc: nn.Module, max_len: int) -> Optional[str]:
+    """None when `enc` evaluates a sequence group handed over as rows with padded length `max_len`, else why not"""
+    if isinstance(enc, DINEncoder):
+        lim = enc.jagged_limit()
+        eff = min(max_len, enc._max_seq_length) if enc._max_seq_length > 0 else max_len
+        if lim is None and eff > DIN_JAGGED_MAX_LEN:
+            lim = f"max_len {eff} must be at most {DIN_JAGGED_MAX_LEN}"
+        return lim
+    return enc.jagged_limit(max_len)
+
+
+def create_seq_encoder(spec, group_total_dim: Dict[str, int]) -> nn.Module:
+    """The encoder module of one `config.SeqEncoderSpec` (the reference's create_seq_encoder, tzrec/modules/sequence.py:370-394);
+    `group_total_dim`: "<sequence group>.query" / ".sequence" -> width."""
+    sequence_dim, query_dim = group_total_dim[f"{spec.input}.sequence"], group_total_dim[f"{spec.input}.query"]
+    if spec.kind == "din_encoder":
+        return DINEncoder(sequence_dim, query_dim, spec.input, attn_mlp=dict(spec.attn_mlp), max_seq_length=spec.max_seq_length)
+    if spec.kind == "simple_attention":
+        return SimpleAttention(sequence_dim, query_dim, spec.input, max_seq_length=spec.max_seq_length)
+    if spec.kind == "pooling_encoder":
+        return PoolingEncoder(sequence_dim, spec.input, pooling_type=spec.pooling_type, max_seq_length=spec.max_seq_length)
+    raise NotImplementedError(f"sequence encoder {spec.kind!r} is not built")
