@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """End to end on one MI355X from a tzrec text config: parse -> build the rank model (tables, groups,
-fused sparse optimizer from the config) -> train on synthetic Criteo-shaped batches.
+fused sparse optimizer from the config) -> train on synthetic Criteo-shaped batches -> evaluate the config's `metrics` on
+held-out batches (state on the device, torcheasyrec_amd/metrics.py).
 
     python examples/train_from_config.py tests/golden/deepfm_mini.config
     python examples/train_from_config.py tests/golden/mmoe_seq_mini.config     (a click history inside the DEEP group)
@@ -84,6 +85,15 @@ def main(path):
         print("delta embedding dump:", dumper.final_dump(step))
         dumper.close()
     print("tables:", {n: tuple(w.shape) for n, w in model.embedding_group.ebc.table_weights().items()})
+    # model_config.metrics (and every task tower's) on a held-out run of batches: the evaluate half of the reference's
+    # train_and_evaluate (tzrec/main.py).  EVAL_GRAPH=1: forward and metric updates replayed from one hipGraph
+    if spec.metrics:
+        from torcheasyrec_amd.metrics import Evaluator, evaluate
+
+        bs = spec.batch_size or 1024
+        held_out = synthetic_batches(spec, int(os.environ.get("EVAL_BATCHES", "8")) * bs, bs, seed=1)
+        result = evaluate(model, held_out, Evaluator(model, spec, dev), graph=os.environ.get("EVAL_GRAPH", "0") == "1")
+        print("eval:", {k: round(float(v), 6) for k, v in result.items()})
 
 
 if __name__ == "__main__":

@@ -1050,6 +1050,52 @@ int tzr_fm_bwd(const float* d_x, int64_t x_stride, int F, int D, int64_t B,
                const float* d_grad_out, int64_t grad_out_stride, float* d_grad_x,
                int64_t grad_x_stride, void* stream);
 
+/* ---- evaluation metrics (csrc/eval_metrics.hip) ------------------------------------------------
+ * State of the binary metrics the reference builds from `model_config.metrics` (tzrec/models/rank_model.py:264-334,
+ * 375-443): torchmetrics' binned AUROC (tzrec/metrics/decay_auc.py:27-60 is the same form), tzrec/metrics/
+ * normalized_entropy.py and tzrec/metrics/grouped_auc.py.  Every update is one asynchronous launch on the caller's
+ * stream that reads device memory only: it can sit inside a captured evaluation step.  Labels are int64 as Batch
+ * carries them; any non-zero label is the positive class.  Entry points added to version 15: no struct or older
+ * entry point changes.
+ *
+ * K14a: tzr_metric_update -- one launch per (tower, eval step) for `auc` and `normalized_entropy` together.
+ *   d_thresholds  float[T], ascending (torch.linspace(0, 1, T): the caller's own floats, so that both sides of a
+ *                 comparison see the same values), 1 <= T <= TZR_METRIC_MAX_THRESHOLDS
+ *   d_hist        uint64[(T + 1) * 2], zeroed by the caller: d_hist[bin * 2 + class] += 1 per sample, where
+ *                 bin(p) = the number of thresholds <= p, found by SEARCHING the threshold values (p >= thr[t] <=> bin > t
+ *                 for every float; a NaN falls into bin 0).  Counted per workgroup in LDS, flushed with 64-bit atomic adds:
+ *                 integers, so the result does not depend on the order.  null: no histogram (T and d_thresholds not read).
+ *   d_ne          double[3] = {sum of cross-entropy, samples, sum of labels}, zeroed by the caller.  The cross-entropy
+ *                 of a sample is torch's F.binary_cross_entropy: -(y max(log p, -100) + (1 - y) max(log(1 - p), -100));
+ *                 summed wave -> workgroup in double, one double atomic add per workgroup and word.  null: skipped.
+ * B < 0, or both states null, or a null input with B > 0: TZR_ERR_INVALID; T > TZR_METRIC_MAX_THRESHOLDS (what one
+ * workgroup's LDS histogram holds): TZR_ERR_UNSUPPORTED; B == 0: TZR_OK, nothing launched. */
+#define TZR_METRIC_MAX_THRESHOLDS 4096
+int tzr_metric_update(const float* d_probs, const int64_t* d_labels, int64_t B, const float* d_thresholds, int T,
+                      uint64_t* d_hist, double* d_ne, void* stream);
+
+/* K14b: grouped AUC, rows kept on the device.  tzr_grouped_auc_append writes row i of the batch to position
+ * cursor + i of the caller's buffers (struct of arrays, `capacity` rows each: prob float, label int32 0/1, key int64)
+ * and advances the cursor by the rows written -- the cursor lives in DEVICE memory, so a captured launch appends behind
+ * the previous replay's rows.  d_state: int64[4], zeroed by the caller = {cursor, overflow, arrivals, -}: rows that do
+ * not fit are not written and counted in `overflow`; `arrivals` is the launch's own workgroup counter (0 between
+ * launches).  B == 0: TZR_OK, nothing launched. */
+int tzr_grouped_auc_append(const float* d_probs, const int64_t* d_labels, const int64_t* d_keys, int64_t B,
+                           float* d_row_probs, int32_t* d_row_labels, int64_t* d_row_keys, int64_t capacity,
+                           int64_t* d_state, void* stream);
+
+/* tzr_grouped_auc_reduce: n rows SORTED by (key, prob) ascending (two stable sorts on the caller's side; no NaN) ->
+ * *d_auc_sum = the sum over the groups that hold both classes (grouped_auc.py:113-116) of the group's exact, tie-aware
+ * AUC, *d_groups = their number.  Per group the Mann-Whitney count with ties at one half is carried as the integer
+ * 2U = sum over positive rows of (2 negatives below + negatives tied) in int64 and divided once, in double, by
+ * 2 P N -- the value the exact ROC trapezoid has.  One row per lane; group and tie-run boundaries by binary search
+ * in the sorted rows, label counts by prefix sums: a group of any size costs its rows nothing extra.  Sums in a fixed
+ * order: the same rows give the same bits.  d_ws: tzr_grouped_auc_reduce_workspace(n) bytes, 256-byte aligned.
+ * n == 0 writes zeros. */
+size_t tzr_grouped_auc_reduce_workspace(int64_t n);
+int tzr_grouped_auc_reduce(const int64_t* d_keys, const float* d_probs, const int32_t* d_labels, int64_t n,
+                           double* d_auc_sum, int64_t* d_groups, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ TZR_OK = 0
 TZR_ERR_INVALID, TZR_ERR_UNSUPPORTED = -1, -4
 TZR_MAX_DST = 8
 TZR_MAX_FEAT_DST = 4
+METRIC_MAX_THRESHOLDS = 4096  # TZR_METRIC_MAX_THRESHOLDS
 POOL_SUM, POOL_MEAN = 0, 1
 DT_F32, DT_F16 = 0, 1
 FWD_MIXED_DTYPE = 1
@@ -275,6 +276,10 @@ _SIGNATURES = {
     "tzr_delta_collect": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _sz, _vp]),
     "tzr_fm_fwd": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp]),
     "tzr_fm_bwd": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "tzr_metric_update": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "tzr_grouped_auc_append": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "tzr_grouped_auc_reduce_workspace": (_sz, [_i64]),
+    "tzr_grouped_auc_reduce": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

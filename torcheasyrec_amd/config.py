@@ -175,6 +175,52 @@ class DenseOptimizerConfig:
     parts: List["DenseOptimizerConfig"] = field(default_factory=list)
 
 
+# the `metric` oneof of protos/metric.proto:53-66 with each member's defaults (metric.proto:4-51); `grouping_key` is required
+METRIC_DEFAULTS = {
+    "auc": {"thresholds": 200},
+    "multiclass_auc": {"thresholds": 200, "average": "macro"},
+    "recall_at_k": {"top_k": 5},
+    "mean_absolute_error": {},
+    "mean_squared_error": {},
+    "accuracy": {"threshold": 0.5, "top_k": 1},
+    "grouped_auc": {},
+    "xauc": {"sample_ratio": 1e-3, "in_batch": False},
+    "grouped_xauc": {"max_pairs_per_group": 100},
+    "normalized_entropy": {"eta": 1e-12},
+}
+
+
+@dataclass
+class MetricSpec:
+    """One `metrics { ... }` entry of the model config or of a task tower (protos/metric.proto:53-66,
+    tzrec/models/rank_model.py:264-334, multi_task_rank.py:144-161): the oneof's member and its fields as written, the proto's
+    defaults filled in.  Read for every kind; which kinds are BUILT is metrics.Evaluator's to say."""
+
+    kind: str
+    fields: dict = field(default_factory=dict)
+    tower: Optional[str] = None  # a task tower's metric: its tower_name
+    label: Optional[str] = None  # the label it is measured against (the tower's label_name, else the first label field)
+
+    @property
+    def suffix(self) -> str:
+        return f"_{self.tower}" if self.tower else ""
+
+    @property
+    def name(self) -> str:  # the key of the reference's metric dict
+        return self.kind + self.suffix
+
+
+def _metric_specs(blocks, tower: Optional[str], label: Optional[str]) -> List[MetricSpec]:
+    out = []
+    for m in blocks:
+        for kind, body in m.items():
+            given = {k: v[-1] for k, v in body[-1].items()} if isinstance(body[-1], Msg) else {}
+            if kind == "grouped_auc" and not given.get("grouping_key"):  # (a `required` field of a kind that is built)
+                raise ValueError(f"metrics: {kind} needs a grouping_key")
+            out.append(MetricSpec(kind=str(kind), fields={**METRIC_DEFAULTS.get(kind, {}), **given}, tower=tower, label=label))
+    return out
+
+
 @dataclass
 class PipelineSpec:
     features: List[FeatureSpec] = field(default_factory=list)
@@ -197,6 +243,8 @@ class PipelineSpec:
     global_sharding_types: List[str] = field(default_factory=list)
     gradient_accumulation_steps: int = 0  # train.proto:151
     grad_clipping: Optional[object] = None  # train.proto:153 -> optimizer.GradClippingConfig
+    # model_config.metrics, then every task tower's metrics in tower order (metrics.Evaluator builds them)
+    metrics: List[MetricSpec] = field(default_factory=list)
 
 
 def _num_embeddings(f: Msg, name: str) -> int:
@@ -416,4 +464,7 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
     dc = cfg.one("data_config", Msg())
     spec.batch_size = int(dc.one("batch_size", 0))
     spec.label_fields = list(dc.many("label_fields"))
+    spec.metrics = _metric_specs(mc.many("metrics"), None, spec.label_fields[0] if spec.label_fields else "label")
+    for t in (spec.model.many("task_towers") if spec.model else []):
+        spec.metrics += _metric_specs(t.many("metrics"), str(t.one("tower_name")), str(t.one("label_name")))
     return spec
