@@ -5,6 +5,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
 
     python examples/train_from_config.py tests/golden/deepfm_mini.config
     python examples/train_from_config.py tests/golden/mmoe_seq_mini.config     (a click history inside the DEEP group)
+    python examples/train_from_config.py tests/golden/jrc_mini.config          (jrc_loss over sessions, a sample weight column)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""
@@ -40,8 +41,10 @@ def synthetic_batches(spec, n_rows, batch_size, seed=0):
                                 uniform_length=None if seq_lens else 1)
         kt = KeyedTensor([f.name for f in dense], [f.value_dim for f in dense],
                          torch.from_numpy(rng.random((b, sum(f.value_dim for f in dense)), dtype=np.float32)))
-        yield Batch({BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt},
-                    {name: torch.from_numpy((rng.random(b) < 0.25).astype(np.int64)) for name in spec.label_fields})
+        labels = {name: torch.from_numpy((rng.random(b) < 0.25).astype(np.int64)) for name in spec.label_fields}
+        # data_config.sample_weight_fields: one float column each (the losses read them, torcheasyrec_amd/losses.py)
+        weights = {name: torch.from_numpy((0.5 + rng.random(b)).astype(np.float32)) for name in spec.sample_weight_fields}
+        yield Batch({BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt}, labels, weights)
 
 
 def main(path):

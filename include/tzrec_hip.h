@@ -460,6 +460,64 @@ int tzr_bce_logits(const float* d_logits, const void* d_labels, int labels_items
                    int labels_are_float, const float* d_sample_weight, int64_t B, float* d_loss,
                    float* d_grad_logits, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the losses a config names (csrc/loss_ops.hip) --------------------------------------------------------------------
+ * tzrec/protos/loss.proto:44-63 as tzrec/models/rank_model.py:181-262 and multi_task_rank.py:97-142 combine them with the
+ * sample weights.  Common to the three entry points:
+ *   labels       d_labels with labels_itemsize / labels_are_float: float32, int32 or int64 (else TZR_ERR_UNSUPPORTED)
+ *   row weights  w_i = d_weight[i] (1 when null) * (d_space_label[i] > 0 ? in_w : out_w) (1 when d_space_label is null;
+ *                the task-space indicator label, typed by space_itemsize / space_is_float like the labels)
+ *   *d_loss      = task_weight * sum_i(w_i l_i) / sum_i(w_i), 0 when sum_i(w_i) == 0 -- the reference's
+ *                mean(l_i * w_i / mean(w)) * weight with div_no_nan; with neither weight input sum(w) is B exactly
+ *   d_grad       d l_i / d logits, times w_i, NOT divided by the normaliser, and
+ *   *d_scale     = task_weight / sum_i(w_i) (0 when the sum is 0): d(*d_loss)/d logits = d_grad * *d_scale, so that
+ *                the autograd backward is one multiply by (grad_out * scale) with no host read
+ * sum(w l) and sum(w) are two partial sums per workgroup, added in index order by a one-workgroup finishing launch: no
+ * float atomics, the same inputs give the same bits.  No host sync (capturable).  Errors are found before anything is
+ * launched and leave every output untouched: TZR_ERR_INVALID (null pointer, B <= 0, C < 2, unknown kind),
+ * TZR_ERR_UNSUPPORTED (label width; B >= 2^30 for the two row-structured entries), TZR_ERR_WORKSPACE (null, not 256-byte
+ * aligned, shorter than the matching *_workspace query). */
+#define TZR_LOSS_BCE 0   /* p0 = label_smoothing s: y' = y (1 - s) + 0.5 s;  l = max(x,0) - x y' + log1p(exp(-|x|)), dl = sigmoid(x) - y' */
+#define TZR_LOSS_FOCAL 1 /* p0 = gamma, p1 = alpha: f = alpha y (1-p)^gamma + (1-alpha)(1-y) p^gamma, p = sigmoid(x);  l = f * bce(x, y),
+                            dl = f (p - y): f is a constant of the gradient (the reference detaches it, tzrec/loss/focal_loss.py:64-72) */
+#define TZR_LOSS_L2 2    /* l = (x - y)^2, dl = 2 (x - y): nn.MSELoss on the prediction `y` */
+size_t tzr_loss_pointwise_workspace(int64_t B);
+int tzr_loss_pointwise(int kind, float p0, float p1, const float* d_logits, const void* d_labels, int labels_itemsize,
+                       int labels_are_float, const float* d_weight, const void* d_space_label, int space_itemsize,
+                       int space_is_float, float in_w, float out_w, float task_weight, int64_t B, float* d_loss,
+                       float* d_grad, float* d_scale, void* ws, size_t ws_bytes, void* stream);
+
+/* nn.CrossEntropyLoss(label_smoothing = eps) over d_logits [B, C] (row_stride floats between rows, unit column stride),
+ * int32 / int64 labels (float labels: TZR_ERR_UNSUPPORTED):  l = (1 - eps)(-log p_y) + (eps / C) sum_c(-log p_c),  d_grad [B, C] contiguous = w (p - ((1 - eps) onehot
+ * + eps / C)).  C <= 8: one lane per row, the row in registers; larger C: one wave per row, lanes stride over the classes.
+ * A label outside [0, C) is never used as an index: its row has l = 0 and a zero gradient row (its weight still counts in
+ * sum(w)) and *d_bad_labels (int64, the caller's to zero, may be null) goes up by one. */
+size_t tzr_softmax_ce_workspace(int64_t B, int C);
+int tzr_softmax_ce(const float* d_logits, int64_t row_stride, int C, const void* d_labels, int labels_itemsize,
+                   int labels_are_float, float eps, const float* d_weight, const void* d_space_label, int space_itemsize,
+                   int space_is_float, float in_w, float out_w, float task_weight, int64_t B, float* d_loss,
+                   float* d_grad, float* d_scale, int64_t* d_bad_labels, void* ws, size_t ws_bytes, void* stream);
+
+/* JRCLoss (tzrec/loss/jrc_loss.py, arXiv 2208.06164) grouped by session, O(B) memory instead of the reference's [B, B]
+ * masks.  d_logits [B, 2] contiguous, l0 = [:, 0], l1 = [:, 1]; a row is positive when its label == 1.  For session s:
+ * A_s = logsumexp of l1 over its negatives, B_s = logsumexp of l0 over its positives (-inf for an empty set).
+ *   l_i = alpha CE_i + (1 - alpha) ge_i,  ge_i = softplus(A_s - l1_i) for a positive row, softplus(B_s - l0_i) otherwise
+ * and the gradient of sum_i w_i l_i in closed form (q_i = sigmoid(A_s - l1_i), r_i = sigmoid(B_s - l0_i), P_s = sum over
+ * positives of w q, Q_s = sum over negatives of w r): a positive row gets -w q on l1 and Q_s exp(l0 - B_s) on l0, a
+ * negative row -w r on l0 and P_s exp(l1 - A_s) on l1.  The reference masks with -1e9 added in fp32, which excludes to
+ * the last bit of an fp32 exp; here the rows are excluded.  A batch without a positive (or without a negative) row makes
+ * the reference's mean form NaN (the mean of an empty tensor times 0); this entry returns the finite sum.
+ * d_session int64 [B]; d_order int64 [B] = a stable argsort of d_session (the caller's sort).  One wave per 64 sorted
+ * rows works through the session heads among them (neighbour compare; the end of the last one by binary search), three
+ * sweeps per session with the lanes striding over its rows: a session of any length is correct, every gradient element
+ * is written by exactly one lane.  Row losses go to a [B] buffer in ROW order and are summed by the fixed tree above: the
+ * loss bits do not depend on how sessions are scheduled. */
+size_t tzr_jrc_loss_workspace(int64_t B);
+int tzr_jrc_loss(const float* d_logits, const void* d_labels, int labels_itemsize, int labels_are_float,
+                 const int64_t* d_session, const int64_t* d_order, float alpha, const float* d_weight,
+                 const void* d_space_label, int space_itemsize, int space_is_float, float in_w, float out_w,
+                 float task_weight, int64_t B, float* d_loss, float* d_grad, float* d_scale, void* ws, size_t ws_bytes,
+                 void* stream);
+
 /* Backward of a Linear+ReLU layer up to the GEMMs: d_grad[b,n] = d_grad_y[b,n] * (d_y[b,n] > 0)
  * and d_colsum[n] = sum_b d_grad[b,n] (the bias gradient), one pass.  Replaces
  * threshold_backward + sum(0) in the autograd of tzrec/modules/mlp.py:37-177 (Perceptron =

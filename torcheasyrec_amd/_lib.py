@@ -234,6 +234,15 @@ _SIGNATURES = {
     "tzr_step_run": (_i32, [_vp, _vp]),
     "tzr_bce_logits_workspace": (_sz, [_i64]),
     "tzr_bce_logits": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tzr_loss_pointwise_workspace": (_sz, [_i64]),
+    "tzr_loss_pointwise": (_i32, [_i32, C.c_float, C.c_float, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, C.c_float, C.c_float,
+                                  C.c_float, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tzr_softmax_ce_workspace": (_sz, [_i64, _i32]),
+    "tzr_softmax_ce": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
+                              _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tzr_jrc_loss_workspace": (_sz, [_i64]),
+    "tzr_jrc_loss": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
+                            _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tzr_relu_bwd_colsum_workspace": (_sz, [_i64, _i32]),
     "tzr_relu_bwd_colsum": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tzr_relu_bwd_colsum_parts": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),

@@ -221,6 +221,87 @@ def _metric_specs(blocks, tower: Optional[str], label: Optional[str]) -> List[Me
     return out
 
 
+# the `loss` oneof of protos/loss.proto:4-11 with each member's defaults (loss.proto:44-63); jrc_loss's `session_name` is required
+LOSS_DEFAULTS = {
+    "binary_cross_entropy": {"label_smoothing": 0.0},
+    "softmax_cross_entropy": {"label_smoothing": 0.0},
+    "l2_loss": {},
+    "jrc_loss": {"alpha": 0.5},
+    "binary_focal_loss": {"gamma": 2.0, "alpha": 0.5},
+}
+SID_LOSS_KINDS = ("recon_loss", "commitment_loss", "contrastive_loss")  # the `sid_loss` oneof (loss.proto:15-19): not built
+
+
+@dataclass
+class LossSpec:
+    """One `losses { ... }` entry of the model config or of a task tower (protos/loss.proto:4-11, tzrec/models/rank_model.py:181-262,
+    multi_task_rank.py:80-142): the oneof's member and its fields as written, the proto's defaults filled in."""
+
+    kind: str
+    fields: dict = field(default_factory=dict)
+    tower: Optional[str] = None  # a task tower's loss: its tower_name
+
+    @property
+    def suffix(self) -> str:
+        return f"_{self.tower}" if self.tower else ""
+
+    @property
+    def name(self) -> str:  # the key of the reference's loss dict
+        return self.kind + self.suffix
+
+
+@dataclass
+class TowerSpec:
+    """What the losses read of a `task_towers` entry (protos/tower.proto:26-57), the proto's defaults filled in."""
+
+    tower_name: str
+    label_name: str
+    num_class: int = 1
+    weight: float = 1.0
+    sample_weight_name: Optional[str] = None
+    task_space_indicator_label: Optional[str] = None
+    in_task_space_weight: float = 1.0
+    out_task_space_weight: float = 1.0
+
+    @property
+    def has_weight(self) -> bool:  # MultiTaskRank.has_weight (multi_task_rank.py:67-78); a written `weight: 1.0` multiplies by one
+        return bool(self.sample_weight_name) or self.weight != 1.0 or bool(self.task_space_indicator_label)
+
+
+def _loss_specs(blocks, tower: Optional[str], num_class: int, sparse_names) -> List[LossSpec]:
+    """The entries of `losses` blocks, refused or validated here, when the spec is built; no block: one plain BCE (what every
+    model computed before the block was read)."""
+    where = f"task tower {tower}" if tower else "model_config"
+    out = []
+    for m in blocks:
+        for kind, body in m.items():
+            if kind not in LOSS_DEFAULTS:
+                raise NotImplementedError(f"{where}: loss {kind!r} is not built (built: {', '.join(LOSS_DEFAULTS)})")
+            given = {k: v[-1] for k, v in body[-1].items()} if isinstance(body[-1], Msg) else {}
+            out.append(LossSpec(kind=str(kind), fields={**LOSS_DEFAULTS[kind], **given}, tower=tower))
+    if not out:
+        out.append(LossSpec(kind="binary_cross_entropy", fields=dict(LOSS_DEFAULTS["binary_cross_entropy"]), tower=tower))
+    for ls in out:
+        kind, f = ls.kind, ls.fields
+        if kind in ("binary_cross_entropy", "binary_focal_loss") and num_class != 1:
+            raise ValueError(f"{where}: num_class must be 1 when loss type is {kind} (got {num_class})")
+        if kind == "softmax_cross_entropy" and num_class <= 1:
+            raise ValueError(f"{where}: num_class must be greater than 1 when loss type is {kind} (got {num_class})")
+        if kind == "jrc_loss":
+            if num_class != 2:
+                raise ValueError(f"{where}: num_class must be 2 when loss type is {kind} (got {num_class})")
+            if not f.get("session_name"):
+                raise ValueError(f"{where}: jrc_loss needs a session_name")
+            if str(f["session_name"]) not in sparse_names:
+                raise ValueError(f"{where}: jrc_loss session_name {f['session_name']!r} is not a sparse feature of the config")
+        if kind == "binary_focal_loss":
+            if not float(f["gamma"]) >= 0:
+                raise ValueError(f"{where}: binary_focal_loss gamma should be greater than or equal to zero (got {f['gamma']})")
+            if not 0 < float(f["alpha"]) < 1:
+                raise ValueError(f"{where}: binary_focal_loss alpha should be in (0, 1) (got {f['alpha']})")
+    return out
+
+
 @dataclass
 class PipelineSpec:
     features: List[FeatureSpec] = field(default_factory=list)
@@ -245,6 +326,13 @@ class PipelineSpec:
     grad_clipping: Optional[object] = None  # train.proto:153 -> optimizer.GradClippingConfig
     # model_config.metrics, then every task tower's metrics in tower order (metrics.Evaluator builds them)
     metrics: List[MetricSpec] = field(default_factory=list)
+    # model_config.losses (a model without task towers), then every task tower's losses in tower order (losses.build_losses)
+    losses: List[LossSpec] = field(default_factory=list)
+    task_towers: List[TowerSpec] = field(default_factory=list)
+    sample_weight_fields: List[str] = field(default_factory=list)  # data_config.sample_weight_fields
+
+    def tower(self, name: Optional[str]) -> Optional[TowerSpec]:
+        return next((t for t in self.task_towers if t.tower_name == name), None)
 
 
 def _num_embeddings(f: Msg, name: str) -> int:
@@ -467,4 +555,17 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
     spec.metrics = _metric_specs(mc.many("metrics"), None, spec.label_fields[0] if spec.label_fields else "label")
     for t in (spec.model.many("task_towers") if spec.model else []):
         spec.metrics += _metric_specs(t.many("metrics"), str(t.one("tower_name")), str(t.one("label_name")))
+    spec.sample_weight_fields = [str(x) for x in dc.many("sample_weight_fields")]
+    sparse_names = {f.name for f in spec.features if f.is_sparse}
+    towers = spec.model.many("task_towers") if spec.model else []
+    if mc.has("losses") or not towers:  # (a multi-task model reads its towers' blocks only, multi_task_rank.py:80-95)
+        spec.losses = _loss_specs(mc.many("losses"), None, spec.num_class, sparse_names)
+    for t in towers:
+        ts = TowerSpec(tower_name=str(t.one("tower_name")), label_name=str(t.one("label_name")), num_class=int(t.one("num_class", 1)),
+                       weight=float(t.one("weight", 1.0)), sample_weight_name=t.one("sample_weight_name"),
+                       task_space_indicator_label=t.one("task_space_indicator_label"),
+                       in_task_space_weight=float(t.one("in_task_space_weight", 1.0)),
+                       out_task_space_weight=float(t.one("out_task_space_weight", 1.0)))
+        spec.task_towers.append(ts)
+        spec.losses += _loss_specs(t.many("losses"), ts.tower_name, ts.num_class, sparse_names)
     return spec

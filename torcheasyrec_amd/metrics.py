@@ -257,10 +257,16 @@ class Evaluator:
         self._towers: Dict[str, List[str]] = {}
         for name, ms in self._specs.items():
             self._towers.setdefault(ms.suffix, []).append(name)
+        # a two-class softmax output: `auc` / `grouped_auc` read the positive class's column (rank_model.py:392-416)
+        self._probs_key: Dict[str, str] = {}
+        for suffix in self._towers:
+            t = spec.tower(suffix[1:]) if suffix and hasattr(spec, "tower") else None
+            num_class = t.num_class if t is not None else int(getattr(spec, "num_class", 1))
+            self._probs_key[suffix] = ("probs1" if num_class == 2 else "probs") + suffix
 
     def update(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> None:
         for suffix, names in self._towers.items():
-            probs = predictions["probs" + suffix]
+            probs = predictions[self._probs_key[suffix]]
             by_kind = {self._specs[n].kind: n for n in names}
             label = batch.labels[self._specs[names[0]].label]
             if "auc" in by_kind or "normalized_entropy" in by_kind:

@@ -4,7 +4,8 @@
 and builds the model the reference would build from the same file
 (/root/reference/tzrec/main.py:134-166 picks the class from the model_config oneof;
 /root/reference/tzrec/models/dlrm.py:26-135, deepfm.py:26-108, rank_model.py:83-262).
-`forward(batch) -> {"logits", "probs"}`; `loss(predictions, batch) -> {"binary_cross_entropy": ...}`.
+`forward(batch) -> {"logits", "probs"}`; `loss(predictions, batch) -> {"binary_cross_entropy": ...}`: one entry per
+`losses { ... }` block of the config, keyed kind + tower suffix, each a fused call of losses.py (csrc/loss_ops.hip).
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from .dlrm import MLP, OutputLinear, _on_emulator
 from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
 from .interaction import FactorizationMachine, dot_interaction
+from .losses import build_losses, output_to_prediction
 
 
 def mlp_kwargs(msg) -> Dict[str, object]:
@@ -46,6 +48,8 @@ class RankModel(nn.Module):
         self._spec = spec
         self._label = spec.label_fields[0] if spec.label_fields else "label"
         self._pg = RankModel._build_pg
+        self._losses = build_losses(spec)  # (refusals and validation happened when the spec was built)
+        self._model_losses = [l for l in self._losses if l.tower is None]
         self.embedding_group = EmbeddingGroup(
             spec.features, spec.feature_groups, wide_embedding_dim=spec.wide_embedding_dim or None,
             device=device, sparse_optimizer=sparse_optimizer if sparse_optimizer is not None else spec.sparse_optimizer,
@@ -86,12 +90,17 @@ class RankModel(nn.Module):
         return self.embedding_group.fused_optimizer
 
     def _output_to_prediction(self, y: torch.Tensor) -> Dict[str, torch.Tensor]:
-        logits = torch.squeeze(y, dim=1)  # rank_model.py:142-146 (num_class == 1)
-        return {"logits": logits, "probs": torch.sigmoid(logits)}
+        return output_to_prediction(y, [l.spec for l in self._model_losses], self._spec.num_class)  # rank_model.py:133-179
 
     def loss(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
-        label = batch.labels[self._label].to(torch.float32)
-        return {"binary_cross_entropy": nn.functional.binary_cross_entropy_with_logits(predictions["logits"], label)}
+        out = {}
+        for l in self._model_losses:
+            if l.plain_bce:  # mean BCE and nothing else: torch's, as before the `losses` block was read
+                label = batch.labels[self._label].to(torch.float32)
+                out[l.name] = nn.functional.binary_cross_entropy_with_logits(predictions["logits"], label)
+            else:
+                out[l.name] = l(predictions, batch)
+        return out
 
 
 class ConfigDLRM(RankModel):
@@ -275,16 +284,15 @@ class ConfigMMoE(RankModel):
         self.mmoe = MMoE(d_in, expert, int(m.one("num_expert")), len(self._towers), gate)
         self.task_mlps = nn.ModuleList()
         self.task_outputs = nn.ModuleList()
+        self._tower_losses = [[l for l in self._losses if l.tower is not None and l.tower.tower_name == name] for name, _ in self._towers]
         for t in m.many("task_towers"):
-            if int(t.one("num_class", 1)) != 1:
-                raise NotImplementedError("task towers with num_class > 1")
             d = hidden[-1]
             if t.has("mlp"):
                 self.task_mlps.append(mlp_from_msg(d, t.one("mlp")))
                 d = self.task_mlps[-1].output_dim()
             else:
                 self.task_mlps.append(nn.Identity())
-            self.task_outputs.append(OutputLinear(d, 1))
+            self.task_outputs.append(OutputLinear(d, int(t.one("num_class", 1))))
         if device is not None:
             for mod in (self.mmoe, self.task_mlps, self.task_outputs):
                 mod.to(device)
@@ -293,15 +301,21 @@ class ConfigMMoE(RankModel):
         task_inputs = self.mmoe(self.build_input(batch)[self._group])
         out: Dict[str, torch.Tensor] = {}
         for i, (tower, _) in enumerate(self._towers):
-            logits = self.task_outputs[i](self.task_mlps[i](task_inputs[i])).squeeze(1)
-            out[f"logits_{tower}"], out[f"probs_{tower}"] = logits, torch.sigmoid(logits)
+            y = self.task_outputs[i](self.task_mlps[i](task_inputs[i]))
+            out.update(output_to_prediction(y, [l.spec for l in self._tower_losses[i]], self.task_outputs[i].out_features, f"_{tower}"))
         return out
 
     def loss(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
         from .dlrm import bce_with_logits
 
-        return {f"binary_cross_entropy_{tower}": bce_with_logits(predictions[f"logits_{tower}"], batch.labels[label])
-                for tower, label in self._towers}
+        out = {}
+        for (tower, label), losses in zip(self._towers, self._tower_losses):
+            for l in losses:
+                if l.plain_bce:  # (tzr_bce_logits: the launches of before)
+                    out[l.name] = bce_with_logits(predictions[f"logits_{tower}"], batch.labels[label])
+                else:
+                    out[l.name] = l(predictions, batch)
+        return out
 
 
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE}
