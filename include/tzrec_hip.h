@@ -924,6 +924,27 @@ int tzr_jagged_pool_fwd(const float* d_kv, int64_t kv_stride, int D, const int64
 int tzr_jagged_pool_bwd(const float* d_grad_out, int64_t grad_out_stride, int D, const int64_t* d_offsets, int64_t B,
                         int64_t N, int64_t max_len, int mode, float* d_dkv, int64_t dkv_stride, void* stream);
 
+/* The cross network of Deep & Cross v1, all L layers in one launch per direction: replaces Cross.forward and its autograd
+ * (tzrec/modules/interaction.py:94-132).  csrc/cross_net.hip.
+ *   tzr_cross_fwd  x_0 = x; s_l = x_l . w_l; x_{l+1} = s_l x_0 + b_l + x_l; d_y = x_L; d_s [B, L] contiguous (nullable: inference)
+ *                  takes the scalars s for the backward.  One launch.
+ *   tzr_cross_bwd  from g = d(loss)/d(y), x and s: d_dx [B, D], d_dw [L, D] and d_db [L, D] (contiguous; row l is the finished
+ *                  gradient of w_l / b_l).  No x_l is read or stored: x_l = (1 + s_0 + .. + s_{l-1}) x + b_0 + .. + b_{l-1}.
+ *                  Two launches: the pass over the batch, which leaves one row of partial sums per workgroup in `ws`
+ *                  (tzr_cross_bwd_workspace(B, D, L) bytes, 256-byte aligned), and their sum in a fixed order.
+ * h_w / h_b: HOST arrays of L device pointers (the reference's L separate [1, D] weights and [D] biases), read by the call and
+ * passed to the kernels by value.  fp32; any D in [1, 1024], L in [1, 8], row strides (in floats) >= D; rows and parameters
+ * need 4-byte alignment only.  TZR_ERR_INVALID: a null pointer (a misaligned workspace), B < 0, D <= 0, L <= 0;
+ * TZR_ERR_UNSUPPORTED: D > 1024, L > 8, a stride below D, a workspace shorter than the query; B == 0 is TZR_OK without a
+ * launch.  One wave per sample, no atomics, every sum over the batch in an order fixed by (B, D, L): bit-reproducible.
+ * Entry points only, no struct or constant changes: the ABI version stays 15. */
+int tzr_cross_fwd(const float* d_x, int64_t x_stride, const float* const* h_w, const float* const* h_b, int L, int64_t B, int D,
+                  float* d_y, int64_t y_stride, float* d_s, void* stream);
+size_t tzr_cross_bwd_workspace(int64_t B, int D, int L);
+int tzr_cross_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, int64_t x_stride, const float* d_s,
+                  const float* const* h_w, const float* const* h_b, int L, int64_t B, int D, float* d_dx, int64_t dx_stride,
+                  float* d_dw, float* d_db, void* ws, size_t ws_size, void* stream);
+
 /* ---- native step driver (csrc/step_driver.hip) ------------------------------------------------------------------
  * Replaces the host side of a steady-state train step of tzrec's pipeline (tzrec/utils/dist_util.py:221-303: Python +
  * torch.distributed calls per collective) for a sharded step that was cut into captured hipGraphs: ONE call queues the

@@ -5,9 +5,12 @@
 ``dot_interaction`` is the fused form DLRM uses here: it reads the dense-MLP output and the pooled
 sparse block separately (no ``cat`` to build [B, 27, 16]) and writes
 ``[interactions | dense | sparse]`` in one pass (/root/reference/tzrec/models/dlrm.py:123-130).
+``Cross`` is the cross network of Deep & Cross v1 with the reference's parameters (interaction.py:94-132), every layer
+of it in one launch per direction (csrc/cross_net.hip).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
@@ -119,3 +122,94 @@ class FactorizationMachine(nn.Module):
         if _traced(feature):
             return torch.ops.tzrec_hip.fm_fwd(feature)
         return _FMFn.apply(feature)
+
+
+FUSED_CROSS = True  # A/B switch: False = the reference's literal loop (a product, a multiply and two adds per layer)
+CROSS_MAX_DIM, CROSS_MAX_LAYERS = 1024, 8  # CN_MAXDIM, CN_MAXL of csrc/cross_net.hip
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    """floats between the rows of a [B, D] tensor with unit column stride (the stride of a single row says nothing)"""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """`t` when its rows are whole and apart (a column slice of a wider tensor is), else a copy (an expanded gradient)"""
+    return t if t.stride(1) == 1 and _row_stride(t) >= t.shape[1] else t.contiguous()
+
+
+def _pointer_array(tensors):
+    return (C.c_void_p * len(tensors))(*[_lib.ptr(t) for t in tensors])
+
+
+class _CrossFn(torch.autograd.Function):
+    """y = x_L of x_{l+1} = (x_l . w_l) x_0 + b_l + x_l: tzr_cross_fwd keeps the scalars x_l . w_l ([B, L]), tzr_cross_bwd
+    returns the input gradient and the finished gradients of every w_l and b_l (rows of one [2, L, D] buffer)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, L: int, *params: torch.Tensor):
+        x = _rows(x)
+        B, D = x.shape
+        params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
+        y = torch.empty(B, D, dtype=torch.float32, device=x.device)
+        s = torch.empty(B, L, dtype=torch.float32, device=x.device)
+        rc = _lib.lib().tzr_cross_fwd(_lib.ptr(x), _row_stride(x), _pointer_array(params[:L]), _pointer_array(params[L:]), L, B, D,
+                                      _lib.ptr(y), D, _lib.ptr(s), _lib.stream_ptr(x.device))
+        _lib.check(rc, "tzr_cross_fwd")
+        ctx.save_for_backward(x, s, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        x, s, *params = ctx.saved_tensors
+        B, D = x.shape
+        L = len(params) // 2
+        gy = _rows(gy)
+        dx = torch.empty(B, D, dtype=torch.float32, device=x.device)
+        dwb = torch.empty(2, L, D, dtype=torch.float32, device=x.device)
+        lib = _lib.lib()
+        ws = _lib.workspace(lib.tzr_cross_bwd_workspace(B, D, L), x.device)
+        rc = lib.tzr_cross_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(s), _pointer_array(params[:L]),
+                               _pointer_array(params[L:]), L, B, D, _lib.ptr(dx), D, _lib.ptr(dwb[0]), _lib.ptr(dwb[1]), _lib.ptr(ws),
+                               ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "tzr_cross_bwd")
+        return (dx, None, *[dwb[0, l].view(1, D) for l in range(L)], *[dwb[1, l] for l in range(L)])
+
+
+class Cross(nn.Module):
+    """Cross layers of the Deep & Cross network (https://arxiv.org/pdf/1708.05123), the reference module's constructor,
+    parameters and forward (tzrec/modules/interaction.py:94-132): `w.<i>.weight` [1, input_dim], `b.<i>` [input_dim]."""
+
+    def __init__(self, input_dim: int, cross_num: int = 3) -> None:
+        super().__init__()
+        self.cross_num = cross_num
+        self._input_dim = input_dim
+        self.w = nn.ModuleList()
+        self.b = nn.ParameterList()
+        for _ in range(cross_num):
+            self.w.append(nn.Linear(input_dim, 1, bias=False))
+            self.b.append(nn.Parameter(torch.empty(input_dim)))
+        self.reset_parameters()
+
+    def output_dim(self) -> int:
+        return self._input_dim
+
+    def reset_parameters(self) -> None:
+        for i in range(self.cross_num):
+            nn.init.xavier_uniform_(self.w[i].weight)
+            nn.init.zeros_(self.b[i])
+
+    def _fused_ok(self, x: torch.Tensor) -> bool:
+        from .dlrm import _on_emulator
+
+        return bool(FUSED_CROSS and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
+                    and 1 <= self.cross_num <= CROSS_MAX_LAYERS and 1 <= x.shape[1] <= CROSS_MAX_DIM
+                    and self.w[0].weight.dtype == torch.float32 and (x.is_cuda or _on_emulator()))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._fused_ok(x):
+            return _CrossFn.apply(x, self.cross_num, *[m.weight for m in self.w], *self.b)
+        x1 = x
+        for i in range(self.cross_num):  # the reference's literal form
+            x1 = self.w[i](x1) * x + self.b[i] + x1
+        return x1

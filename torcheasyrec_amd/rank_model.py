@@ -18,7 +18,7 @@ from .config import PipelineSpec
 from .dlrm import MLP, OutputLinear, _on_emulator
 from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
-from .interaction import FactorizationMachine, dot_interaction
+from .interaction import Cross, FactorizationMachine, dot_interaction
 from .losses import build_losses, output_to_prediction
 
 
@@ -318,7 +318,34 @@ class ConfigMMoE(RankModel):
         return out
 
 
-_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE}
+class ConfigDCNV1(RankModel):
+    """`dcn_v1 {...}` (tzrec/models/dcn.py:36-73): the cross network and a deep MLP over the (single) feature group, a final MLP
+    over [cross | deep], a logits layer without bias.  `cross { cross_num }` (protos/module.proto:82-85) defaults to 3 layers."""
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        self._group = eg.group_names()[0]
+        d_in = eg.group_total_dim(self._group)
+        cross = m.one("cross") if m.has("cross") else {}
+        other = sorted(k for k in cross if k != "cross_num")
+        if other:
+            raise ValueError(f"dcn_v1: cross has no field {other[0]!r} (fields: cross_num)")
+        self.cross = Cross(d_in, cross_num=int(cross.one("cross_num", 3)) if cross else 3)
+        self.deep = mlp_from_msg(d_in, m.one("deep"))
+        self.final_dnn = mlp_from_msg(self.cross.output_dim() + self.deep.output_dim(), m.one("final"))
+        self.output_linear = OutputLinear(self.final_dnn.output_dim(), spec.num_class, bias=False)
+        if device is not None:
+            for mod in (self.cross, self.deep, self.final_dnn, self.output_linear):
+                mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        features = self.build_input(batch)[self._group]
+        y = torch.cat([self.cross(features), self.deep(features)], dim=-1)
+        return self._output_to_prediction(self.output_linear(self.final_dnn(y)))
+
+
+_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
