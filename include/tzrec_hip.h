@@ -678,6 +678,16 @@ typedef struct TzrWgradParts { uint64_t opaque[24]; } TzrWgradParts; /* filled b
 int tzr_dense_adam_fused(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
                          const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
                          float weight_decay, void* stream);
+/* ... and, when one of the tensors is the W1 [64, 783] of the fused interaction layer (contiguous: ldw = 783), its packed copies
+ * (tzr_ia_top_pack_w1) written by the thread that updates each element: plain stores in the same launch.  h_w1 null, or
+ * h_w1->param not among the tensors: exactly tzr_dense_adam_fused.  Either copy may be 0. */
+typedef struct TzrPackedW1 {
+  uint64_t param;                  /* the parameter tensor the copies belong to (matched against TzrAdamTensor.param) */
+  uint64_t fwd_packed, bwd_packed; /* float[tzr_ia_top_packed_floats()] each */
+} TzrPackedW1; /* 24 bytes */
+int tzr_dense_adam_fused_w1(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
+                            const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, const TzrPackedW1* h_w1, void* stream);
 /* The dense optimizer step of every kind `train_config.dense_optimizer` and its `part_optimizers` can name
  * (tzrec/optim/optimizer_builder.py:100-260 -> torch.optim.SGD / Adagrad / Adam / AdamW / Adadelta / RMSprop), over every
  * dense tensor of the step in ONE launch per TZR_ADAM_MAX_TENSORS tensors, whatever mix of kinds (csrc/dense_optim_fused.hip).
@@ -1107,6 +1117,26 @@ int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_stride, cons
                                 int H, const float* d_W1, int64_t ldw, const float* d_scale, float* d_grad_dense,
                                 int64_t grad_dense_stride, float* d_grad_sparse, int64_t grad_sparse_stride,
                                 void* stream);
+/* W1 in the order of the two kernels' MFMA fragments (csrc/interaction_pack.h), for the DLRM-Criteo shape (n = 27 vectors with
+ * the dense one, D = 16, H = 64).  Out of the plain matrix every persistent workgroup re-orders the 200 KB through LDS before its
+ * first tile; out of a packed copy its lanes load their registers directly.  Same numbers in the same registers: results are
+ * bit-identical to the plain entry points.
+ *   tzr_ia_top_packed_floats: floats of either copy (16-byte aligned buffers).
+ *   tzr_ia_top_pack_w1: both copies (either pointer may be null) of W1 [64, ldw]; n != 27: TZR_ERR_UNSUPPORTED.
+ *   _top_fwd_packed / _top_bwd_packed: the plain entry points with the matching copy; null, d_z != null (forward) or another
+ *   shape: the copy is not read and W1 is staged as ever.  `scale` stays a multiply in the backward kernel.
+ * The copies are the caller's to keep equal to W1: tzr_dense_adam_fused_w1 writes them in the optimizer's launch. */
+int tzr_ia_top_packed_floats(void);
+int tzr_ia_top_pack_w1(const float* d_W1, int64_t ldw, int n, float* d_fwd_packed, float* d_bwd_packed, void* stream);
+int tzr_dot_interaction_top_fwd_packed(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                       int64_t sparse_stride, int F, int D, int64_t B, const float* d_W1, int64_t ldw,
+                                       const float* d_bias, int H, int relu, float* d_z, int64_t z_stride, float* d_y1,
+                                       int64_t y1_stride, const float* d_W1_fwd_packed, void* stream);
+int tzr_dot_interaction_top_bwd_packed(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                       int64_t sparse_stride, int F, int D, int64_t B, const float* d_g1, int64_t g1_stride,
+                                       int H, const float* d_W1, int64_t ldw, const float* d_scale, float* d_grad_dense,
+                                       int64_t grad_dense_stride, float* d_grad_sparse, int64_t grad_sparse_stride,
+                                       const float* d_W1_bwd_packed, void* stream);
 
 /* K9c: the weight gradient of that first Linear, dW1 = scale * g1^T z [H, P + D n] (autograd of nn.Linear in
  * tzrec/modules/mlp.py:58-83 behind tzrec/models/dlrm.py:123-135), with the interaction rows z REBUILT from the

@@ -119,14 +119,23 @@ def prof():
     _lib.use_library(path)
     L = _lib.lib()
     dev = torch.device("cuda", 0)
-    D, F, H, B = 16, 26, 64, 65536
+    D, F, H = 16, 26, 64
     width = 27 * 26 // 2 + D * 27
     st = _lib.stream_ptr(dev)
+    for B in [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "65536").split(",")]:
+        prof_at(L, dev, st, D, F, H, B, width)
+
+
+def prof_at(L, dev, st, D, F, H, B, width):
+    import ctypes
+
+    import numpy as np
+
     dense, sparse = torch.randn(B, D, device=dev), torch.randn(B, F * D, device=dev)
     W1, b1, g1 = torch.randn(H, width, device=dev) * 0.05, torch.randn(H, device=dev), torch.randn(B, H, device=dev)
     z, y1 = torch.empty(B, width, device=dev), torch.empty(B, H, device=dev)
     gd, gs = torch.empty_like(dense), torch.empty_like(sparse)
-    tab = torch.zeros(256 * 16 * 6, dtype=torch.int64, device=dev)
+    tab = torch.zeros(256 * 16 * (6 + 2), dtype=torch.int64, device=dev)  # tile-loop phases, then [W1 prologue, entry to exit]
     L.tzr_it_prof_table(ctypes.c_void_p(tab.data_ptr()))
     ws = _lib.workspace(L.tzr_dot_interaction_top_wgrad_workspace(F, D, 1, H), dev)
     dW = torch.empty(H, width, device=dev)
@@ -149,9 +158,16 @@ def prof():
                 L.tzr_dot_interaction_top_fwd(_lib.ptr(dense), D, _lib.ptr(sparse), F * D, F, D, B, _lib.ptr(W1), width, _lib.ptr(b1), H, 1,
                                               _lib.ptr(z) if kind == "fwd+z" else None, width, _lib.ptr(y1), H, st)
             torch.cuda.synchronize()
-        per_wg = 32.0 if kind == "wgrad" else 16.0  # tiles per workgroup
-        t = tab.cpu().numpy().reshape(256, 16, 6).astype(np.float64) / per_wg
-        print(f"{kind}: shader clocks per tile, mean over workgroups; per wave (rows) x phase (cols) {names[kind]}")
+        per_wg = B / 256.0 / (8.0 if kind == "wgrad" else 16.0)  # tiles per workgroup
+        raw = tab.cpu().numpy().astype(np.float64)
+        t = raw[:256 * 16 * 6].reshape(256, 16, 6) / per_wg
+        if kind != "wgrad":  # (the fused forward / backward: what a workgroup spends on W1 before its first tile)
+            pro = raw[256 * 16 * 6:].reshape(256, 16, 2)
+            wg = pro.max(axis=1)  # a workgroup is as late as its last wave
+            print(f"{kind} B {B}: W1 prologue, shader clocks per workgroup (its slowest wave): mean {wg[:, 0].mean():.0f} min {wg[:, 0].min():.0f} "
+                  f"max {wg[:, 0].max():.0f}; entry to exit: mean {wg[:, 1].mean():.0f} min {wg[:, 1].min():.0f} max {wg[:, 1].max():.0f}; "
+                  f"share {wg[:, 0].mean() / wg[:, 1].mean():.3f}")
+        print(f"{kind} B {B}: shader clocks per tile, mean over workgroups; per wave (rows) x phase (cols) {names[kind]}")
         if kind == "wgrad":  # by column group (workgroup b: group (b >> 3) & 3)
             for gidx in range(4):
                 sel = [b for b in range(256) if ((b >> 3) & 3) == gidx]

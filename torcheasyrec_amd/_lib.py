@@ -97,6 +97,10 @@ class TzrWgradParts(C.Structure):
     _fields_ = [("opaque", C.c_uint64 * 24)]
 
 
+class TzrPackedW1(C.Structure):
+    _fields_ = [("param", C.c_uint64), ("fwd_packed", C.c_uint64), ("bwd_packed", C.c_uint64)]
+
+
 ADAM_SRC_TENSOR, ADAM_SRC_ROWS, ADAM_SRC_WGRAD = 0, 1, 2
 
 
@@ -182,6 +186,8 @@ _SIGNATURES = {
                                           C.POINTER(TzrSparseOptim), _vp, _vp, _vp, _sz, _vp]),
     "tzr_dense_adam_fused": (_i32, [C.POINTER(TzrAdamTensor), C.POINTER(TzrAdamSource), _i32, C.POINTER(TzrWgradParts), _vp, C.c_float,
                                     C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "tzr_dense_adam_fused_w1": (_i32, [C.POINTER(TzrAdamTensor), C.POINTER(TzrAdamSource), _i32, C.POINTER(TzrWgradParts), _vp, C.c_float,
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(TzrPackedW1), _vp]),
     "tzr_dense_optim_fused": (_i32, [C.POINTER(TzrDenseOptTensor), C.POINTER(TzrAdamSource), _i32, C.POINTER(TzrDenseOptGroup), _i32,
                                      C.POINTER(TzrWgradParts), _vp]),
     "tzr_mlp2_bwd_parts": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _sz, C.POINTER(C.c_int),
@@ -197,6 +203,12 @@ _SIGNATURES = {
                                            _vp, _i64, _vp]),
     "tzr_dot_interaction_top_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
                                            _i64, _vp, _i64, _vp]),
+    "tzr_ia_top_packed_floats": (_i32, []),
+    "tzr_ia_top_pack_w1": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "tzr_dot_interaction_top_fwd_packed": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64,
+                                                  _vp, _i64, _vp, _vp]),
+    "tzr_dot_interaction_top_bwd_packed": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
+                                                  _i64, _vp, _i64, _vp, _vp]),
     "tzr_dot_interaction_top_wgrad_workspace": (_i64, [_i32, _i32, _i32, _i32]),
     "tzr_dot_interaction_top_wgrad": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp,
                                              _i64, _vp]),

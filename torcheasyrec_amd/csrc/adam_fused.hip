@@ -12,6 +12,7 @@
 // differ from it by fp32 rounding); the step counter of a tensor is read by every workgroup and moved on by the LAST of the
 // tensor's workgroups to finish.
 #include "fused_grad.h"
+#include "interaction_pack.h"
 
 namespace {
 
@@ -20,10 +21,16 @@ struct FusedTable {
   FusedPlan p;
 };
 
+// the tensor of the launch (-1: none) that is the fused interaction layer's W1 [64][783], and its copies in fragment order
+struct PackedW1 {
+  float *fwd, *bwd;
+  int tensor;
+};
+
 }  // namespace
 
-__global__ __launch_bounds__(256) void tzr_adam_fused_kernel(FusedTable T, const float* __restrict__ lr_ptr, float lr_host, float b1,
-                                                             float b2, float eps, float wd) {
+__global__ __launch_bounds__(256) void tzr_adam_fused_kernel(FusedTable T, PackedW1 W, const float* __restrict__ lr_ptr, float lr_host,
+                                                             float b1, float b2, float eps, float wd) {
   __shared__ float sl[16][17];
   int y = 0;
   while (y + 1 < T.p.n && (int)blockIdx.x >= T.p.first[y + 1]) ++y;  // (workgroup-uniform, <= 32 steps through kernel arguments)
@@ -47,33 +54,55 @@ __global__ __launch_bounds__(256) void tzr_adam_fused_kernel(FusedTable T, const
   fused_grad_each(T.p.s[y], T.p.wg, gout, a.numel, lb, nblk, sl, [&](int64_t i, float gi) {
     if (!p) gout[i] = gi;
     else adam_update(p, m, v, k, i, p[i], gi);
+    if (y == W.tensor) {  // (workgroup-uniform) the new value into W1's packed copies too: the interaction kernels read those
+      const int h = (int)(i / IT_PACK_WIDTH), col = (int)(i - (int64_t)h * IT_PACK_WIDTH);
+      int pf, pb;
+      it_pack_pos(h, it_pack_vcol(col), &pf, &pb);
+      const float w = p[i];
+      if (W.fwd) W.fwd[pf] = w;
+      if (W.bwd) W.bwd[pb] = w;
+    }
   });
   if (a.param) fused_step_arrive(state, lb, nblk, step);
 }
 
 // h_sources (nullable: every gradient is a finished tensor) runs parallel to h_tensors; at most one source of kind
 // TZR_ADAM_SRC_WGRAD, described by h_wgrad.  A tensor with param == 0 only gets its finished gradient stored into `grad`.
-extern "C" int tzr_dense_adam_fused(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
-                                    const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, void* stream) {
+extern "C" int tzr_dense_adam_fused_w1(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
+                                       const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
+                                       float weight_decay, const TzrPackedW1* h_w1, void* stream) {
   if (!h_tensors || n_tensors <= 0) return TZR_ERR_INVALID;
+  if (h_w1 && ((h_w1->fwd_packed | h_w1->bwd_packed) & 15)) return TZR_ERR_INVALID;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int base = 0; base < n_tensors; base += TZR_ADAM_MAX_TENSORS) {
     FusedTable T;
     T.p.n = std::min(TZR_ADAM_MAX_TENSORS, n_tensors - base);
     std::memset(&T.p.wg, 0, sizeof(T.p.wg));
+    PackedW1 W = {nullptr, nullptr, -1};
     int blocks = 0;
     for (int i = 0; i < T.p.n; ++i) {
       const TzrAdamTensor& a = h_tensors[base + i];
       T.t[i] = a;
+      if (h_w1 && h_w1->param && a.param == h_w1->param) {
+        if (a.numel != (int64_t)IT_PACK_H * IT_PACK_WIDTH) return TZR_ERR_INVALID;
+        W.fwd = reinterpret_cast<float*>(h_w1->fwd_packed);
+        W.bwd = reinterpret_cast<float*>(h_w1->bwd_packed);
+        W.tensor = i;
+      }
       if (a.param && (!a.exp_avg || !a.exp_avg_sq || !a.state)) return TZR_ERR_INVALID;
       const int rc = fused_plan_tensor(T.p, i, a.numel, a.param != 0, a.grad != 0, h_sources ? &h_sources[base + i] : nullptr, h_wgrad, &blocks);
       if (rc != TZR_OK) return rc;
     }
     T.p.first[T.p.n] = blocks;
     if (blocks == 0) continue;
-    hipLaunchKernelGGL(tzr_adam_fused_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T, d_lr, lr, beta1, beta2, eps, weight_decay);
+    hipLaunchKernelGGL(tzr_adam_fused_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T, W, d_lr, lr, beta1, beta2, eps, weight_decay);
   }
   TZR_CHECK_LAUNCH();
   return TZR_OK;
+}
+
+extern "C" int tzr_dense_adam_fused(const TzrAdamTensor* h_tensors, const TzrAdamSource* h_sources, int n_tensors,
+                                    const TzrWgradParts* h_wgrad, const float* d_lr, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, void* stream) {
+  return tzr_dense_adam_fused_w1(h_tensors, h_sources, n_tensors, h_wgrad, d_lr, lr, beta1, beta2, eps, weight_decay, nullptr, stream);
 }

@@ -19,6 +19,7 @@
 // by the MFMAs of the other three (an 8-wave version with twice the work per wave ran at half the MFMA rate, and
 // interleaving the instruction streams by hand inside a wave did not help).
 #include "tzr_common.h"
+#include "interaction_pack.h"
 #include <type_traits>
 #include <tzr_gfx950.h>
 
@@ -47,7 +48,16 @@ typedef float it_f32x4 __attribute__((ext_vector_type(4)));
 #ifdef IT_PROF
 #define IT_PROF_DECL uint64_t it_tl = __builtin_amdgcn_s_memtime(), it_ts[6] = {0, 0, 0, 0, 0, 0}
 #define IT_PROF_MARK(i) do { const uint64_t it_now = __builtin_amdgcn_s_memtime(); it_ts[i] += it_now - it_tl; it_tl = it_now; } while (0)
-#define IT_PROF_DUMP(tab) do { if (tab && lane == 0) for (int i_ = 0; i_ < 6; ++i_) (tab)[((size_t)blockIdx.x * IT_WAVES + wv) * 6 + i_] = it_ts[i_]; } while (0)
+// ... and behind the tile-loop table [256 workgroups][16 waves][6], per wave: [0] the clocks from the kernel's entry to the end of
+// the W1 prologue (fragments in registers, before anything else is set up), [1] entry to exit
+#define IT_PROF_PRO_BASE ((size_t)256 * IT_WAVES * 6)
+#define IT_PROF_PRO_SLOT(tab, i) (tab)[IT_PROF_PRO_BASE + ((size_t)blockIdx.x * IT_WAVES + threadIdx.x / TZR_WAVE) * 2 + (i)]
+#define IT_PROF_PRO_BEGIN const uint64_t it_p0 = __builtin_amdgcn_s_memtime()
+#define IT_PROF_PRO_PARAM , const uint64_t it_p0
+#define IT_PROF_PRO_ARG , it_p0
+#define IT_PROF_PRO_END(tab) do { if ((tab) && (threadIdx.x & (TZR_WAVE - 1)) == 0) IT_PROF_PRO_SLOT(tab, 0) = __builtin_amdgcn_s_memtime() - it_p0; } while (0)
+#define IT_PROF_DUMP(tab) do { if (tab && lane == 0) { for (int i_ = 0; i_ < 6; ++i_) (tab)[((size_t)blockIdx.x * IT_WAVES + wv) * 6 + i_] = it_ts[i_]; \
+    IT_PROF_PRO_SLOT(tab, 1) = __builtin_amdgcn_s_memtime() - it_p0; } } while (0)
 extern "C" uint64_t* g_tzr_it_prof;
 uint64_t* g_tzr_it_prof = nullptr;
 extern "C" void tzr_it_prof_table(uint64_t* d_table) { g_tzr_it_prof = d_table; }
@@ -55,6 +65,10 @@ extern "C" void tzr_it_prof_table(uint64_t* d_table) { g_tzr_it_prof = d_table; 
 #define IT_PROF_DECL
 #define IT_PROF_MARK(i)
 #define IT_PROF_DUMP(tab)
+#define IT_PROF_PRO_BEGIN
+#define IT_PROF_PRO_PARAM
+#define IT_PROF_PRO_ARG
+#define IT_PROF_PRO_END(tab)
 #endif
 
 struct __attribute__((packed, aligned(4))) it_f4u {
@@ -100,6 +114,7 @@ __device__ __forceinline__ int it_real_col(int c, int P, int npb, int nblk) {
 // B = 65 536) instead of 243 + 2 x 205 MB.
 struct ItBwdArgs {
   const float *dense, *sparse, *g1, *W1, *scale;
+  const float* W1p;  // nullable: W1 in fragment order (interaction_pack.h, the backward's copy), 27 vectors only
   float *gdense, *gsparse;
   int64_t dense_stride, sparse_stride, g1_stride, ldw, gdense_stride, gsparse_stride, B;
   int n, hd;
@@ -133,8 +148,29 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
   // ---- W1 fragments (B operand: lane supplies W[k = 16 q + ks][column of (block, r)]); blocks behind the wave's last stay
   // zero.  Staged through LDS in slabs of 16 blocks x 64 rows so the global loads are coalesced runs: lanes asking for
   // their own elements straight from L2 (4 to 16 lines per load, every CU the same lines at once) took 11 - 24 us.
+  IT_PROF_PRO_BEGIN;
   float Wf[NB][IT_KS];
-  {
+  if (XL && a.W1p) {
+    // ... or, from the copy in fragment order, the lane's 48 registers as twelve coalesced 16-byte loads; no slabs, no barriers
+    const float sc = a.scale ? *a.scale : 1.f;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+      const float4 w = tzr_ld4(a.W1p + it_pack_bwd_off(wv, j, lane));
+      float* f = &Wf[j >> 2][4 * (j & 3)];
+      f[0] = sc * w.x; f[1] = sc * w.y; f[2] = sc * w.z; f[3] = sc * w.w;
+    }
+    // (the one pad column is a plain zero, whatever the scale: as the staged path leaves it)
+    constexpr int pv = IT_PACK_P >> 4;
+    if (wv == (pv & 15) && r == (IT_PACK_P & 15)) {
+#pragma unroll
+      for (int ks = 0; ks < IT_KS; ++ks) Wf[pv >> 4][ks] = 0.f;
+    }
+    if (wv == 0) {
+#pragma unroll
+      for (int ks = 0; ks < IT_KS; ++ks) Wx[ks * TZR_WAVE + lane] = sc * a.W1p[it_pack_bwd_x_off(ks, lane)];
+    }
+    __syncthreads();
+  } else {
     const float sc = a.scale ? *a.scale : 1.f;
     float* Wl = Z;  // [64 rows][256 + 1]: the slab
     const int c = threadIdx.x & 255, k0 = threadIdx.x >> 8;  // thread -> slab column, rows k0, k0 + 4, ...
@@ -170,6 +206,7 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
     }
     __syncthreads();
   }
+  IT_PROF_PRO_END(a.prof);
   // ---- where pair (k, c) lies in a sample's dz row (byte offset), or the zero slot: the first pad float behind the row
   {
     const int e = threadIdx.x, k = e >> 5, c = e & 31;
@@ -424,6 +461,7 @@ __global__ __launch_bounds__(IT_THREADS) void tzr_ia_top_bwd_kernel(ItBwdArgs a)
 // HBM) is produced right behind the product of tile t, with one barrier pair per tile.
 struct ItFwdArgs {
   const float *dense, *sparse, *W1, *bias;
+  const float* W1p;  // nullable: W1 in fragment order (interaction_pack.h, the forward's copy), read by it_fwd_criteo only
   float *z, *y1;
   int64_t dense_stride, sparse_stride, ldw, z_stride, y1_stride, B;
   int n, hd, relu, stagger;
@@ -493,7 +531,7 @@ __device__ __forceinline__ void it_fwd_row_pairs_out(const float* __restrict__ z
 template <int NB, int REM, int ZP>
 __device__ __forceinline__ void it_fwd_stage_w(const ItFwdArgs& a, float* __restrict__ Zs, float (&Wf)[NB][4], float (&Wx)[REM > 0 ? REM : 1],
                                                int n, int P, int npb, int base, int rem, int vfirst, int vlast, int r, int q,
-                                               int kg, int hb) {
+                                               int kg, int hb IT_PROF_PRO_PARAM) {
   const int nblk = npb + n;
   float* Wl = Zs;
   const int c = threadIdx.x;  // thread -> virtual column (16 nblk <= 1024 of them)
@@ -527,6 +565,7 @@ __device__ __forceinline__ void it_fwd_stage_w(const ItFwdArgs& a, float* __rest
     }
   }
   __syncthreads();
+  IT_PROF_PRO_END(a.prof);
   for (int k = threadIdx.x; k < 2 * IT_TS * ZP; k += IT_THREADS) Zs[k] = 0.f;
   __syncthreads();
 }
@@ -551,7 +590,8 @@ __device__ __forceinline__ void it_fwd_loop(const ItFwdArgs& a, float* __restric
   const int vfirst = kg * base, vlast = vfirst + base;
   float Wf[NB][4];
   float Wx[REM > 0 ? REM : 1];  // ... and for k-step kg of the left-over blocks
-  it_fwd_stage_w<NB, REM, ZP>(a, Zs, Wf, Wx, n, P, npb, base, rem, vfirst, vlast, r, q, kg, hb);
+  IT_PROF_PRO_BEGIN;
+  it_fwd_stage_w<NB, REM, ZP>(a, Zs, Wf, Wx, n, P, npb, base, rem, vfirst, vlast, r, q, kg, hb IT_PROF_PRO_ARG);
   const int64_t ntiles = (a.B + IT_TS - 1) / IT_TS;
   const int64_t G = gridDim.x;
   int64_t t = blockIdx.x;
@@ -691,6 +731,7 @@ __device__ __forceinline__ void it_fwd_loop(const ItFwdArgs& a, float* __restric
 static_assert(IT_C_NBLK == 4 * 12 + 1, "twelve whole blocks per K-group and one k-step of the 49th");
 static_assert(2 * IT_C_ZT + 2 * IT_C_YT <= 2 * IT_TS * IT_ZP + IT_C_YT, "fits the forward's LDS");
 static_assert(IT_C_ZT * 4 < 65536 && IT_C_YT * 4 < 65536, "the other buffer is an immediate offset of a DS instruction");
+static_assert(IT_PACK_N == IT_N_CRITEO && IT_PACK_P == IT_C_P && IT_PACK_NPB == IT_C_NPB && IT_PACK_H == IT_H, "interaction_pack.h describes this shape");
 
 __device__ __forceinline__ void it_fwd_criteo(const ItFwdArgs& a, float* __restrict__ Zs, float* __restrict__ Ys, int lane, int wv) {
   constexpr int n = IT_N_CRITEO, P = IT_C_P, npb = IT_C_NPB, NB = 12;
@@ -699,7 +740,21 @@ __device__ __forceinline__ void it_fwd_criteo(const ItFwdArgs& a, float* __restr
   const int vfirst = kg * NB;
   float Wf[NB][4];
   float Wx[1];
-  it_fwd_stage_w<NB, 1, IT_C_ZP>(a, Zs, Wf, Wx, n, P, npb, NB, 1, vfirst, vfirst + NB, r, q, kg, hb);
+  IT_PROF_PRO_BEGIN;
+  if (a.W1p) {
+    // the copy in fragment order: twelve coalesced 16-byte loads and one dword per lane, in flight while the tiles are zeroed
+#pragma unroll
+    for (int m = 0; m < NB; ++m) {
+      const float4 w = tzr_ld4(a.W1p + it_pack_fwd_off(wv, m, lane));
+      Wf[m][0] = w.x; Wf[m][1] = w.y; Wf[m][2] = w.z; Wf[m][3] = w.w;
+    }
+    Wx[0] = a.W1p[it_pack_fwd_x_off(wv, lane)];
+    IT_PROF_PRO_END(a.prof);
+    for (int k = threadIdx.x; k < 2 * IT_TS * IT_C_ZP; k += IT_THREADS) Zs[k] = 0.f;
+    __syncthreads();
+  } else {
+    it_fwd_stage_w<NB, 1, IT_C_ZP>(a, Zs, Wf, Wx, n, P, npb, NB, 1, vfirst, vfirst + NB, r, q, kg, hb IT_PROF_PRO_ARG);
+  }
   const int Bn = (int)a.B;  // (32-bit tile and sample counters, checked by the launcher: scalar compares)
   const int ntiles = (Bn + IT_TS - 1) / IT_TS;
   const int G = gridDim.x;
@@ -908,11 +963,38 @@ extern "C" int tzr_dot_interaction_top_supported(int F, int D, int has_dense, in
   return ((n * (n - 1) / 2 + 15) / 16 + n) <= IT_MAXBLK ? 1 : 0;
 }
 
-extern "C" int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_stride, const float* d_sparse,
-                                           int64_t sparse_stride, int F, int D, int64_t B, const float* d_g1,
-                                           int64_t g1_stride, int H, const float* d_W1, int64_t ldw,
-                                           const float* d_scale, float* d_grad_dense, int64_t grad_dense_stride,
-                                           float* d_grad_sparse, int64_t grad_sparse_stride, void* stream) {
+// W1 [64][ldw] of the 27-vector shape -> its two copies in fragment order (either destination may be null)
+__global__ __launch_bounds__(256) void tzr_ia_top_pack_w1_kernel(const float* __restrict__ W1, int64_t ldw, float* __restrict__ fwd,
+                                                                 float* __restrict__ bwd) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= IT_PACK_H * IT_PACK_VCOLS) return;
+  const int h = idx / IT_PACK_VCOLS, vc = idx - h * IT_PACK_VCOLS;
+  const int col = it_real_col(vc, IT_PACK_P, IT_PACK_NPB, IT_PACK_NPB + IT_PACK_N);
+  const float w = col >= 0 ? W1[(int64_t)h * ldw + col] : 0.f;
+  int pf, pb;
+  it_pack_pos(h, vc, &pf, &pb);
+  if (fwd) fwd[pf] = w;
+  if (bwd) bwd[pb] = w;
+}
+
+extern "C" int tzr_ia_top_pack_w1(const float* d_W1, int64_t ldw, int n, float* d_fwd_packed, float* d_bwd_packed, void* stream) {
+  if (!d_W1 || (!d_fwd_packed && !d_bwd_packed)) return TZR_ERR_INVALID;
+  if (n != IT_PACK_N) return TZR_ERR_UNSUPPORTED;
+  if (ldw < IT_PACK_WIDTH || ((reinterpret_cast<uintptr_t>(d_fwd_packed) | reinterpret_cast<uintptr_t>(d_bwd_packed)) & 15)) return TZR_ERR_INVALID;
+  hipLaunchKernelGGL(tzr_ia_top_pack_w1_kernel, dim3((IT_PACK_H * IT_PACK_VCOLS + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     d_W1, ldw, d_fwd_packed, d_bwd_packed);
+  TZR_CHECK_LAUNCH();
+  return TZR_OK;
+}
+
+extern "C" int tzr_ia_top_packed_floats(void) { return IT_PACK_FLOATS; }
+
+extern "C" int tzr_dot_interaction_top_bwd_packed(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                                  int64_t sparse_stride, int F, int D, int64_t B, const float* d_g1,
+                                                  int64_t g1_stride, int H, const float* d_W1, int64_t ldw,
+                                                  const float* d_scale, float* d_grad_dense, int64_t grad_dense_stride,
+                                                  float* d_grad_sparse, int64_t grad_sparse_stride, const float* d_W1_bwd_packed,
+                                                  void* stream) {
   const int hd = d_dense ? 1 : 0;
   const int n = F + hd;
   if (!d_sparse || !d_g1 || !d_W1 || !d_grad_sparse || F <= 0 || B < 0) return TZR_ERR_INVALID;
@@ -924,9 +1006,11 @@ extern "C" int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_s
       ((reinterpret_cast<uintptr_t>(d_sparse) | reinterpret_cast<uintptr_t>(d_grad_sparse) | reinterpret_cast<uintptr_t>(d_g1) |
         reinterpret_cast<uintptr_t>(d_dense) | reinterpret_cast<uintptr_t>(d_grad_dense)) & 15))
     return TZR_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(d_W1_bwd_packed) & 15) return TZR_ERR_INVALID;
   if (B == 0) return TZR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ItBwdArgs a;
+  a.W1p = n == IT_N_CRITEO ? d_W1_bwd_packed : nullptr;  // (other shapes: the plain W1, as ever)
   a.dense = d_dense; a.sparse = d_sparse; a.g1 = d_g1; a.W1 = d_W1; a.scale = d_scale; a.gdense = d_grad_dense; a.gsparse = d_grad_sparse;
   a.dense_stride = dense_stride; a.sparse_stride = sparse_stride; a.g1_stride = g1_stride; a.ldw = ldw;
   a.gdense_stride = grad_dense_stride; a.gsparse_stride = grad_sparse_stride; a.B = B; a.n = n; a.hd = hd;
@@ -940,10 +1024,20 @@ extern "C" int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_s
   return TZR_OK;
 }
 
-extern "C" int tzr_dot_interaction_top_fwd(const float* d_dense, int64_t dense_stride, const float* d_sparse,
-                                           int64_t sparse_stride, int F, int D, int64_t B, const float* d_W1,
-                                           int64_t ldw, const float* d_bias, int H, int relu, float* d_z,
-                                           int64_t z_stride, float* d_y1, int64_t y1_stride, void* stream) {
+extern "C" int tzr_dot_interaction_top_bwd(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                           int64_t sparse_stride, int F, int D, int64_t B, const float* d_g1,
+                                           int64_t g1_stride, int H, const float* d_W1, int64_t ldw,
+                                           const float* d_scale, float* d_grad_dense, int64_t grad_dense_stride,
+                                           float* d_grad_sparse, int64_t grad_sparse_stride, void* stream) {
+  return tzr_dot_interaction_top_bwd_packed(d_dense, dense_stride, d_sparse, sparse_stride, F, D, B, d_g1, g1_stride, H, d_W1, ldw, d_scale,
+                                            d_grad_dense, grad_dense_stride, d_grad_sparse, grad_sparse_stride, nullptr, stream);
+}
+
+extern "C" int tzr_dot_interaction_top_fwd_packed(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                                  int64_t sparse_stride, int F, int D, int64_t B, const float* d_W1,
+                                                  int64_t ldw, const float* d_bias, int H, int relu, float* d_z,
+                                                  int64_t z_stride, float* d_y1, int64_t y1_stride, const float* d_W1_fwd_packed,
+                                                  void* stream) {
   const int hd = d_dense ? 1 : 0;
   const int n = F + hd;
   if (!d_sparse || !d_W1 || !d_y1 || F <= 0 || B < 0) return TZR_ERR_INVALID;
@@ -955,9 +1049,11 @@ extern "C" int tzr_dot_interaction_top_fwd(const float* d_dense, int64_t dense_s
       ((reinterpret_cast<uintptr_t>(d_sparse) | reinterpret_cast<uintptr_t>(d_dense)) & 15) ||
       (reinterpret_cast<uintptr_t>(d_y1) & 3) || (reinterpret_cast<uintptr_t>(d_z) & 3))
     return TZR_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(d_W1_fwd_packed) & 15) return TZR_ERR_INVALID;
   if (B == 0) return TZR_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ItFwdArgs a;
+  a.W1p = (n == IT_N_CRITEO && !d_z) ? d_W1_fwd_packed : nullptr;  // (the z-writing kernel and other shapes: the plain W1, as ever)
   a.dense = d_dense; a.sparse = d_sparse; a.W1 = d_W1; a.bias = d_bias; a.z = d_z; a.y1 = d_y1;
   a.dense_stride = dense_stride; a.sparse_stride = sparse_stride; a.ldw = ldw; a.z_stride = z_stride; a.y1_stride = y1_stride;
   a.B = B; a.n = n; a.hd = hd; a.relu = relu;
@@ -971,4 +1067,12 @@ extern "C" int tzr_dot_interaction_top_fwd(const float* d_dense, int64_t dense_s
   else hipLaunchKernelGGL(tzr_ia_top_fwd_kernel, dim3(it_grid(B)), dim3(IT_THREADS), 0, st, a);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
+}
+
+extern "C" int tzr_dot_interaction_top_fwd(const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                           int64_t sparse_stride, int F, int D, int64_t B, const float* d_W1,
+                                           int64_t ldw, const float* d_bias, int H, int relu, float* d_z,
+                                           int64_t z_stride, float* d_y1, int64_t y1_stride, void* stream) {
+  return tzr_dot_interaction_top_fwd_packed(d_dense, dense_stride, d_sparse, sparse_stride, F, D, B, d_W1, ldw, d_bias, H, relu, d_z, z_stride,
+                                            d_y1, y1_stride, nullptr, stream);
 }

@@ -12,7 +12,7 @@ from __future__ import annotations
 import contextlib
 import os
 import weakref
-from typing import Iterable, List, Optional
+from typing import Iterable, List, Optional, Tuple
 
 import ctypes as C
 
@@ -677,6 +677,83 @@ def _owned_wgrad(batch: int, row_floats: int) -> bool:
     return bool(OWNED_WGRAD) and batch * max(row_floats, 64) < (1 << 32)
 
 
+# ---- W1 of the fused interaction layer in the order of the kernels' MFMA fragments (csrc/interaction_pack.h) ----------------
+# Out of the plain [64, 783] matrix every persistent workgroup of tzr_dot_interaction_top_fwd / _bwd re-orders W1 through LDS
+# before its first tile (~6 us per launch); out of a packed copy the lanes load their registers directly.  A FusedDenseAdam
+# that owns such a parameter keeps two copies beside it and writes them in its own launch; every other writer (`copy_`,
+# `load_state_dict`, another optimizer) moves the tensor's `_version`, which is compared before each use outside a replayed
+# graph: on a mismatch the pack kernel runs.  A captured step is checked when it is captured -- whoever overwrites W1 between
+# replays calls `repack_w1(param)`.  A parameter no FusedDenseAdam owns has no copies: the kernels stage W1 as ever.
+W1_PACKED_SHAPE = (64, 27 * 26 // 2 + 16 * 27)
+
+
+class _PackedW1:
+    __slots__ = ("ref", "fwd", "bwd", "version")
+
+
+_W1_PACKED: dict = {}  # data_ptr of the parameter -> _PackedW1
+
+
+def _packed_entry(p: torch.Tensor) -> Optional["_PackedW1"]:
+    e = _W1_PACKED.get(p.data_ptr())
+    if e is None:
+        return None
+    q = e.ref()
+    if q is None or q.data_ptr() != p.data_ptr() or tuple(q.shape) != W1_PACKED_SHAPE:  # (the owner is gone, its address reused)
+        del _W1_PACKED[p.data_ptr()]
+        return None
+    return e
+
+
+def register_packed_w1(p: torch.Tensor) -> Optional["_PackedW1"]:
+    """Packed copies for `p` if it has the shape of DLRM-Criteo's first top-MLP weight (stale until first used)."""
+    if tuple(p.shape) != W1_PACKED_SHAPE or p.dtype != torch.float32 or not p.is_contiguous():
+        return None
+    e = _packed_entry(p)
+    if e is None:
+        for k in [k for k, o in _W1_PACKED.items() if o.ref() is None]:
+            del _W1_PACKED[k]
+        e = _PackedW1()
+        e.ref = weakref.ref(p)
+        n = int(_lib.lib().tzr_ia_top_packed_floats())
+        e.fwd = torch.zeros(n, dtype=torch.float32, device=p.device)
+        e.bwd = torch.zeros(n, dtype=torch.float32, device=p.device)
+        e.version = -1
+        _W1_PACKED[p.data_ptr()] = e
+    return e
+
+
+def pack_w1(W1: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(forward copy, backward copy) of a plain W1 [64, 783] (tzr_ia_top_pack_w1)."""
+    W1 = _f32c(W1.detach())
+    n = int(_lib.lib().tzr_ia_top_packed_floats())
+    fwd, bwd = (torch.zeros(n, dtype=torch.float32, device=W1.device) for _ in range(2))
+    _lib.check(_lib.lib().tzr_ia_top_pack_w1(_lib.ptr(W1), W1.stride(0), 27, _lib.ptr(fwd), _lib.ptr(bwd), _lib.stream_ptr(W1.device)),
+               "tzr_ia_top_pack_w1")
+    return fwd, bwd
+
+
+def repack_w1(p: torch.Tensor) -> None:
+    """Bring the packed copies of `p` (if it has any) up to date with it now: after W1 was overwritten behind a captured step."""
+    e = _packed_entry(p)
+    if e is None:
+        return
+    q = e.ref()
+    _lib.check(_lib.lib().tzr_ia_top_pack_w1(_lib.ptr(q.data), q.stride(0), 27, _lib.ptr(e.fwd), _lib.ptr(e.bwd), _lib.stream_ptr(q.device)),
+               "tzr_ia_top_pack_w1")
+    e.version = q._version
+
+
+def _fresh_packed_w1(W1: torch.Tensor) -> Optional["_PackedW1"]:
+    """the up-to-date copies of W1 for a kernel about to read it, or None: the plain path"""
+    e = _packed_entry(W1)
+    if e is None:
+        return None
+    if e.version != e.ref()._version:
+        repack_w1(W1)
+    return e
+
+
 class _InteractionTopLossFn(torch.autograd.Function):
     """DLRM from the embeddings to the loss: dot interaction + first top-MLP layer as one kernel per direction
     (tzr_dot_interaction_top_fwd / _bwd, csrc/interaction_top.hip), the rest of the top MLP + loss + their backward as
@@ -696,10 +773,12 @@ class _InteractionTopLossFn(torch.autograd.Function):
         y1 = torch.empty(B, H1, dtype=torch.float32, device=dev)
         z = None if _owned_wgrad(B, sparse.shape[1]) else torch.empty(B, width, dtype=torch.float32, device=dev)
         W1_, b1_ = _f32c(W1), _f32c(b1)
-        _lib.check(_lib.lib().tzr_dot_interaction_top_fwd(
+        pk = _fresh_packed_w1(W1_) if (n == 27 and D == 16 and H1 == 64) else None
+        _lib.check(_lib.lib().tzr_dot_interaction_top_fwd_packed(
             _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(W1_), W1_.stride(0),
-            _lib.ptr(b1_), H1, 1, _lib.ptr(z), width, _lib.ptr(y1), y1.stride(0), _lib.stream_ptr(dev)),
-            "tzr_dot_interaction_top_fwd")
+            _lib.ptr(b1_), H1, 1, _lib.ptr(z), width, _lib.ptr(y1), y1.stride(0), _lib.ptr(pk.fwd) if pk is not None else None,
+            _lib.stream_ptr(dev)), "tzr_dot_interaction_top_fwd_packed")
+        ctx.w1_packed = pk
         logits, g1, dW2, db2, dw3, scal, db1 = _mlp_tail(y1, labels, W2, b2, w3, b3)
         ctx.save_for_backward(dense, sparse, W1_, g1, dW2, db2, dw3, scal, db1)
         ctx.z = z
@@ -720,10 +799,12 @@ class _InteractionTopLossFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gs = torch.empty_like(sparse)
             gd = torch.empty_like(dense)
-            _lib.check(_lib.lib().tzr_dot_interaction_top_bwd(
+            pk = ctx.w1_packed  # (as fresh as the saved W1: autograd refuses a W1 changed since the forward)
+            _lib.check(_lib.lib().tzr_dot_interaction_top_bwd_packed(
                 _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(g1), g1.stride(0),
                 g1.shape[1], _lib.ptr(W1), W1.stride(0), _lib.ptr(gl32), _lib.ptr(gd), gd.stride(0), _lib.ptr(gs),
-                gs.stride(0), _lib.stream_ptr(sparse.device)), "tzr_dot_interaction_top_bwd")
+                gs.stride(0), _lib.ptr(pk.bwd) if pk is not None else None, _lib.stream_ptr(sparse.device)),
+                "tzr_dot_interaction_top_bwd_packed")
         if not ctx.needs_input_grad[3]:
             dW1 = None
         elif ctx.z is None:
@@ -854,10 +935,15 @@ def _launch_fused(rows, tables, launch) -> None:
         del keep
 
 
-def _after_fused_step(opt) -> None:
+def _after_fused_step(opt, packed_written=()) -> None:
     name = type(opt).__name__
     for p in opt.params:
         _DEFERRED.pop(id(p), None)
+    if _W1_PACKED:  # a launch that wrote W1 through its address and not its packed copies: stale
+        for p in opt.params:
+            e = _W1_PACKED.get(p.data_ptr())
+            if e is not None and e not in packed_written:
+                e.version = -1
     if any(len(e) > 4 and e[4] == id(opt) and e[3] == _GENERATION[0] for e in _PENDING.values()):
         # a backward left a gradient of one of THIS optimizer's parameters as partial sums and the tensor that reached `.grad` is
         # another one (autograd copied it): its parameter was just stepped with unwritten memory.  Never silently.
@@ -892,6 +978,8 @@ class FusedDenseAdam:
         self._state = torch.zeros(len(self.params), 40, dtype=torch.float32, device=dev)
         self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
         self._lr_host = float(lr)
+        for p in self.params:  # W1 of the fused interaction layer: packed copies, written by `step`'s launch
+            register_packed_w1(p)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         _zero_grad(self.params, set_to_none)
@@ -918,12 +1006,27 @@ class FusedDenseAdam:
         if not rows:
             return
         b1, b2 = g["betas"]
-        _launch_fused(
-            [(p.data, gr, m, v, st) for p, gr, m, v, st in rows], _adam_tables,
-            lambda tab, src, wg: _lib.check(_lib.lib().tzr_dense_adam_fused(
+        written = []  # packed copies of W1 this step's launches keep up to date
+
+        def launch(tab, src, wg):
+            w1 = None
+            if _W1_PACKED:
+                for i in range(len(tab)):
+                    e = _W1_PACKED.get(tab[i].param) if tab[i].param else None
+                    if e is not None and e.ref() is not None and e.ref().data_ptr() == tab[i].param:
+                        # (one per launch; the launch writes every element, so copies that were stale are whole behind it)
+                        w1 = _lib.TzrPackedW1(tab[i].param, _lib.ptr(e.fwd), _lib.ptr(e.bwd))
+                        written.append(e)
+                        break
+            _lib.check(_lib.lib().tzr_dense_adam_fused_w1(
                 tab, src, len(tab), C.byref(wg) if wg is not None else None, _lib.ptr(self._lr_dev), g["lr"], b1, b2, g["eps"],
-                g["weight_decay"], _lib.stream_ptr(self.device)), "tzr_dense_adam_fused"))
-        _after_fused_step(self)
+                g["weight_decay"], C.byref(w1) if w1 is not None else None, _lib.stream_ptr(self.device)), "tzr_dense_adam_fused_w1")
+
+        _launch_fused([(p.data, gr, m, v, st) for p, gr, m, v, st in rows], _adam_tables, launch)
+        for e in written:  # the launch wrote W1 through its address: move its version on, so that the recorded one means something
+            torch.autograd.graph.increment_version(e.ref())
+            e.version = e.ref()._version
+        _after_fused_step(self, written)
 
     def state_dict(self) -> dict:
         return {"state": {i: {"step": self._state[i, 0].clone(), "exp_avg": m, "exp_avg_sq": v}
