@@ -180,7 +180,7 @@ def test_pack_gradients_equals_concatenation_and_fails_loudly_on_a_lost_partial(
     assert len(dense._PENDING) >= 4
     flat = pack_gradients(list(g_fused))
     assert flat is not None and torch.equal(flat.cpu(), want.cpu())
-    assert not any(e[3] == dense._GENERATION[0] for e in dense._PENDING.values())
+    assert not any(e.generation == dense._GENERATION[0] for e in dense._PENDING.values())
     torch.manual_seed(1)
     o3, g_lost = grads(True)
     with pytest.raises(RuntimeError, match="partial sums"):
@@ -258,3 +258,89 @@ def test_an_abandoned_backward_pass_does_not_look_like_a_shared_layer(dev):
     assert bool(all(torch.isfinite(p).all() for p in own))
     dense._PENDING.clear()
     del o
+
+
+def _mlp2_params(dev):
+    """the smallest shapes at which `mlp2` defers four gradients: Wa [64, 13], ba [64], Wb [16, 64], bb [16]"""
+    return [torch.nn.Parameter(t) for t in (torch.randn(64, 13, device=dev) * 0.1, torch.zeros(64, device=dev),
+                                            torch.randn(16, 64, device=dev) * 0.1, torch.zeros(16, device=dev))]
+
+
+def test_a_tensor_of_another_size_at_a_deferred_gradients_address_is_a_finished_tensor(dev):
+    """a deferred gradient that nobody steps leaves its entry behind; a finished gradient of ANOTHER size at that address (the
+    allocator reuses it) is stepped as the tensor it is, not as the partial rows of the one that is gone"""
+    from torcheasyrec_amd.dense import mlp2
+
+    torch.manual_seed(0)
+    own = _mlp2_params(dev)
+    o = FusedDenseAdam(own, lr=1e-2, fuse_finish=True)
+    g_Wa, _, _, _ = gs = torch.autograd.grad(mlp2(torch.randn(96, 13, device=dev), *own).sum(), own)
+    assert len(dense._PENDING) == 4 and g_Wa.data_ptr() in dense._PENDING
+    fake = g_Wa.view(-1)[:100]  # same address, other numel
+    fake.fill_(7.0)
+    q = torch.nn.Parameter(torch.ones(100, device=dev))
+    q.grad = fake
+    FusedDenseAdam([q], lr=1e-2).step()
+    r = torch.nn.Parameter(torch.ones(100))
+    r.grad = torch.full((100,), 7.0)
+    torch.optim.Adam([r], lr=1e-2).step()
+    torch.testing.assert_close(q.detach().cpu(), r.detach(), rtol=2e-6, atol=2e-7)
+    assert g_Wa.data_ptr() not in dense._PENDING
+    dense._PENDING.clear()
+    dense._DEFERRED.clear()
+    del o, gs
+
+
+@pytest.mark.parametrize("set_to_none", [True, False])
+def test_zero_grad_forgets_a_backward_pass_that_was_not_stepped(dev, set_to_none):
+    """backward, zero_grad, no step: nothing of that pass stays in the ledger, and the next backward + step trains"""
+    from torcheasyrec_amd.dense import mlp2
+
+    torch.manual_seed(0)
+    own = _mlp2_params(dev)
+    o = FusedDenseAdam(own, lr=1e-2, fuse_finish=True)
+    x = torch.randn(96, 13, device=dev)
+    mlp2(x, *own).sum().backward()
+    assert len(dense._PENDING) == 4
+    o.zero_grad(set_to_none=set_to_none)
+    assert not dense._PENDING and not dense._DEFERRED
+    if set_to_none:
+        assert all(p.grad is None for p in own)
+    else:
+        assert all(p.grad is not None and not bool(p.grad.any()) for p in own)  # (the unwritten tensors: zeros now)
+    before = [p.detach().clone() for p in own]
+    mlp2(x, *own).sum().backward()
+    o.step()
+    assert all(not torch.equal(a, p.detach()) for a, p in zip(before, own))
+    assert bool(all(torch.isfinite(p).all() for p in own))
+    dense._PENDING.clear()
+    del o
+
+
+def test_two_weight_gradient_slice_sets_in_one_chunk_equal_the_finished_gradients(dev):
+    """two parameters whose gradients are both slice sets of tzr_dot_interaction_top_wgrad_parts, stepped by one optimizer: a
+    launch adds up one set, so the second is written out by a launch of its own first -- the same parameters, bit for bit,
+    as with gradients that were finished by the kernel's own reduction"""
+    from torcheasyrec_amd.dense import interaction_top_wgrad
+
+    B, F, D, H = 64, 26, 16, 64
+    gen = torch.Generator().manual_seed(0)
+    dn, sp = torch.randn(B, D, generator=gen).to(dev), torch.randn(B, F * D, generator=gen).to(dev)
+    g1s = [torch.randn(B, H, generator=gen).to(dev) for _ in range(2)]
+    w0 = [torch.randn(H, 27 * 26 // 2 + D * 27, generator=gen) * 0.1 for _ in range(2)]
+
+    def run(fuse):
+        ws = [torch.nn.Parameter(w.clone().to(dev)) for w in w0]
+        dense.FUSE_FINISH = False
+        o = FusedDenseAdam(ws, lr=1e-2, fuse_finish=fuse)
+        for w, g1 in zip(ws, g1s):
+            w.grad = interaction_top_wgrad(dn, sp, D, g1, defer_for=(w,))
+        kinds = sorted(e.kind for e in dense._PENDING.values())
+        o.step()
+        assert not dense._PENDING
+        return [w.detach().cpu().clone() for w in ws], kinds
+
+    (pa, ka), (pb, kb) = run(False), run(True)
+    assert ka == [] and kb == ["wgrad", "wgrad"]
+    for a, b, w in zip(pa, pb, w0):
+        assert torch.equal(a, b) and not torch.equal(a, w)

@@ -9,7 +9,9 @@ tests compare against torch to 1e-6.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
+import dataclasses
 import os
 import weakref
 from typing import Iterable, List, Optional, Tuple
@@ -73,7 +75,7 @@ def relu_bwd_colsum(grad_y: torch.Tensor, y: torch.Tensor, defer_for=None):
         G = C.c_int(0)
         _lib.check(L.tzr_relu_bwd_colsum_parts(_lib.ptr(gy), gy.stride(0), _lib.ptr(y), y.stride(0), B, N, _lib.ptr(g), g.stride(0),
                                                _lib.ptr(ws), ws.numel(), C.byref(G), _lib.stream_ptr(y.device)), "tzr_relu_bwd_colsum_parts")
-        _PENDING[col.data_ptr()] = ("rows", (ws,), (G.value, N, 0), _GENERATION[0], _owner_id(defer_for), tuple(id(q) for q in defer_for))
+        _defer(col, "rows", (ws,), (G.value, N, 0), defer_for)
         return g, col
     _lib.check(L.tzr_relu_bwd_colsum(_lib.ptr(gy), gy.stride(0), _lib.ptr(y), y.stride(0), B, N, _lib.ptr(g), g.stride(0),
                                      _lib.ptr(col), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(y.device)), "tzr_relu_bwd_colsum")
@@ -208,8 +210,8 @@ def skinny_linear_bwd(grad_y: torch.Tensor, x: torch.Tensor, weight: torch.Tenso
                                                  n, _lib.ptr(gx), 0 if gx is None else gx.stride(0), _lib.ptr(ws), ws.numel(), C.byref(G),
                                                  C.byref(P), _lib.stream_ptr(x.device)), "tzr_skinny_linear_bwd_parts")
         gw, gb = wb[:n * K].view(n, K), wb[n * K:n * K + n]
-        _PENDING[gw.data_ptr()] = ("rows", (ws, wb), (G.value, P.value, 0), _GENERATION[0], _owner_id(defer_for), tuple(id(q) for q in defer_for))
-        _PENDING[gb.data_ptr()] = ("rows", (ws, wb), (G.value, P.value, n * K), _GENERATION[0], _owner_id(defer_for), tuple(id(q) for q in defer_for))
+        _defer(gw, "rows", (ws, wb), (G.value, P.value, 0), defer_for)
+        _defer(gb, "rows", (ws, wb), (G.value, P.value, n * K), defer_for)
         return gx, gw, gb
     _lib.check(L.tzr_skinny_linear_bwd(_lib.ptr(gy), gy.stride(0), _lib.ptr(xs), xs.stride(0), _lib.ptr(weight), weight.stride(0), B, K, n,
                                        _lib.ptr(gx), 0 if gx is None else gx.stride(0), _lib.ptr(wb), _lib.ptr(ws), ws.numel(),
@@ -301,6 +303,12 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.contiguous().float()
 
 
+def _step_grads(params, grads: Optional[List[torch.Tensor]] = None) -> list:
+    """what a dense optimizer's step starts from: (index, gradient as contiguous fp32) of every parameter that has one -- its `.grad`, or `grads[index]`"""
+    grads = [p.grad for p in params] if grads is None else grads
+    return [(i, _f32c(g)) for i, g in enumerate(grads) if g is not None]
+
+
 def weight_grad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """g^T x ([H, B] x [B, K]) -- the weight gradient of a Linear layer.  One output tile of 64 x 783 and a 65536-long
     reduction is the worst shape for a GEMM library: as 16 batched products over slices of the batch plus a 16-way sum
@@ -369,13 +377,32 @@ def _loss_is_root(gl: Optional[torch.Tensor] = None) -> bool:
 # gradient before the optimizer has run -- clipping, a collective, gradient accumulation -- calls `materialize_pending()` first;
 # the flag is the caller's statement that nothing does.
 FUSE_FINISH = False
-# data_ptr of the returned gradient tensor -> (kind, keep-alive tensors, source fields, generation).  (NO reference to the tensor
-# itself: autograd hands a gradient over to `.grad` without a copy only when nobody else holds it -- a copy would be a copy of
-# unwritten memory under another address.  Claimed by address: `FusedDenseAdam.step` / `materialize_pending` look their tensors up.)
+# data_ptr of the returned gradient tensor -> _Pending.  (NO reference to the tensor itself: autograd hands a gradient over to
+# `.grad` without a copy only when nobody else holds it -- a copy would be a copy of unwritten memory under another address.
+# Claimed by address: `FusedDenseAdam.step` / `materialize_pending` look their tensors up.)
 _PENDING: dict = {}
 # id of a parameter whose gradient was left as partial sums -> the backward pass that did it (autograd's graph-task id; cleared by
 # the optimizer's step / zero_grad)
 _DEFERRED: dict = {}
+_OPTIMIZERS: "weakref.WeakSet" = weakref.WeakSet()  # live FusedDenseAdam objects (materialize_pending's default reach)
+_FUSED_OWNER: dict = {}  # id(parameter) -> (weakref of the parameter, weakref of the fuse_finish optimizer that steps it)  (by id: tensors compare elementwise)
+_GENERATION = [0]  # optimizer steps seen: an entry nobody has claimed two steps later belongs to a tensor that is gone
+
+
+@dataclasses.dataclass(slots=True)
+class _Pending:  # what an unwritten gradient tensor stands for
+    kind: str  # "rows" | "wgrad"
+    keep: tuple  # the tensors the sums lie in (kept alive; rows: [0] holds them)
+    where: object  # rows: (G, P, col) of tzr_mlp2_bwd_parts' layout; wgrad: the TzrWgradParts blob
+    numel: int  # of the tensor it stands for: another size at its address is another tensor
+    generation: int
+    owner: int  # id of the fusing optimizer that steps the parameters (0: none)
+    params: tuple  # ids of the parameters of that backward
+
+
+# one tensor of a fused optimizer launch.  `grad`: where the gradient goes / lies; `key`: the tensor autograd returned (what _PENDING
+# knows) when that is another one; `param` None: the gradient is only written out; `group`: of tzr_dense_optim_fused
+_Row = collections.namedtuple("_Row", "param grad state0 state1 state key group", defaults=(None, 0))
 
 
 def _backward_pass_id() -> int:
@@ -388,6 +415,29 @@ def _owner_id(params) -> int:
     ent = _FUSED_OWNER.get(id(params[0])) if params else None
     o = ent[1]() if ent is not None else None
     return id(o) if o is not None else 0
+
+
+def _defer(tensor: torch.Tensor, kind: str, keep: tuple, where, params) -> None:
+    """note that `tensor`, about to be returned to autograd unwritten, stands for these partial sums"""
+    _PENDING[tensor.data_ptr()] = _Pending(kind, keep, where, tensor.numel(), _GENERATION[0], _owner_id(params), tuple(id(q) for q in params))
+
+
+def _claim(t: torch.Tensor) -> Optional[_Pending]:
+    """the entry `t` stands for, taken out of the ledger; None: a finished tensor (an entry of another size goes too: its tensor is gone)"""
+    e = _PENDING.pop(t.data_ptr(), None)
+    return e if e is not None and e.numel == t.numel() else None
+
+
+def _forget(param_ids: set) -> None:
+    """drop what the backward passes of these parameters left behind"""
+    for ptr in [q for q, e in _PENDING.items() if param_ids.intersection(e.params)]:
+        del _PENDING[ptr]
+
+
+def _one_launch(tensors) -> int:
+    """how many of `tensors`, from the front, ONE launch takes: at most 32, among them at most one weight-gradient slice set"""
+    wg = [n for n, t in enumerate(tensors[:32]) if (e := _PENDING.get(t.data_ptr())) is not None and e.kind == "wgrad" and e.numel == t.numel()]
+    return wg[1] if len(wg) > 1 else min(len(tensors), 32)
 
 
 def _defer_finish(dev: torch.device, params=()) -> bool:
@@ -410,66 +460,36 @@ def _defer_finish(dev: torch.device, params=()) -> bool:
         # left as partial sums -- may not have reached `.grad` yet: nothing here can write it out in time.  Never silently.
         raise RuntimeError("FusedDenseAdam(fuse_finish=True): a parameter takes part in the model twice (a shared layer): its two "
                            "gradients would be added before the first is written; construct the optimizer with fuse_finish=False")
-    stale = {id(p) for p in params if id(p) in _DEFERRED}
-    if stale:  # their earlier pass was abandoned (gradients dropped by hand): what it left behind goes with it
-        for ptr in [q for q, e in _PENDING.items() if len(e) > 5 and stale.intersection(e[5])]:
-            del _PENDING[ptr]
+    _forget({id(p) for p in params if id(p) in _DEFERRED})  # their earlier pass was abandoned (gradients dropped by hand): what it left behind goes with it
     _DEFERRED.update((id(p), task) for p in params)
     return True
 
 
 def _adam_tables(rows, tensor_type=None):
-    """rows: (param | None, grad, exp_avg | None, exp_avg_sq | None, state | None) -> the C arrays of tzr_dense_adam_fused; with
-    `tensor_type` = _lib.TzrDenseOptTensor those of tzr_dense_optim_fused (the two optimizer-state tensors of a row are then
-    the kind's state0 / state1, and a row goes on with (key tensor, group index))"""
-    n = len(rows)
+    """_Rows, no more than `_one_launch` takes -> the C arrays of tzr_dense_adam_fused (`tensor_type` = _lib.TzrDenseOptTensor: of tzr_dense_optim_fused)"""
     T = tensor_type or _lib.TzrAdamTensor
     s0, s1 = ("exp_avg", "exp_avg_sq") if T is _lib.TzrAdamTensor else ("state0", "state1")
-    tab = (T * n)()
-    src = (_lib.TzrAdamSource * n)()
-    wg = None
-    keep = []
-    for i, row in enumerate(rows):
-        p, gr, m, v, st = row[:5]
-        key = row[5] if len(row) > 5 else gr  # the tensor autograd returned (what _PENDING knows); `gr` = where the gradient goes / lies
-        tab[i].param = _lib.ptr(p) if p is not None else 0
-        tab[i].grad = _lib.ptr(gr)
-        setattr(tab[i], s0, _lib.ptr(m) if m is not None else 0)
-        setattr(tab[i], s1, _lib.ptr(v) if v is not None else 0)
-        tab[i].state = _lib.ptr(st) if st is not None else 0
-        tab[i].numel = gr.numel()
-        if len(row) > 6:
-            tab[i].group = row[6]
-        pend = _PENDING.pop(key.data_ptr(), None)
-        if pend is None:
-            src[i].kind = _lib.ADAM_SRC_TENSOR
-            if key is not gr:
-                src[i].parts = _lib.ptr(key)  # a finished tensor elsewhere: copied
-                keep.append((key,))
-        elif pend[0] == "rows":
-            _, alive, (G, P, col) = pend[:3]
-            if col + gr.numel() > P:  # an entry left behind by a tensor that is gone, its address reused: this gradient is a finished tensor
-                src[i].kind = _lib.ADAM_SRC_TENSOR
-                if key is not gr:
-                    src[i].parts = _lib.ptr(key)
-                    keep.append((key,))
-                continue
-            src[i].kind, src[i].G, src[i].P, src[i].col, src[i].parts = _lib.ADAM_SRC_ROWS, G, P, col, _lib.ptr(alive[0])
-            keep.append(alive)
-        else:
-            _, alive, blob = pend[:3]
-            if wg is not None:  # (one slice set per launch: the first stays, this one is written out on its own below)
-                _PENDING[key.data_ptr()] = pend
-                src[i].kind = -1
-                continue
-            src[i].kind, wg = _lib.ADAM_SRC_WGRAD, blob
-            keep.append(alive)
+    tab, src = (T * len(rows))(), (_lib.TzrAdamSource * len(rows))()
+    wg, keep = None, []
+    for i, r in enumerate(rows):
+        key = r.grad if r.key is None else r.key
+        tab[i].param = _lib.ptr(r.param) if r.param is not None else 0
+        tab[i].grad = _lib.ptr(r.grad)
+        setattr(tab[i], s0, _lib.ptr(r.state0) if r.state0 is not None else 0)
+        setattr(tab[i], s1, _lib.ptr(r.state1) if r.state1 is not None else 0)
+        tab[i].state = _lib.ptr(r.state) if r.state is not None else 0
+        tab[i].numel = r.grad.numel()
+        if r.group:
+            tab[i].group = r.group
+        e = _claim(key)
+        if e is None:  # a finished tensor; elsewhere: copied
+            src[i].kind, src[i].parts = _lib.ADAM_SRC_TENSOR, _lib.ptr(key) if key is not r.grad else 0
+        elif e.kind == "rows":
+            src[i].kind, (src[i].G, src[i].P, src[i].col), src[i].parts = _lib.ADAM_SRC_ROWS, e.where, _lib.ptr(e.keep[0])
+        else:  # (the one slice set of this launch: the C side refuses a second)
+            src[i].kind, wg = _lib.ADAM_SRC_WGRAD, e.where
+        keep.append(e.keep if e is not None else (key,))
     return tab, src, wg, keep
-
-
-_OPTIMIZERS: "weakref.WeakSet" = weakref.WeakSet()  # live FusedDenseAdam objects (materialize_pending's default reach)
-_FUSED_OWNER: dict = {}  # id(parameter) -> (weakref of the parameter, weakref of the fuse_finish optimizer that steps it)  (by id: tensors compare elementwise)
-_GENERATION = [0]  # optimizer steps seen: an entry nobody has claimed two steps later belongs to a tensor that is gone
 
 
 def materialize_pending(tensors: Optional[Iterable[torch.Tensor]] = None) -> None:
@@ -482,19 +502,12 @@ def materialize_pending(tensors: Optional[Iterable[torch.Tensor]] = None) -> Non
         tensors = [p.grad for o in list(_OPTIMIZERS) for p in o.params if p.grad is not None]
     todo = [t for t in tensors if t is not None and t.data_ptr() in _PENDING]
     while todo:
-        rows, rest, has_wg = [], [], False
-        for t in todo:
-            is_wg = _PENDING[t.data_ptr()][0] == "wgrad"
-            if len(rows) == 32 or (is_wg and has_wg):  # (one slice set per launch)
-                rest.append(t)
-                continue
-            has_wg = has_wg or is_wg
-            rows.append((None, t, None, None, None))
-        tab, src, wg, keep = _adam_tables(rows)
-        _lib.check(_lib.lib().tzr_dense_adam_fused(tab, src, len(rows), C.byref(wg) if wg is not None else None, None, 0.0, 0.9, 0.999,
-                                                   1e-8, 0.0, _lib.stream_ptr(rows[0][1].device)), "tzr_dense_adam_fused")
+        n = _one_launch(todo)
+        tab, src, wg, keep = _adam_tables([_Row(None, t, None, None, None) for t in todo[:n]])
+        _lib.check(_lib.lib().tzr_dense_adam_fused(tab, src, n, C.byref(wg) if wg is not None else None, None, 0.0, 0.9, 0.999,
+                                                   1e-8, 0.0, _lib.stream_ptr(todo[0].device)), "tzr_dense_adam_fused")
         del keep
-        todo = rest
+        todo = todo[n:]
 
 
 PACKED_LAUNCHES = [0]  # pack_gradients calls that launched / of them: with partial sums among the sources (tests)
@@ -503,21 +516,17 @@ PACKED_PARTIALS = [0]
 
 def pack_gradients(grads) -> Optional[torch.Tensor]:
     """torch.cat([g.reshape(-1) for g in grads]) in ONE launch that takes each gradient as it lies -- a finished tensor (copied) or
-    the partial sums a backward left for the optimizer (added up on the way, same order as their finishing launch: bit-identical)
-    -- the flat buffer of the sharded step's dense all-reduce.  None: not a case for it (the caller concatenates)."""
+    the partial sums a backward left for the optimizer (added up on the way: bit-identical to the finishing launch for tzr_mlp2_bwd's
+    rows and the weight-gradient slices, equal up to fp32 rounding for rows tzr_colsum_finish_kernel would finish) -- the flat
+    buffer of the sharded step's dense all-reduce.  None: not a case for it (the caller concatenates)."""
     grads = list(grads)
-    if not grads or len(grads) > 32 or any(g.dtype != torch.float32 or not g.is_contiguous() for g in grads):
+    if not grads or any(g.dtype != torch.float32 or not g.is_contiguous() for g in grads) or _one_launch(grads) < len(grads):
         return None
-    if sum(1 for g in grads if _PENDING.get(g.data_ptr(), ("",))[0] == "wgrad") > 1:
-        return None
-    total = sum(g.numel() for g in grads)
-    flat = torch.empty(total, dtype=torch.float32, device=grads[0].device)
-    rows, o = [], 0
-    for g in grads:
-        rows.append((None, flat[o:o + g.numel()], None, None, None, g))
-        o += g.numel()
+    sizes = [g.numel() for g in grads]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=grads[0].device)
+    rows = [_Row(None, part, None, None, None, key=g) for part, g in zip(flat.split(sizes), grads)]
     tab, src, wg, keep = _adam_tables(rows)
-    if any(e[3] == _GENERATION[0] for e in _PENDING.values()):
+    if any(e.generation == _GENERATION[0] for e in _PENDING.values()):
         # a backward of THIS step left partial sums that none of `grads` claims: autograd handed its tensor on as a copy (another
         # address) -- the copy is unwritten memory.  Never silently.
         raise RuntimeError("pack_gradients: a gradient left as partial sums (FusedDenseAdam(fuse_finish=True)) is not among the tensors "
@@ -571,7 +580,7 @@ class _Mlp2Fn(torch.autograd.Function):
                                             _lib.stream_ptr(xs.device)), "tzr_mlp2_bwd_parts")
             col = 0
             for t in (dWb, dbb, dWa, dba):
-                _PENDING[t.data_ptr()] = ("rows", (ws,), (G.value, P.value, col), _GENERATION[0], _owner_id(ctx.param_refs), tuple(id(q) for q in ctx.param_refs))
+                _defer(t, "rows", (ws,), (G.value, P.value, col), ctx.param_refs)
                 col += t.numel()
             return None, dWa, dba, dWb, dbb
         _lib.check(L.tzr_mlp2_bwd(_lib.ptr(g), g.stride(0), _lib.ptr(hb), hb.stride(0), _lib.ptr(ha), ha.stride(0), _lib.ptr(xs),
@@ -837,7 +846,7 @@ def interaction_top_wgrad(dense: torch.Tensor, sparse: torch.Tensor, D: int, g1:
         _lib.check(L.tzr_dot_interaction_top_wgrad_parts(
             _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(g1), g1.stride(0), H,
             _lib.ptr(scale), _lib.ptr(ws), ws.numel(), C.byref(blob), _lib.stream_ptr(sparse.device)), "tzr_dot_interaction_top_wgrad_parts")
-        _PENDING[dW.data_ptr()] = ("wgrad", (ws, scale), blob, _GENERATION[0], _owner_id(defer_for), tuple(id(q) for q in defer_for))
+        _defer(dW, "wgrad", (ws, scale), blob, defer_for)
         return dW
     _lib.check(L.tzr_dot_interaction_top_wgrad(
         _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(g1), g1.stride(0), H,
@@ -905,8 +914,7 @@ def _register_fused(opt, fuse_finish: bool) -> torch.device:
 
 
 def _zero_grad(params, set_to_none: bool = True) -> None:
-    for p in params:
-        _DEFERRED.pop(id(p), None)
+    _forget({id(p) for p in params if _DEFERRED.pop(id(p), None) is not None})  # (a backward that is not stepped: forgotten whole)
     for p in params:
         if set_to_none:
             p.grad = None
@@ -924,13 +932,12 @@ def _check_lr_synced(opt, stale: bool) -> None:
 
 
 def _launch_fused(rows, tables, launch) -> None:
-    """`rows` in launches of <= 32: tables(rows) -> (tab, src, wg, keep), launch(tab, src, wg)"""
+    """`rows` (_Row, key = grad) in launches of <= 32: tables(rows) -> (tab, src, wg, keep), launch(tab, src, wg)"""
     for base in range(0, len(rows), 32):
         part = rows[base:base + 32]
+        grads = [r.grad for r in part]
+        materialize_pending(grads[_one_launch(grads):])  # (from a second slice set on: written out first)
         tab, src, wg, keep = tables(part)
-        if any(src[i].kind < 0 for i in range(len(tab))):  # (a second slice set in one launch: written out first)
-            materialize_pending([r[1] for r in part])
-            tab, src, wg, keep = tables(part)
         launch(tab, src, wg)
         del keep
 
@@ -944,7 +951,7 @@ def _after_fused_step(opt, packed_written=()) -> None:
             e = _W1_PACKED.get(p.data_ptr())
             if e is not None and e not in packed_written:
                 e.version = -1
-    if any(len(e) > 4 and e[4] == id(opt) and e[3] == _GENERATION[0] for e in _PENDING.values()):
+    if any(e.owner == id(opt) and e.generation == _GENERATION[0] for e in _PENDING.values()):
         # a backward left a gradient of one of THIS optimizer's parameters as partial sums and the tensor that reached `.grad` is
         # another one (autograd copied it): its parameter was just stepped with unwritten memory.  Never silently.
         raise RuntimeError(f"{name}(fuse_finish=True): a gradient left as partial sums did not reach its parameter's .grad "
@@ -952,7 +959,7 @@ def _after_fused_step(opt, packed_written=()) -> None:
                            "fuse_finish=False for this model")
     if _PENDING:  # (entries of tensors that are gone -- a gradient autograd dropped: unclaimed two steps later)
         _GENERATION[0] += 1
-        for ptr in [q for q, e in _PENDING.items() if e[3] < _GENERATION[0] - 2]:
+        for ptr in [q for q, e in _PENDING.items() if e.generation < _GENERATION[0] - 2]:
             del _PENDING[ptr]
 
 
@@ -995,14 +1002,7 @@ class FusedDenseAdam:
     def step(self, grads: Optional[List[torch.Tensor]] = None) -> None:
         g = self.param_groups[0]
         _check_lr_synced(self, g["lr"] != self._lr_host)
-        rows = []
-        for i, p in enumerate(self.params):
-            gr = p.grad if grads is None else grads[i]
-            if gr is None:
-                continue
-            if gr.dtype != torch.float32 or not gr.is_contiguous():
-                gr = gr.contiguous().float()
-            rows.append((p, gr, self.exp_avg[i], self.exp_avg_sq[i], self._state[i]))
+        rows = [_Row(self.params[i].data, gr, self.exp_avg[i], self.exp_avg_sq[i], self._state[i]) for i, gr in _step_grads(self.params, grads)]
         if not rows:
             return
         b1, b2 = g["betas"]
@@ -1022,7 +1022,7 @@ class FusedDenseAdam:
                 tab, src, len(tab), C.byref(wg) if wg is not None else None, _lib.ptr(self._lr_dev), g["lr"], b1, b2, g["eps"],
                 g["weight_decay"], C.byref(w1) if w1 is not None else None, _lib.stream_ptr(self.device)), "tzr_dense_adam_fused_w1")
 
-        _launch_fused([(p.data, gr, m, v, st) for p, gr, m, v, st in rows], _adam_tables, launch)
+        _launch_fused(rows, _adam_tables, launch)
         for e in written:  # the launch wrote W1 through its address: move its version on, so that the recorded one means something
             torch.autograd.graph.increment_version(e.ref())
             e.version = e.ref()._version

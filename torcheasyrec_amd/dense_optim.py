@@ -95,17 +95,12 @@ class FusedDenseOptimizer:
     def step(self, grads: Optional[List[torch.Tensor]] = None) -> None:
         dense._check_lr_synced(self, any(g["lr"] != h for g, h in zip(self.param_groups, self._lr_host)))
         rows = []
-        for i, p in enumerate(self.params):
-            gr = p.grad if grads is None else grads[i]
-            if gr is None:
-                continue
-            if gr.dtype != torch.float32 or not gr.is_contiguous():
-                gr = gr.contiguous().float()
+        for i, gr in dense._step_grads(self.params, grads):
             g = self.param_groups[self._group_of[i]]
             if _n_states(g) != len(self.state[i]):
                 raise RuntimeError("FusedDenseOptimizer: a group's momentum was switched on or off after construction")
             st = list(self.state[i].values()) + [None, None]
-            rows.append((p.data, gr, st[0], st[1], self._state[i], gr, self._group_of[i]))
+            rows.append(dense._Row(self.params[i].data, gr, st[0], st[1], self._state[i], group=self._group_of[i]))
         if not rows:
             return
         _lib.check_device(self._lr_dev)
