@@ -51,7 +51,7 @@ def run(iters, B=65536, seed=0, variant=0):
         if variant in (1, 3):
             torch.cuda.synchronize()
         plan = getattr(kjt, "_tzr_plan", None)
-        ws = plan[2] if plan is not None else None
+        ws = plan.ws if plan is not None else None
         (out * g).sum().backward()
         torch.cuda.synchronize()
         if ws is not None:

@@ -697,6 +697,41 @@ def test_forward_launch_that_carries_the_plan(dev, kind, B, monkeypatch):
         L.tzr_tune(b"fwd_plan", 1)
 
 
+def test_plan_left_by_a_forward_never_reaches_the_backward_of_refreshed_ids(dev, monkeypatch):
+    """A forward carries the plan and its backward never runs; the ids are refreshed IN PLACE (a static input buffer); the next
+    forward of the same object does NOT carry a plan.  Its backward must plan the fresh ids, not apply through the plan of the
+    old ones: every table and state equals a collection that saw only the fresh batch."""
+    from torcheasyrec_amd import _lib
+
+    L = _lib.lib()
+    monkeypatch.setenv("TZR_BWD_PLAN", "cells")
+    assert L.tzr_tune(b"bwd_direct", -1) == 0 and L.tzr_tune(b"fwd_plan", 2) == 0
+    try:
+        opt = SparseOptimizerConfig(kind="adagrad", lr=0.05)
+        keys, rows, B = ["c0", "c1", "c2", "c3"], [5000, 300, 3, 4], 300
+        cfgs, _ = _make_tables(SPEC_CRITEO_SMALL)
+        e1 = EmbeddingBagCollection(cfgs, device=dev, optimizer=opt)
+        e2 = EmbeddingBagCollection(cfgs, device=dev, optimizer=opt)
+        rng = np.random.default_rng(5)
+        k1 = _make_kjt(keys, rows, B, rng).to(dev)
+        fresh = _make_kjt(keys, rows, B, rng).to(dev)
+        e1(k1)  # (plan made, never consumed)
+        assert e1.forward_plans == 1 and k1._tzr_plan is not None
+        k1.values().copy_(fresh.values())
+        e1.forward_plan = False  # (as a demotion in "auto" or a declined fused launch: this forward goes out on its own)
+        g = torch.from_numpy(rng.standard_normal((B, 64)).astype(np.float32)).to(dev)
+        (e1(k1).values() * g).sum().backward()
+        (e2(fresh).values() * g).sum().backward()
+        assert e1.forward_plans == 1
+        for n in e1.table_weights():
+            assert torch.equal(e1.table_weights()[n].cpu(), e2.table_weights()[n].cpu()), n
+        for n in e1.table_states():
+            assert torch.equal(e1.table_states()[n].cpu(), e2.table_states()[n].cpu()), n
+    finally:
+        L.tzr_tune(b"bwd_direct", 0)
+        L.tzr_tune(b"fwd_plan", 1)
+
+
 def test_forward_that_carries_the_plan_with_a_frozen_table_and_what_it_declines(dev, monkeypatch):
     """A frozen table: the forward reads it (forward descriptors), the plan in the same launch leaves it out (backward descriptors) --
     same bits as the two launches.  Per-sample weights, half-precision tables, jagged bags: the forward goes out on its own."""

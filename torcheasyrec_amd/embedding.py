@@ -17,7 +17,6 @@ KeyedTensor`` with keys in table-then-feature order).  Differences by design:
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 from dataclasses import dataclass, field
@@ -29,6 +28,7 @@ from torch import nn
 
 from . import _lib, opt_kinds
 from .sparse import KeyedJaggedTensor, KeyedTensor
+from .sparse_bwd import SparseBackward, cells_geometry, direct_supported, grad_dsts
 
 
 @dataclass
@@ -262,6 +262,19 @@ class _CellsGeo:
         self.demoted = False
 
 
+@dataclass(slots=True)
+class _Plan:
+    """The backward index plan of one batch, kept on the batch object (`kjt._tzr_plan`; None: no plan) between the launch that
+    made it and the backward that applies it (`EmbeddingBagCollection._claim`)."""
+
+    owner: int                           # id() of the collection that planned
+    dst_names: Tuple[str, ...]
+    ws: torch.Tensor                     # the workspace that holds the plan
+    ready: Optional["torch.cuda.Event"]  # recorded behind a plan made on the side stream, else None
+    geo: Optional[_CellsGeo]             # the cells plan's geometry; None: the exact plan
+    origin: str                          # "forward": carried by the forward's launch; "caller": plan_backward / plan_backward_async
+
+
 def mask_frozen_descriptors(tables: np.ndarray, feats: np.ndarray, frozen: Sequence[bool]):
     """Backward twins of (TzrTable[], TzrFeature[]) in which the lookups of frozen tables
     (`trainable: false`, tzrec/features/feature.py:629, models/model.py:162-201) are marked "not owned"
@@ -369,6 +382,9 @@ class EmbeddingBagCollection(nn.Module):
         # default id): the one-launch backward then lets all of a table's workgroups sum such a row (TZR_GRAD_HOT_ROWS,
         # include/tzrec_hip.h); zch.ManagedCollisionEmbeddingBagCollection sets it
         self.expect_hot_rows = False
+        # (max rows, max dim) over the tables: every backward call takes them, the configs never change
+        self._dims = (max(c.num_embeddings for c in self._configs), max(c.embedding_dim for c in self._configs))
+        self._direct_ws: Dict[int, torch.Tensor] = {}  # n_positions -> the one-launch backward's persistent workspace
         # Which index plan a batch of one id per bag takes (batches with jagged bags always take the exact one):
         #   "exact"  tzr_pooled_bwd_plan: four launches, any id distribution at full speed (heavy buckets, hot rows);
         #   "cells"  tzr_pooled_bwd_cells_plan: ONE launch; unit sizes are expectations for evenly drawn ids, a unit that holds
@@ -385,19 +401,8 @@ class EmbeddingBagCollection(nn.Module):
     def _cells_geometry(self, meta: _Meta, B: int) -> Optional[_CellsGeo]:
         if B in meta.cells:
             return meta.cells[B]
-        L = _lib.lib()
-        _, max_dim = self._bwd_dims()
-        info = (C.c_int64 * 8)()
-        tp, fp = meta.bwd_tables_np.ctypes.data, meta.bwd_feats_np.ctypes.data
-        rc = L.tzr_bwd_cells_geometry(tp, len(self._configs), fp, len(self._lookups), B, max_dim, None, 0, info)
-        geo = None
-        if rc == _lib.TZR_OK:
-            img = np.zeros(int(info[0]), dtype=np.uint8)
-            _lib.check(L.tzr_bwd_cells_geometry(tp, len(self._configs), fp, len(self._lookups), B, max_dim, img.ctypes.data, img.nbytes,
-                                                info), "tzr_bwd_cells_geometry")
-            geo = _CellsGeo(img, info, self._device)
-        elif rc != -4:  # (TZR_ERR_UNSUPPORTED: simply not a case for the cells plan)
-            _lib.check(rc, "tzr_bwd_cells_geometry")
+        made = cells_geometry(meta.bwd_tables_np, meta.bwd_feats_np, B, self._bwd_dims()[1])
+        geo = None if made is None else _CellsGeo(*made, self._device)
         meta.cells[B] = geo
         return geo
 
@@ -582,20 +587,21 @@ class EmbeddingBagCollection(nn.Module):
         offsets = None if uniform else kjt.offsets()
         return uniform, offsets
 
-    def _forward_carries_plan(self, kjt: KeyedJaggedTensor, meta: _Meta) -> Optional["_CellsGeo"]:
-        """The cells geometry when this batch's forward can carry the backward's index plan in its launch
+    def _forward_carries_plan(self, kjt: KeyedJaggedTensor, meta: _Meta) -> Optional[Tuple["_CellsGeo", SparseBackward]]:
+        """The cells geometry and the backward to plan when this batch's forward can carry the backward's index plan in its launch
         (tzr_pooled_fwd_cells_plan: one id per bag, fp32 tables, no per-sample weights, a batch the cells plan takes)."""
         if not self.forward_plan or self._has_fp16 or kjt.uniform_length() != 1 or kjt.weights_or_none() is not None:
             return None
-        cached = getattr(kjt, "_tzr_plan", None)
-        if cached is not None and not (len(cached) > 5 and cached[5] == "forward"):
+        left = getattr(kjt, "_tzr_plan", None)
+        if left is not None and left.origin == "caller":
             return None  # planned ahead by the caller (plan_backward / plan_backward_async): that plan is the batch's
-        # (a plan left by an earlier forward of this object whose backward never ran is dropped: the ids may have been refreshed in place)
-        if self.backward_is_direct(kjt):
+        p = self._problem(kjt, meta)
+        if p.direct_supported():
             return None
         if not _lib.lib().tzr_pooled_fwd_cells_plan_supported(len(meta.slots_np), kjt.stride()):
             return None
-        return self._cells_for(kjt, meta)
+        geo = self._cells_for(kjt, meta)
+        return None if geo is None else (geo, p)
 
     def _launch_forward(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...], with_plan: bool = False) -> List[torch.Tensor]:
         """`with_plan`: a backward of this batch follows (the autograd node's forward): the launch may carry its index plan."""
@@ -605,29 +611,31 @@ class EmbeddingBagCollection(nn.Module):
         uniform, offsets = self._kjt_args(kjt)
         widths = [sum(self._out_dim[k] for k in ks) for _, ks in layout]
         outs = [torch.empty(B, w, dtype=torch.float32, device=self._device) for w in widths]
-        dsts = (_lib.TzrDst * len(outs))()
-        for i, o in enumerate(outs):
-            dsts[i].ptr = _lib.ptr(o)
-            dsts[i].stride = o.stride(0)
-        geo = self._forward_carries_plan(kjt, meta) if with_plan else None
-        if geo is not None:
-            L = _lib.lib()
-            N = kjt.values().numel()
-            max_dim = self._bwd_dims()[1]
-            ws = _lib.workspace(L.tzr_pooled_bwd_workspace(N, self._n_positions(kjt), len(self._lookups), len(self._configs), B, max_dim),
-                                self._device)
+        dsts = grad_dsts(outs)
+        carried = None
+        if with_plan:
+            left = getattr(kjt, "_tzr_plan", None)
+            if left is not None and left.origin == "forward" and left.owner == id(self):
+                # left by an earlier forward of this object whose backward never ran: the ids may have been refreshed in place
+                # since.  Dropped HERE, before this forward decides anything: whichever way it goes, its backward plans anew
+                kjt._tzr_plan = None  # type: ignore[attr-defined]
+            carried = self._forward_carries_plan(kjt, meta)
+        if carried is not None:
+            geo, p = carried
+            ws = _lib.workspace(p.plan_bytes(), self._device)
             ev = self._timers.start("fwd+plan") if self._timers is not None else None
-            rc = L.tzr_pooled_fwd_cells_plan(
+            # the forward's half as tzr_pooled_fwd takes it, the plan's half (tables, lookups, ids, sizes) from `p`
+            rc = _lib.lib().tzr_pooled_fwd_cells_plan(
                 _lib.ptr(meta.d_tables), _lib.ptr(meta.d_feats), len(self._lookups), _lib.ptr(meta.d_slots), len(meta.slots_np), dsts,
-                len(outs), _lib.ptr(meta.d_bwd_tables), len(self._configs), _lib.ptr(meta.d_bwd_feats), len(self._lookups), max_dim,
-                _lib.ptr(kjt.values()), N, B, geo.h_ptr, _lib.ptr(geo.d_img), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device))
-            if rc != -4:  # (TZR_ERR_UNSUPPORTED: nothing was launched -- the two calls, as below)
+                len(outs), _lib.ptr(p.d_tables), p.n_tables, _lib.ptr(p.d_feats), p.n_feats, p.max_dim,
+                _lib.ptr(p.values), p.n_values, p.B, geo.h_ptr, _lib.ptr(geo.d_img), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device))
+            if rc != _lib.TZR_ERR_UNSUPPORTED:  # (else nothing was launched -- the two calls, as below)
                 if ev is not None:
                     ev.record()
                 _lib.check(rc, "tzr_pooled_fwd_cells_plan")
                 if self._device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
                     ws.record_stream(torch.cuda.current_stream(self._device))
-                kjt._tzr_plan = (id(self), dst_names, ws, None, geo, "forward")  # type: ignore[attr-defined]
+                kjt._tzr_plan = _Plan(id(self), dst_names, ws, None, geo, "forward")  # type: ignore[attr-defined]
                 self.forward_plans += 1
                 return outs
             if self._timers is not None:
@@ -645,7 +653,7 @@ class EmbeddingBagCollection(nn.Module):
         return outs
 
     def _bwd_dims(self) -> Tuple[int, int]:
-        return (max(c.num_embeddings for c in self._configs), max(c.embedding_dim for c in self._configs))
+        return self._dims
 
     def _n_positions(self, kjt: KeyedJaggedTensor) -> int:
         """Capacity of the backward plan's table-major position space: every lookup (key -> table)
@@ -657,23 +665,28 @@ class EmbeddingBagCollection(nn.Module):
             mult[lk.key] = mult.get(lk.key, 0) + 1
         return kjt.values().numel() * max(mult.values())
 
-    def _direct_workspace(self, n_positions: int) -> torch.Tensor:
+    def _problem(self, kjt: KeyedJaggedTensor, meta: _Meta) -> SparseBackward:
+        """The fused backward of this batch, on the backward descriptors of `meta`"""
+        _, offsets = self._kjt_args(kjt)
+        max_rows, max_dim = self._bwd_dims()
+        values = kjt.values()
+        return SparseBackward(self._device, meta.d_bwd_tables, meta.d_bwd_feats, len(self._configs), len(self._lookups), meta.n_keys,
+                              max_rows, max_dim, values, offsets, kjt.weights_or_none(), values.numel(), self._n_positions(kjt),
+                              kjt.stride())
+
+    def _direct_workspace(self, p: SparseBackward) -> torch.Tensor:
         """The persistent workspace of tzr_pooled_bwd_direct (zeroed once: its arrival counters reset themselves; the
         launches of one collection run in stream order, so one buffer per size serves them all)."""
-        cache = self.__dict__.setdefault("_direct_ws", {})
-        ws = cache.get(n_positions)
+        ws = self._direct_ws.get(p.n_positions)
         if ws is None:
-            _, max_dim = self._bwd_dims()
             # (never evicted: captured hipGraphs replay launches that hold these addresses)
-            ws = cache[n_positions] = _lib.zeroed_workspace(
-                _lib.lib().tzr_pooled_bwd_direct_workspace(n_positions, len(self._configs), max_dim), self._device)
+            ws = self._direct_ws[p.n_positions] = _lib.zeroed_workspace(p.direct_bytes(), self._device)
         return ws
 
     def backward_is_direct(self, kjt: KeyedJaggedTensor) -> bool:
         """Small batches skip the index plan: ONE launch sorts and applies (tzr_pooled_bwd_direct,
         csrc/pooled_bwd_direct.hip) -- when the library takes the shape and the size (tzr_tune "bwd_direct")."""
-        return bool(_lib.lib().tzr_pooled_bwd_direct_supported(self._n_positions(kjt), len(self._lookups), len(self._configs),
-                                                               1 if kjt.uniform_length() == 1 else 0, 0))
+        return direct_supported(self._n_positions(kjt), len(self._lookups), len(self._configs), kjt.uniform_length() == 1)
 
     def backward_form(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...] = ("__all__",)) -> str:
         """which form the fused backward of this batch takes right now: "direct" (one launch, no plan), "cells" (one-launch plan +
@@ -683,39 +696,31 @@ class EmbeddingBagCollection(nn.Module):
         meta = self._meta(kjt.keys(), self._layout_for(dst_names))
         return "cells" if self._cells_for(kjt, meta) is not None else "exact"
 
+    def _plan(self, kjt: KeyedJaggedTensor, meta: _Meta, p: SparseBackward) -> Tuple[torch.Tensor, Optional[_CellsGeo]]:
+        """K6 on the current stream: the cells plan when the batch takes it, else the exact one.  Returns (workspace, geometry)."""
+        ws = _lib.workspace(p.plan_bytes(), self._device)
+        geo = self._cells_for(kjt, meta)
+        ev = self._timers.start("plan") if self._timers is not None else None
+        if geo is not None:
+            p.cells_plan(geo, ws)
+        else:
+            p.plan(ws)
+        if ev is not None:
+            ev.record()
+        if self._device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
+            ws.record_stream(torch.cuda.current_stream(self._device))
+        return ws, geo
+
     def plan_backward(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...] = ("__all__",)) -> Optional[torch.Tensor]:
         """K6: build the backward index plan for this batch (depends on ids only, so callers may run
         it early on a side stream).  Returns the workspace holding the plan -- None for a batch whose
         backward needs none (`backward_is_direct`)."""
-        if self.backward_is_direct(kjt):
+        meta = self._meta(kjt.keys(), self._layout_for(dst_names))
+        p = self._problem(kjt, meta)
+        if p.direct_supported():
             return None
-        layout = self._layout_for(dst_names)
-        meta = self._meta(kjt.keys(), layout)
-        L = _lib.lib()
-        B, N = kjt.stride(), kjt.values().numel()
-        uniform, offsets = self._kjt_args(kjt)
-        max_rows, max_dim = self._bwd_dims()
-        NP = self._n_positions(kjt)
-        nbytes = L.tzr_pooled_bwd_workspace(N, NP, len(self._lookups), len(self._configs), B, max_dim)
-        ws = _lib.workspace(nbytes, self._device)
-        geo = self._cells_for(kjt, meta)
-        ev = self._timers.start("plan") if self._timers is not None else None
-        if geo is not None:
-            rc = L.tzr_pooled_bwd_cells_plan(
-                _lib.ptr(meta.d_bwd_tables), len(self._configs), _lib.ptr(meta.d_bwd_feats), len(self._lookups), max_dim,
-                _lib.ptr(kjt.values()), N, B, geo.h_ptr, _lib.ptr(geo.d_img), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device))
-        else:
-            rc = L.tzr_pooled_bwd_plan(
-                _lib.ptr(meta.d_bwd_tables), len(self._configs), _lib.ptr(meta.d_bwd_feats), len(self._lookups),
-                meta.n_keys, max_rows, max_dim, _lib.ptr(kjt.values()), _lib.ptr(offsets), N, NP, B,
-                1 if uniform else 0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device),
-            )
-        if ev is not None:
-            ev.record()
-        _lib.check(rc, "tzr_pooled_bwd_cells_plan" if geo is not None else "tzr_pooled_bwd_plan")
-        if self._device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            ws.record_stream(torch.cuda.current_stream(self._device))
-        kjt._tzr_plan = (id(self), dst_names, ws, None, geo)  # type: ignore[attr-defined]
+        ws, geo = self._plan(kjt, meta, p)
+        kjt._tzr_plan = _Plan(id(self), dst_names, ws, None, geo, "caller")  # type: ignore[attr-defined]
         return ws
 
     def plan_backward_async(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...] = ("__all__",)) -> None:
@@ -730,74 +735,63 @@ class EmbeddingBagCollection(nn.Module):
         cur = torch.cuda.current_stream(self._device)
         self._side_stream.wait_stream(cur)  # ids / descriptors were produced on the current stream
         with torch.cuda.stream(self._side_stream):
-            ws = self.plan_backward(kjt, dst_names)
+            self.plan_backward(kjt, dst_names)
             ev = torch.cuda.Event()
             ev.record()
         if not torch.cuda.is_current_stream_capturing():  # (a captured step owns its buffers for the graph's life)
             for t in (kjt.values(), kjt.offsets_or_none()):
                 if t is not None:
                     t.record_stream(self._side_stream)
-        kjt._tzr_plan = (id(self), dst_names, ws, ev, kjt._tzr_plan[4])  # type: ignore[attr-defined]
+        kjt._tzr_plan.ready = ev  # type: ignore[attr-defined]
+
+    def _claim(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...], use: bool = True) -> Optional[_Plan]:
+        """Take the batch's plan.  The attribute is cleared whatever it held; the record comes back only when this collection made
+        it for these destinations -- and the current stream waits for a plan made on the side stream.  `use` False: the backward
+        needs no plan (the one-launch form): cleared, nothing waited for."""
+        plan = getattr(kjt, "_tzr_plan", None)
+        kjt._tzr_plan = None  # type: ignore[attr-defined]
+        if not use or plan is None or plan.owner != id(self) or plan.dst_names != dst_names:
+            return None
+        if plan.ready is not None:
+            cur = torch.cuda.current_stream(self._device)
+            cur.wait_event(plan.ready)
+            if not torch.cuda.is_current_stream_capturing():
+                plan.ws.record_stream(cur)
+        return plan
 
     def _launch_backward(self, kjt: KeyedJaggedTensor, dst_names: Tuple[str, ...], grads) -> None:
         if self.fused_optimizer is None:
             return  # frozen tables
-        direct = self.backward_is_direct(kjt)
-        cached = getattr(kjt, "_tzr_plan", None)
-        geo = None
-        if direct:
-            ws = None
-        elif cached is not None and cached[0] == id(self) and cached[1] == dst_names:
-            ws, geo = cached[2], cached[4]
-            if cached[3] is not None:
-                torch.cuda.current_stream(self._device).wait_event(cached[3])
-                if not torch.cuda.is_current_stream_capturing():
-                    ws.record_stream(torch.cuda.current_stream(self._device))
-        else:
-            ws = self.plan_backward(kjt, dst_names)
-            geo = kjt._tzr_plan[4]  # type: ignore[attr-defined]
         layout = self._layout_for(dst_names)
         meta = self._meta(kjt.keys(), layout)
-        B, N = kjt.stride(), kjt.values().numel()
-        uniform, offsets = self._kjt_args(kjt)
-        max_rows, max_dim = self._bwd_dims()
+        p = self._problem(kjt, meta)
+        direct = p.direct_supported()
+        plan = self._claim(kjt, dst_names, use=not direct)
+        if plan is not None:
+            ws, geo = plan.ws, plan.geo
+        else:
+            ws, geo = (None, None) if direct else self._plan(kjt, meta, p)
         widths = [sum(self._out_dim[k] for k in ks) for _, ks in layout]
         gl = []
         for g, w in zip(grads, widths):
             if g is None:
-                g = torch.zeros(B, w, dtype=torch.float32, device=self._device)
+                g = torch.zeros(p.B, w, dtype=torch.float32, device=self._device)
             g = g.contiguous()
             if g.dtype != torch.float32:
                 g = g.float()
             gl.append(g)
-        gd = (_lib.TzrDst * len(gl))()
-        for i, g in enumerate(gl):
-            gd[i].ptr = _lib.ptr(g)
-            gd[i].stride = g.stride(0)
+        gd = grad_dsts(gl)
         self.fused_optimizer.begin_step(self._device)
         opt = self.fused_optimizer.optim_struct(self._device)
         ev = self._timers.start("apply") if self._timers is not None else None
         if direct:
-            dws = self._direct_workspace(self._n_positions(kjt))
-            rc = _lib.lib().tzr_pooled_bwd_direct(
-                _lib.ptr(meta.d_bwd_tables), len(self._configs), _lib.ptr(meta.d_bwd_feats), len(self._lookups), max_rows, max_dim,
-                _lib.ptr(kjt.values()), _lib.ptr(offsets), _lib.ptr(kjt.weights_or_none()), N, self._n_positions(kjt), B,
-                1 if uniform else 0, _lib.GRAD_HOT_ROWS if self.expect_hot_rows else 0, gd, len(gl), opt, _lib.ptr(dws), dws.numel(),
-                _lib.stream_ptr(self._device))
+            p.direct(self._direct_workspace(p), gd, opt, hot_rows=self.expect_hot_rows)
         elif geo is not None:
-            rc = _lib.lib().tzr_pooled_bwd_cells_apply(
-                _lib.ptr(meta.d_bwd_tables), _lib.ptr(meta.d_bwd_feats), len(self._lookups), len(self._configs), max_dim, None, N, B, 0,
-                gd, len(gl), opt, geo.h_ptr, _lib.ptr(geo.d_img), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device))
+            p.cells_apply(geo, ws, gd, opt)
         else:
-            rc = _lib.lib().tzr_pooled_bwd_apply(
-                _lib.ptr(meta.d_bwd_tables), _lib.ptr(meta.d_bwd_feats), len(self._lookups), len(self._configs),
-                max_dim, _lib.ptr(offsets), _lib.ptr(kjt.weights_or_none()), N, self._n_positions(kjt), B,
-                1 if uniform else 0, 0,
-                gd, len(gl), opt, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self._device),
-            )
+            p.apply(ws, gd, opt)
         if ev is not None:
             ev.record()
-        _lib.check(rc, "tzr_pooled_bwd_direct" if direct else ("tzr_pooled_bwd_cells_apply" if geo is not None else "tzr_pooled_bwd_apply"))
         if geo is not None and self.plan_mode == "auto":
             # the overflow word follows the apply to the host (8 bytes, no wait): `_cells_for` looks at it before the next plan
             geo.launches += 1
@@ -805,7 +799,6 @@ class EmbeddingBagCollection(nn.Module):
             if self._device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
                 geo.copied = torch.cuda.Event()
                 geo.copied.record(torch.cuda.current_stream(self._device))
-        kjt._tzr_plan = None  # type: ignore[attr-defined]
 
     def register_post_lookup_tracker_fn(self, fn) -> None:
         """torchrec's hook of the same name, which the reference's ModelDeltaTracker registers on every

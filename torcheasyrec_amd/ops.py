@@ -25,6 +25,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .sparse_bwd import SparseBackward, grad_dsts
 
 _NS = "tzrec_hip"
 
@@ -183,13 +184,6 @@ def _(block_sizes, rank_offsets, lengths, offsets, values, weights, stride, worl
 
 
 # ---- pooled lookup + fused backward ----------------------------------------------------------------
-def _dsts(tensors: List[Tensor]):
-    arr = (_lib.TzrDst * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i].ptr, arr[i].stride = _lib.ptr(t), t.stride(0)
-    return arr
-
-
 @torch.library.custom_op(f"{_NS}::pooled_fwd", mutates_args=())
 def pooled_fwd(tables: List[Tensor], d_tables: Tensor, d_feats: Tensor, d_slots: Tensor, values: Tensor, offsets: Optional[Tensor],
                weights: Optional[Tensor], stride: int, dst_widths: List[int], mixed_dtype: bool) -> List[Tensor]:
@@ -200,7 +194,7 @@ def pooled_fwd(tables: List[Tensor], d_tables: Tensor, d_feats: Tensor, d_slots:
     outs = [torch.empty(B, w, dtype=torch.float32, device=dev) for w in dst_widths]
     rc = _lib.lib().tzr_pooled_fwd_ex(_lib.ptr(d_tables), _lib.ptr(d_feats), d_feats.numel() // _lib.FEATURE_DT.itemsize, _lib.ptr(d_slots),
                                       d_slots.numel() // _lib.SLOT_DT.itemsize, _lib.ptr(values), _lib.ptr(offsets), _lib.ptr(weights), B,
-                                      _dsts(outs), len(outs), 1 if offsets is None else 0, _lib.FWD_MIXED_DTYPE if mixed_dtype else 0,
+                                      grad_dsts(outs), len(outs), 1 if offsets is None else 0, _lib.FWD_MIXED_DTYPE if mixed_dtype else 0,
                                       _lib.stream_ptr(dev))
     _lib.check(rc, "tzr_pooled_fwd")
     return outs
@@ -212,26 +206,21 @@ def _(tables, d_tables, d_feats, d_slots, values, offsets, weights, stride, dst_
 
 
 def _pooled_bwd(kind: int, tables, states, d_tables, d_feats, values, offsets, weights, grads, lr, stride, n_keys, max_rows, eps):
-    dev, L = values.device, _lib.lib()
-    B, N = stride, values.numel()
+    dev, B, N = values.device, stride, values.numel()
     F, T = d_feats.numel() // _lib.FEATURE_DT.itemsize, d_tables.numel() // _lib.TABLE_DT.itemsize
-    uniform = offsets is None
     # capacity of the table-major position space.  Ragged bags: a key read through k tables contributes its ids k times
     # (EmbeddingBagCollection._n_positions knows k from its lookups: N * max k); the op sees only device descriptors, so it
     # takes the bound that holds for every sharing pattern, N * F -- F times the module's workspace when no key is shared
     # (ADVICE round 2 suggested N: too small as soon as two tables read one key).
-    NP = F * B if uniform else N * F
-    max_dim = max(int(t.shape[1]) for t in tables)
-    ws = _lib.workspace(L.tzr_pooled_bwd_workspace(N, NP, F, T, B, max_dim), dev)
-    rc = L.tzr_pooled_bwd_plan(_lib.ptr(d_tables), T, _lib.ptr(d_feats), F, n_keys, max_rows, max_dim, _lib.ptr(values), _lib.ptr(offsets),
-                               N, NP, B, 1 if uniform else 0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "tzr_pooled_bwd_plan")
+    NP = F * B if offsets is None else N * F
+    p = SparseBackward(dev, d_tables, d_feats, T, F, n_keys, max_rows, max(int(t.shape[1]) for t in tables), values, offsets, weights,
+                       N, NP, B)
+    ws = _lib.workspace(p.plan_bytes(), dev)
+    p.plan(ws)
     opt = _lib.TzrSparseOptim()
     opt.kind, opt.weight_decay_mode, opt.d_lr, opt.eps = kind, _lib.WD_NONE, _lib.ptr(lr), eps
     gl = [g.contiguous() for g in grads]
-    rc = L.tzr_pooled_bwd_apply(_lib.ptr(d_tables), _lib.ptr(d_feats), F, T, max_dim, _lib.ptr(offsets), _lib.ptr(weights), N, NP, B,
-                                1 if uniform else 0, 0, _dsts(gl), len(gl), opt, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "tzr_pooled_bwd_apply")
+    p.apply(ws, grad_dsts(gl), opt)
 
 
 @torch.library.custom_op(f"{_NS}::pooled_bwd_adagrad", mutates_args=("tables", "states"))

@@ -23,6 +23,7 @@ from torch import nn
 from . import _lib
 from .dlrm import MLP
 from .embedding import EmbeddingBagCollection, EmbeddingBagConfig, SparseOptimizerConfig
+from .sparse_bwd import SparseBackward, grad_dsts
 from .sparse import JaggedTensor, KeyedJaggedTensor  # noqa: F401  (JaggedTensor re-exported)
 
 
@@ -199,24 +200,18 @@ class EmbeddingCollection(nn.Module):
         if self.fused_optimizer is None:
             return
         m = self._meta(kjt.keys())
-        L = _lib.lib()
         N = kjt.values().numel()
         if N == 0:
             return
         g = g.contiguous().float()
-        ks = kjt._tzr_key_start  # type: ignore[attr-defined]
-        dev, stream = self._device, _lib.stream_ptr(self._device)
-        ws = _lib.workspace(L.tzr_pooled_bwd_workspace(N, N, m["K"], m["T"], 1, self.dim), dev)
-        _lib.check(L.tzr_pooled_bwd_plan(_lib.ptr(m["d_tables"]), m["T"], _lib.ptr(m["d_feats"]), m["K"], m["K"],
-                                         m["max_rows"], self.dim, _lib.ptr(kjt.values()), _lib.ptr(ks), N, N, 1, 0,
-                                         _lib.ptr(ws), ws.numel(), stream), "tzr_pooled_bwd_plan")
+        dev = self._device
+        # one gradient row per id; the ids of key k lie behind key_start[k]
+        p = SparseBackward(dev, m["d_tables"], m["d_feats"], m["T"], m["K"], m["K"], m["max_rows"], self.dim, kjt.values(),
+                           kjt._tzr_key_start, None, N, N, 1, grad_mode=1)  # type: ignore[attr-defined]
+        ws = _lib.workspace(p.plan_bytes(), dev)
+        p.plan(ws)
         self.fused_optimizer.begin_step(dev)
-        opt = self.fused_optimizer.optim_struct(dev)
-        g1 = (_lib.TzrDst * 1)()
-        g1[0].ptr, g1[0].stride = _lib.ptr(g), g.stride(0)
-        _lib.check(L.tzr_pooled_bwd_apply(_lib.ptr(m["d_tables"]), _lib.ptr(m["d_feats"]), m["K"], m["T"], self.dim,
-                                          _lib.ptr(ks), None, N, N, 1, 0, 1, g1, 1, opt, _lib.ptr(ws), ws.numel(),
-                                          stream), "tzr_pooled_bwd_apply")
+        p.apply(ws, grad_dsts([g]), self.fused_optimizer.optim_struct(dev))
 
     def forward(self, features: KeyedJaggedTensor) -> Dict[str, JaggedTensor]:
         if self._lookup_trackers:

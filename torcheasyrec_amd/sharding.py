@@ -48,6 +48,7 @@ from .dlrm import MLP, OutputLinear
 from .embedding import EmbeddingBagCollection, EmbeddingBagConfig, SparseOptimizerConfig
 from .interaction import dot_interaction
 from .sparse import KeyedJaggedTensor, block_bucketize
+from .sparse_bwd import SparseBackward, direct_supported, grad_dsts
 
 
 def row_wise_plan(rows: Sequence[int], world: int, whole: Optional[Sequence[bool]] = None) -> Tuple[List[int], List[int]]:
@@ -707,11 +708,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         stream = _lib.stream_ptr(dev)
         if outs is None:
             outs = [torch.empty(B, w, dtype=torch.float32, device=dev) for w in rm["widths"]]
-        dsts = (_lib.TzrDst * len(outs))()
-        for i, o in enumerate(outs):
-            if o.shape != (B, rm["widths"][i]) or o.stride(1) != 1:
-                raise ValueError("output buffer shape")
-            dsts[i].ptr, dsts[i].stride = _lib.ptr(o), o.stride(0)
+        dsts = self._dst_array(outs, B, rm["widths"])
         work = None
         if "rw_n" in rm:
             sub = st["sub"]
@@ -762,102 +759,74 @@ class ShardedEmbeddingBagCollection(nn.Module):
 
     # K6 depends on ids only: a pipeline may run both plans right after the input dist, one batch
     # ahead on its side stream (`plan_ahead`), and the backward then starts at K7
-    def _plan_dp(self, st: dict) -> torch.Tensor:
-        L, dev, D = _lib.lib(), self._device, self.dim
+    def _dp_problem(self, st: dict) -> SparseBackward:
+        """replicated tables: the pooled gradients of my samples, summed per row into `_dp_acc` (the accumulate descriptors)"""
         kjt, rm, uniform = st["kjt"], st["rm"], st["uniform"]
-        B, N_all, n_dp, T_dp = kjt.stride(), kjt.values().numel(), rm["dp_n"], len(self._dp)
-        NP = n_dp * B if uniform else N_all
-        ws = self._slot_workspace(st.get("slot") if "cap" in st else None, "ws_dp", L.tzr_pooled_bwd_workspace(N_all, NP, n_dp, T_dp, B, D))
-        _lib.check(L.tzr_pooled_bwd_plan(_lib.ptr(rm["dp_d_acc_tables"]), T_dp, _lib.ptr(rm["dp_d_bwd_feats"]), n_dp,
-                                         rm["n_keys"], rm["dp_max_rows"], D, _lib.ptr(kjt.values()),
-                                         _lib.ptr(None if uniform else kjt.offsets()), N_all, NP, B, 1 if uniform else 0,
-                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "tzr_pooled_bwd_plan")
+        B, N_all, n_dp = kjt.stride(), kjt.values().numel(), rm["dp_n"]
+        return SparseBackward(self._device, rm["dp_d_acc_tables"], rm["dp_d_bwd_feats"], len(self._dp), n_dp, rm["n_keys"],
+                              rm["dp_max_rows"], self.dim, kjt.values(), None if uniform else kjt.offsets(), kjt.weights_or_none(),
+                              N_all, n_dp * B if uniform else N_all, B)
+
+    def _rw_problem(self, st: dict) -> SparseBackward:
+        """owned shards: one gradient row per received id, the ids of each (sender, key) segment behind `key_start`.  (ZCH tables:
+        the row ids are the owner's remap of the received ones, which exists once `exchange_rows` has run.)"""
+        om, n_recv = st["om"], st["n_recv"]
+        return SparseBackward(self._device, om["d_bwd_tables"], om["d_bwd_feats"], om["T"], om["K"], om["K"], om["max_rows"], self.dim,
+                              st.get("owner_ids", st["recv_ids"]), st["key_start"], None, n_recv, n_recv, 1, grad_mode=1)
+
+    def _plan_half(self, st: dict, what: str, p: SparseBackward) -> torch.Tensor:
+        ws = self._slot_workspace(st.get("slot") if "cap" in st else None, "ws_" + what, p.plan_bytes())
+        p.plan(ws)
         return ws
+
+    def _plan_dp(self, st: dict) -> torch.Tensor:
+        return self._plan_half(st, "dp", self._dp_problem(st))
 
     def _plan_rw(self, st: dict) -> torch.Tensor:
-        L, dev, D = _lib.lib(), self._device, self.dim
-        om, n_recv = st["om"], st["n_recv"]
-        K, T = om["K"], om["T"]
-        ws = self._slot_workspace(st.get("slot") if "cap" in st else None, "ws_rw", L.tzr_pooled_bwd_workspace(n_recv, n_recv, K, T, 1, D))
-        _lib.check(L.tzr_pooled_bwd_plan(_lib.ptr(om["d_bwd_tables"]), T, _lib.ptr(om["d_bwd_feats"]), K, K, om["max_rows"], D,
-                                         _lib.ptr(st.get("owner_ids", st["recv_ids"])), _lib.ptr(st["key_start"]), n_recv,
-                                         n_recv, 1, 0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "tzr_pooled_bwd_plan")
-        return ws
+        return self._plan_half(st, "rw", self._rw_problem(st))
 
     # -- the fused backward of one half (replicas / owned shards): planned pair, or ONE launch for small batches ------
-    def _direct_ws(self, what: str, slot, n_positions: int, n_tables: int) -> torch.Tensor:
+    def _direct_ws(self, what: str, st: dict, p: SparseBackward) -> torch.Tensor:
         """persistent zero-initialised workspace of tzr_pooled_bwd_direct (its counters reset themselves); one per half,
         pipeline slot and size -- never evicted: captured graphs hold the address"""
-        key = ("direct", what, slot, int(n_positions), int(n_tables))
+        key = ("direct", what, st.get("slot") if "cap" in st else None, int(p.n_positions), int(p.n_tables))
         hit = self._slot_bufs.get(key)
         if hit is None:
-            hit = _lib.zeroed_workspace(_lib.lib().tzr_pooled_bwd_direct_workspace(n_positions, n_tables, self.dim), self._device)
-            self._slot_bufs[key] = hit
+            hit = self._slot_bufs[key] = _lib.zeroed_workspace(p.direct_bytes(), self._device)
         return hit
 
+    # (sizes only: `plan_ahead` asks before the owner's row ids exist)
     def _dp_direct(self, st: dict) -> bool:
-        kjt, rm = st["kjt"], st["rm"]
-        uniform = st["uniform"]
-        NP = rm["dp_n"] * kjt.stride() if uniform else kjt.values().numel()
-        return bool(_lib.lib().tzr_pooled_bwd_direct_supported(NP, rm["dp_n"], len(self._dp), 1 if uniform else 0, 0))
+        kjt, n_dp = st["kjt"], st["rm"]["dp_n"]
+        return direct_supported(n_dp * kjt.stride() if st["uniform"] else kjt.values().numel(), n_dp, len(self._dp), st["uniform"])
 
     def _rw_direct(self, st: dict) -> bool:
-        om = st["om"]
-        return bool(_lib.lib().tzr_pooled_bwd_direct_supported(st["n_recv"], om["K"], om["T"], 0, 1))
+        return direct_supported(st["n_recv"], st["om"]["K"], st["om"]["T"], False, 1)
 
-    def _bwd_dp(self, st: dict, gd, n_dst: int) -> None:
+    def _bwd_half(self, st: dict, what: str, p: SparseBackward, grads, opt) -> None:
+        if p.direct_supported():
+            p.direct(self._direct_ws(what, st, p), grads, opt)
+            return
+        ws = st.get("ws_" + what)
+        if ws is None:
+            ws = st["ws_" + what] = self._plan_half(st, what, p)
+        p.apply(ws, grads, opt)
+
+    def _bwd_dp(self, st: dict, gd) -> None:
         """replicated tables: exact per-row gradient sums of my samples into `_dp_acc` (ACCUMULATE)"""
-        L, dev, D = _lib.lib(), self._device, self.dim
-        kjt, rm, uniform = st["kjt"], st["rm"], st["uniform"]
-        B, N_all, n_dp, T_dp = kjt.stride(), kjt.values().numel(), rm["dp_n"], len(self._dp)
-        NP = n_dp * B if uniform else N_all
-        offsets = None if uniform else kjt.offsets()
-        stream = _lib.stream_ptr(dev)
+        dev = self._device
         # `_dp_acc` is zero on entry because the previous step's tzr_dense_rows_update_clear left it so.  A step that raised
         # between this pass and that update left sums behind: cleared here (never inside a capture: a captured step ran whole)
         if getattr(self, "_dp_acc_dirty", False) and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             self._dp_acc.zero_()
         self._dp_acc_dirty = True
-        if self._dp_direct(st):
-            ws = self._direct_ws("dp", st.get("slot") if "cap" in st else None, NP, T_dp)
-            _lib.check(L.tzr_pooled_bwd_direct(_lib.ptr(rm["dp_d_acc_tables"]), T_dp, _lib.ptr(rm["dp_d_bwd_feats"]), n_dp,
-                                               rm["dp_max_rows"], D, _lib.ptr(kjt.values()), _lib.ptr(offsets),
-                                               _lib.ptr(kjt.weights_or_none()), N_all, NP, B, 1 if uniform else 0, 0, gd, n_dst,
-                                               self._optim_struct(_lib.OPT_ACCUMULATE), _lib.ptr(ws), ws.numel(), stream),
-                       "tzr_pooled_bwd_direct")
-            return
-        ws = st.get("ws_dp")
-        if ws is None:
-            ws = st["ws_dp"] = self._plan_dp(st)
-        _lib.check(L.tzr_pooled_bwd_apply(_lib.ptr(rm["dp_d_acc_tables"]), _lib.ptr(rm["dp_d_bwd_feats"]), n_dp, T_dp, D,
-                                          _lib.ptr(offsets), _lib.ptr(kjt.weights_or_none()), N_all, NP, B,
-                                          1 if uniform else 0, 0, gd, n_dst,
-                                          self._optim_struct(_lib.OPT_ACCUMULATE), _lib.ptr(ws), ws.numel(), stream),
-                   "tzr_pooled_bwd_apply")
+        self._bwd_half(st, "dp", self._dp_problem(st), gd, self._optim_struct(_lib.OPT_ACCUMULATE))
 
     def _bwd_rw(self, st: dict, grecv: torch.Tensor) -> None:
         """owned shards: sort by (table, row) + fused optimizer over the received per-id gradient rows"""
-        L, dev, D = _lib.lib(), self._device, self.dim
-        om, n_recv = st["om"], st["n_recv"]
-        if n_recv <= 0:
+        if st["n_recv"] <= 0:
             return
-        K, T = om["K"], om["T"]
-        stream = _lib.stream_ptr(dev)
-        g1 = (_lib.TzrDst * 1)()
-        g1[0].ptr, g1[0].stride = _lib.ptr(grecv), grecv.stride(0)
-        ids = st.get("owner_ids", st["recv_ids"])
-        if self._rw_direct(st):
-            ws = self._direct_ws("rw", st.get("slot") if "cap" in st else None, n_recv, T)
-            _lib.check(L.tzr_pooled_bwd_direct(_lib.ptr(om["d_bwd_tables"]), T, _lib.ptr(om["d_bwd_feats"]), K, om["max_rows"], D,
-                                               _lib.ptr(ids), _lib.ptr(st["key_start"]), None, n_recv, n_recv, 1, 0, 1, g1, 1,
-                                               self._optim_struct(), _lib.ptr(ws), ws.numel(), stream), "tzr_pooled_bwd_direct")
-            return
-        ws2 = st.get("ws_rw")
-        if ws2 is None:
-            ws2 = st["ws_rw"] = self._plan_rw(st)
-        _lib.check(L.tzr_pooled_bwd_apply(_lib.ptr(om["d_bwd_tables"]), _lib.ptr(om["d_bwd_feats"]), K, T, D,
-                                          _lib.ptr(st["key_start"]), None, n_recv, n_recv, 1, 0, 1, g1, 1,
-                                          self._optim_struct(), _lib.ptr(ws2), ws2.numel(), stream), "tzr_pooled_bwd_apply")
+        self._bwd_half(st, "rw", self._rw_problem(st), grad_dsts([grecv]), self._optim_struct())
 
     def plan_ahead(self, st: dict) -> dict:
         """K6 of both halves, for a pipeline to run a batch ahead -- for the halves that have a plan at all (a small
@@ -895,9 +864,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
             if g is None:
                 g = torch.zeros(B, w, dtype=torch.float32, device=dev)
             gl.append(g.contiguous().float())
-        gd = (_lib.TzrDst * len(gl))()
-        for i, g in enumerate(gl):
-            gd[i].ptr, gd[i].stride = _lib.ptr(g), g.stride(0)
+        gd = grad_dsts(gl)
 
         # Order of issue = overlap: the gradient all-to-all flies while the replicas' gradients are
         # sorted and summed; their all-reduce flies while the owners sort and apply the exchanged rows.
@@ -920,7 +887,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
             w_rows = self._a2a(grecv[:n_recv], grow[:n_out], st["recv_splits"], st["send_splits"], async_op=True)
         if "dp_n" in rm:
             # replicas: exact per-row gradient sums of my samples -> all-reduce -> same dense update
-            self._bwd_dp(st, gd, len(gl))  # (`_dp_acc` is zero: tzr_dense_rows_update_clear leaves it so)
+            self._bwd_dp(st, gd)  # (`_dp_acc` is zero: tzr_dense_rows_update_clear leaves it so)
             w_acc = dist.all_reduce(self._dp_acc, group=self.pg, async_op=True)
         if w_rows is not None:
             w_rows.wait()
@@ -944,12 +911,10 @@ class ShardedEmbeddingBagCollection(nn.Module):
     # same arguments, same order per table as `lookup` / `_backward_impl`; only the overlap of a collective with the
     # replicas' kernels is given up.  Capacity-bounded states only (`"cap" in st`).
     def _dst_array(self, outs: Sequence[torch.Tensor], B: int, widths: Sequence[int]):
-        dsts = (_lib.TzrDst * len(outs))()
-        for i, o in enumerate(outs):
-            if o.shape != (B, widths[i]) or o.stride(1) != 1:
+        for o, w in zip(outs, widths):
+            if o.shape != (B, w) or o.stride(1) != 1:
                 raise ValueError("output buffer shape")
-            dsts[i].ptr, dsts[i].stride = _lib.ptr(o), o.stride(0)
-        return dsts
+        return grad_dsts(outs)
 
     def seg_owner_rows(self, st: dict, outs: List[torch.Tensor], dp: bool = True) -> None:
         """owner: one row per received id (-> `coll_rows`); `dp`: also the replicated tables, pooled straight into `outs`
@@ -1038,7 +1003,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         if "dp_n" in rm:
             gl = st["_grads_alive"]
             gd = self._dst_array(gl, B, rm["widths"])
-            self._bwd_dp(st, gd, len(gl))  # (`_dp_acc` is zero: tzr_dense_rows_update_clear leaves it so)
+            self._bwd_dp(st, gd)  # (`_dp_acc` is zero: tzr_dense_rows_update_clear leaves it so)
 
     def coll_grads(self, st: dict) -> None:
         self.coll_grads_rw(st)
