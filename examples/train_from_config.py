@@ -7,6 +7,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/mmoe_seq_mini.config     (a click history inside the DEEP group)
     python examples/train_from_config.py tests/golden/jrc_mini.config          (jrc_loss over sessions, a sample weight column)
     python examples/train_from_config.py tests/golden/dcn_mini.config          (dcn_v1: the cross network in one launch)
+    python examples/train_from_config.py tests/golden/xdeepfm_mini.config      (xdeepfm: the CIN without its [B, H F, D] tensor)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""

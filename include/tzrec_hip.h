@@ -955,6 +955,34 @@ int tzr_cross_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, in
                   const float* const* h_w, const float* const* h_b, int L, int64_t B, int D, float* d_dx, int64_t dx_stride,
                   float* d_dw, float* d_db, void* ws, size_t ws_size, void* stream);
 
+/* The compressed interaction network of xDeepFM: replaces CIN.forward and its autograd (tzrec/modules/interaction.py:183-233),
+ * which per layer build z = einsum("bhd,bfd->bhfd") as a [B, H F, D] tensor and keep it for the backward.  csrc/cin.hip; z is
+ * never built, forward or backward.  x is the group tensor [B, F D] (X0[f, (b, d)] = x[b, f D + d]), H_0 = F, H_{i+1} = O_i:
+ *   tzr_cin_fwd   X^{i+1}[b, o, d] = c_i[o] + sum_{h,f} W_i[o, h F + f] X^i[b, h, d] X0[b, f, d];  d_y[b, O_0 + .. + O_{i-1} + o] =
+ *                 sum_d X^{i+1}[b, o, d].  ONE launch for every layer.  h_xs: HOST array of L - 1 device pointers, h_xs[i] takes
+ *                 X^{i+1} [B, O_i, D] contiguous, the saved state of the backward (nullable, or null entries: inference; X^L is
+ *                 only pooled and never stored).
+ *   tzr_cin_bwd   from d_grad_y [B, sum O], x and the saved h_xs: d_gx [B, F D], and in d_dwc, contiguous, per layer dW_i
+ *                 [O_i, H_i F] followed by dc_i [O_i].  The saved state is CONSUMED: on return h_xs[i] holds dX^{i+1} (a second
+ *                 backward needs a second forward); this is what keeps the backward free of any [B, O, D] temporary.  2 L + 1
+ *                 launches: per layer the weight gradient (a workgroup owns its output tile and walks its part of the columns;
+ *                 the layer's S_i parts, a function of the shapes alone, lie in `ws`) and the input gradients, then one launch that
+ *                 adds every layer's parts 0..S_i-1.
+ *                 `ws`: tzr_cin_bwd_workspace bytes, 256-byte aligned.
+ * h_w / h_c: HOST arrays of L device pointers (Conv1d weight [O_i, H_i F, 1] and bias [O_i], contiguous); h_layers: HOST
+ * array of the L sizes O_i.  fp32; D in [1, 64], F in [1, 64], O_i in [1, 256], L in [1, 4], B < 2^30; row strides (floats) of x
+ * and gx >= F D, of y and grad_y >= sum O.  Every pointer needs 4-byte alignment only (single-float loads and stores), so a
+ * column slice of a wider tensor is taken as it lies.  TZR_ERR_INVALID: a null pointer, B < 0, a size <= 0;
+ * TZR_ERR_UNSUPPORTED: outside the limits above; TZR_ERR_WORKSPACE: `ws` null, misaligned or shorter than the query less its
+ * 256 bytes of slack.  Every check precedes the first launch; B == 0 is TZR_OK without a launch.  No atomics; every sum's order
+ * is a function of the shapes alone: bit-reproducible.  Entry points only: the ABI version stays 15. */
+int tzr_cin_fwd(const float* d_x, int64_t x_stride, const float* const* h_w, const float* const* h_c, const int* h_layers, int L,
+                int64_t B, int F, int D, float* const* h_xs, float* d_y, int64_t y_stride, void* stream);
+size_t tzr_cin_bwd_workspace(int64_t B, int F, int D, const int* h_layers, int L);
+int tzr_cin_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, int64_t x_stride, const float* const* h_w,
+                const int* h_layers, int L, int64_t B, int F, int D, float* const* h_xs, float* d_gx, int64_t gx_stride,
+                float* d_dwc, void* ws, size_t ws_size, void* stream);
+
 /* ---- native step driver (csrc/step_driver.hip) ------------------------------------------------------------------
  * Replaces the host side of a steady-state train step of tzrec's pipeline (tzrec/utils/dist_util.py:221-303: Python +
  * torch.distributed calls per collective) for a sharded step that was cut into captured hipGraphs: ONE call queues the

@@ -527,7 +527,8 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
         if k not in skip and isinstance(v[-1], Msg):
             spec.model_name, spec.model = k, v[-1]
     spec.num_class = int(mc.one("num_class", 1))
-    spec.wide_embedding_dim = int(spec.model.one("wide_embedding_dim", 0)) if spec.model else 0
+    # (0 = the embedding group's fallback of 4, DeepFM's proto default; the xdeepfm message defaults to 16, rank_model.proto:69)
+    spec.wide_embedding_dim = int(spec.model.one("wide_embedding_dim", 16 if spec.model_name == "xdeepfm" else 0)) if spec.model else 0
     tc = cfg.one("train_config", Msg())
     if tc.has("sparse_optimizer"):
         spec.sparse_optimizer = sparse_optimizer_from_config(tc.one("sparse_optimizer"))

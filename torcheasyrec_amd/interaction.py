@@ -7,6 +7,8 @@ sparse block separately (no ``cat`` to build [B, 27, 16]) and writes
 ``[interactions | dense | sparse]`` in one pass (/root/reference/tzrec/models/dlrm.py:123-130).
 ``Cross`` is the cross network of Deep & Cross v1 with the reference's parameters (interaction.py:94-132), every layer
 of it in one launch per direction (csrc/cross_net.hip).
+``CIN`` is the compressed interaction network of xDeepFM with the reference's parameters (interaction.py:183-233); the
+[B, H F, D] product tensor the reference builds per layer never exists (csrc/cin.hip).
 """
 from __future__ import annotations
 
@@ -213,3 +215,101 @@ class Cross(nn.Module):
         for i in range(self.cross_num):  # the reference's literal form
             x1 = self.w[i](x1) * x + self.b[i] + x1
         return x1
+
+
+FUSED_CIN = True  # A/B switch: False = the reference's literal loop (einsum to [B, H F, D], Conv1d, sum per layer)
+CIN_MAX_DIM, CIN_MAX_FEATURES, CIN_MAX_LAYER_SIZE, CIN_MAX_LAYERS = 64, 64, 256, 4  # CIN_MAXD, CIN_MAXF, CIN_MAXO, CIN_MAXL of csrc/cin.hip
+
+
+class _CINFn(torch.autograd.Function):
+    """y = cat_i sum_d X^{i+1} on tzr_cin_fwd (one launch, saves X^1 .. X^{L-1}) and tzr_cin_bwd (2 L + 1 launches), which returns
+    the input gradient and every layer's finished weight and bias gradient (pieces of one buffer).  The backward writes dX^i
+    over the saved X^i, so it runs once per forward."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, F: int, D: int, layers, *params: torch.Tensor):
+        x = _rows(x)
+        B, L = x.shape[0], len(layers)
+        params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
+        y = torch.empty(B, sum(layers), dtype=torch.float32, device=x.device)
+        save = any(ctx.needs_input_grad)
+        xs = [torch.empty(B, o, D, dtype=torch.float32, device=x.device) for o in layers[:-1]] if save else []
+        sizes = (C.c_int * L)(*layers)
+        rc = _lib.lib().tzr_cin_fwd(_lib.ptr(x), _row_stride(x), _pointer_array(params[:L]), _pointer_array(params[L:]), sizes, L, B, F, D,
+                                    _pointer_array(xs) if xs else None, _lib.ptr(y), y.shape[1], _lib.stream_ptr(x.device))
+        _lib.check(rc, "tzr_cin_fwd")
+        ctx.save_for_backward(x, *params[:L], *xs)
+        ctx.cfg, ctx.consumed = (F, D, tuple(layers)), False
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        F, D, layers = ctx.cfg
+        L = len(layers)
+        x, *rest = ctx.saved_tensors
+        ws_, xs = rest[:L], rest[L:]
+        if ctx.consumed:
+            raise RuntimeError("CIN: the backward overwrites the saved activations with their gradients and ran already; "
+                               "run the forward again (or set interaction.FUSED_CIN = False) for a second backward")
+        ctx.consumed = True
+        B = x.shape[0]
+        gy = _rows(gy)
+        hs = (F,) + layers[:-1]
+        total = sum(o * h * F + o for o, h in zip(layers, hs))
+        gx = torch.empty(B, F * D, dtype=torch.float32, device=x.device)
+        dwc = torch.empty(total, dtype=torch.float32, device=x.device)
+        lib, sizes = _lib.lib(), (C.c_int * L)(*layers)
+        ws = _lib.workspace(lib.tzr_cin_bwd_workspace(B, F, D, sizes, L), x.device)
+        rc = lib.tzr_cin_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _pointer_array(ws_), sizes, L, B, F, D,
+                             _pointer_array(xs) if xs else None, _lib.ptr(gx), F * D, _lib.ptr(dwc), _lib.ptr(ws), ws.numel(),
+                             _lib.stream_ptr(x.device))
+        _lib.check(rc, "tzr_cin_bwd")
+        gws, gcs, off = [], [], 0
+        for o, h in zip(layers, hs):
+            gws.append(dwc[off:off + o * h * F].view(o, h * F, 1))
+            gcs.append(dwc[off + o * h * F:off + o * h * F + o])
+            off += o * h * F + o
+        return (gx, None, None, None, *gws, *gcs)
+
+
+class CIN(nn.Module):
+    """Compressed interaction network of xDeepFM (https://arxiv.org/pdf/1803.05170), the reference module's constructor,
+    parameters and forward (tzrec/modules/interaction.py:183-233): `cin_layers.<i>` is a Conv1d(H_i F, O_i, kernel_size=1)."""
+
+    def __init__(self, feature_num: int, cin_layer_size) -> None:
+        super().__init__()
+        self.feature_num = feature_num
+        self.cin_layer_size = list(cin_layer_size)
+        self.cin_layers = nn.ModuleList()
+        for i, layer_size in enumerate(self.cin_layer_size):
+            in_channels = feature_num * (self.cin_layer_size[i - 1] if i > 0 else feature_num)
+            self.cin_layers.append(nn.Conv1d(in_channels=in_channels, out_channels=layer_size, kernel_size=1))
+
+    def output_dim(self) -> int:
+        return sum(self.cin_layer_size)
+
+    def _fused_ok(self, x: torch.Tensor) -> bool:
+        from .dlrm import _on_emulator
+
+        L = len(self.cin_layer_size)
+        return bool(FUSED_CIN and x.dim() == 3 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
+                    and x.shape[1] == self.feature_num and 1 <= L <= CIN_MAX_LAYERS
+                    and 1 <= x.shape[1] <= CIN_MAX_FEATURES and 1 <= x.shape[2] <= CIN_MAX_DIM
+                    and all(1 <= o <= CIN_MAX_LAYER_SIZE for o in self.cin_layer_size)
+                    and all(m.weight.dtype == torch.float32 and m.bias is not None for m in self.cin_layers)
+                    and (x.is_cuda or _on_emulator()))
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if self._fused_ok(input):
+            B, F, D = input.shape
+            # (a view of a group tensor, or of a column slice of one, reshapes to its [B, F D] rows as they lie: no copy)
+            return _CINFn.apply(input.reshape(B, F * D), F, D, tuple(self.cin_layer_size), *[m.weight for m in self.cin_layers],
+                                *[m.bias for m in self.cin_layers])
+        batch_size, field_num, embed_dim = input.shape
+        x_vec, x_out = input, []
+        for i, o in enumerate(self.cin_layer_size):  # the reference's literal form
+            z = torch.einsum("bhd,bfd->bhfd", x_vec, input)
+            z = z.reshape(batch_size, field_num * (self.cin_layer_size[i - 1] if i > 0 else field_num), embed_dim)
+            x_vec = self.cin_layers[i](z)
+            x_out.append(torch.sum(x_vec, dim=2))
+        return torch.cat(x_out, dim=1) if x_out else input.new_zeros(batch_size, 0)

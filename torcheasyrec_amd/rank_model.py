@@ -18,7 +18,7 @@ from .config import PipelineSpec
 from .dlrm import MLP, OutputLinear, _on_emulator
 from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
-from .interaction import Cross, FactorizationMachine, dot_interaction
+from .interaction import CIN, Cross, FactorizationMachine, dot_interaction
 from .losses import build_losses, output_to_prediction
 
 
@@ -345,7 +345,43 @@ class ConfigDCNV1(RankModel):
         return self._output_to_prediction(self.output_linear(self.final_dnn(y)))
 
 
-_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1}
+class ConfigXDeepFM(RankModel):
+    """`xdeepfm {...}` (tzrec/models/xdeepfm.py:44-86): the compressed interaction network over the WIDE group, reshaped to
+    [B, F, wide_embedding_dim] (16 when the config omits it, protos/models/rank_model.proto:69), a deep MLP over group `deep`,
+    a final MLP over [cin | deep], a logits layer with bias.  `cin { cin_layer_size }` (protos/module.proto) is required."""
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        if not m.has("cin"):
+            raise ValueError("xdeepfm: the model needs a `cin { cin_layer_size: ... }` block")
+        cin = m.one("cin")
+        other = sorted(k for k in cin if k != "cin_layer_size")
+        if other:
+            raise ValueError(f"xdeepfm: cin has no field {other[0]!r} (fields: cin_layer_size)")
+        layers = [int(v) for v in cin.many("cin_layer_size")]
+        if not layers:
+            raise ValueError("xdeepfm: cin needs at least one cin_layer_size")
+        wide_dims = eg.group_dims("wide")
+        self._feature_num, self._wide_dim = len(wide_dims), spec.wide_embedding_dim
+        assert set(wide_dims) == {self._wide_dim}, f"wide features must all have dim {self._wide_dim}, got {set(wide_dims)}"
+        self.deep = mlp_from_msg(eg.group_total_dim("deep"), m.one("deep"))
+        self.cin = CIN(self._feature_num, layers)
+        self.final = mlp_from_msg(self.cin.output_dim() + self.deep.output_dim(), m.one("final"))
+        self.output_mlp = OutputLinear(self.final.output_dim(), spec.num_class)
+        if device is not None:
+            for mod in (self.deep, self.cin, self.final, self.output_mlp):
+                mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        g = self.build_input(batch)
+        cin_feat = self.cin(g["wide"].reshape(-1, self._feature_num, self._wide_dim))
+        y = self.final(torch.cat([cin_feat, self.deep(g["deep"])], dim=1))
+        return self._output_to_prediction(self.output_mlp(y))
+
+
+_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1,
+           "xdeepfm": ConfigXDeepFM}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
