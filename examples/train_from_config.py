@@ -8,6 +8,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/jrc_mini.config          (jrc_loss over sessions, a sample weight column)
     python examples/train_from_config.py tests/golden/dcn_mini.config          (dcn_v1: the cross network in one launch)
     python examples/train_from_config.py tests/golden/xdeepfm_mini.config      (xdeepfm: the CIN without its [B, H F, D] tensor)
+    python examples/train_from_config.py tests/golden/masknet_mini.config      (mask_net: LayerNorm, masks and concat in two row launches)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""

@@ -955,6 +955,36 @@ int tzr_cross_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, in
                   const float* const* h_w, const float* const* h_b, int L, int64_t B, int D, float* d_dx, int64_t dx_stride,
                   float* d_dw, float* d_db, void* ws, size_t ws_size, void* stream);
 
+/* LayerNorm, an optional ReLU and an optional elementwise mask over rows, up to eight outputs per launch: the non-GEMM work of
+ * MaskNet (tzrec/modules/masknet.py:77-85, 142-161).  csrc/ln_mask.hip.
+ *   tzr_ln_mask_fwd  f_j = act(LN(x_j; gamma_j, beta_j, eps)), act = ReLU (relu != 0) or identity; out_j = f_j * m_j, or f_j
+ *                    when h_m is null.  shared_x != 0: every j reads x_0, gamma_0, beta_0 (the arrays h_x, h_x_stride, h_gamma,
+ *                    h_beta hold ONE entry), the statistics are computed once and LN(x) is never stored; otherwise they hold
+ *                    n_out entries.  d_stats [B, n_stat, 2] contiguous takes (mean, rstd), n_stat = 1 (shared) or n_out.
+ *                    LN is nn.LayerNorm's (biased variance, eps inside the root), the variance a second pass over
+ *                    (x - mean)^2.  One launch.
+ *   tzr_ln_mask_bwd  from gout_j, the same x / gamma / beta / m and d_stats: gm_j = gout_j * f_j (with masks), the pre-mask
+ *                    gradient sum_j gout_j * m_j (shared) or gout_j * m_j through the ReLU mask (recomputed by the
+ *                    forward's instruction sequence) and LN's backward into gx_j (n_stat of them), d_dgamma and d_dbeta
+ *                    [n_stat, D] contiguous, finished.  Two launches: the pass over the batch, which leaves one row of
+ *                    partial sums per workgroup in `ws` (tzr_ln_mask_bwd_workspace bytes, 256-byte aligned), and their sum in
+ *                    a fixed order.
+ * Every h_* is a HOST array (of device pointers, or of row strides in floats), read by the call and passed to the kernels by
+ * value; x_j, m_j, out_j, gout_j, gx_j, gm_j may be column slices of wider tensors.  fp32; D in [1, 1024], n_out in [1, 8],
+ * strides >= D, 4-byte alignment.  TZR_ERR_INVALID: a null pointer (h_m / h_m_stride / h_gm / h_gm_stride may be null
+ * together: no masks), a misaligned workspace, B < 0, D <= 0, n_out <= 0; TZR_ERR_UNSUPPORTED: D > 1024, n_out > 8, a stride
+ * below D, a workspace shorter than the query; B == 0 is TZR_OK without a launch.  One wave per sample, no atomics, every
+ * sum over the batch in an order fixed by (B, D, n_out, shared_x): bit-reproducible.  Entry points only: the ABI version stays 15. */
+int tzr_ln_mask_fwd(const float* const* h_x, const int64_t* h_x_stride, const float* const* h_gamma, const float* const* h_beta,
+                    const float* const* h_m, const int64_t* h_m_stride, float* const* h_out, const int64_t* h_out_stride, int n_out,
+                    int shared_x, int relu, float eps, int64_t B, int D, float* d_stats, void* stream);
+size_t tzr_ln_mask_bwd_workspace(int64_t B, int D, int n_out, int shared_x);
+int tzr_ln_mask_bwd(const float* const* h_gout, const int64_t* h_gout_stride, const float* const* h_x, const int64_t* h_x_stride,
+                    const float* const* h_gamma, const float* const* h_beta, const float* const* h_m, const int64_t* h_m_stride,
+                    const float* d_stats, int n_out, int shared_x, int relu, int64_t B, int D, float* const* h_gx,
+                    const int64_t* h_gx_stride, float* const* h_gm, const int64_t* h_gm_stride, float* d_dgamma, float* d_dbeta,
+                    void* ws, size_t ws_size, void* stream);
+
 /* The compressed interaction network of xDeepFM: replaces CIN.forward and its autograd (tzrec/modules/interaction.py:183-233),
  * which per layer build z = einsum("bhd,bfd->bhfd") as a [B, H F, D] tensor and keep it for the backward.  csrc/cin.hip; z is
  * never built, forward or backward.  x is the group tensor [B, F D] (X0[f, (b, d)] = x[b, f D + d]), H_0 = F, H_{i+1} = O_i:

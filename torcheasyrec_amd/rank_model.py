@@ -20,6 +20,7 @@ from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
 from .interaction import CIN, Cross, FactorizationMachine, dot_interaction
 from .losses import build_losses, output_to_prediction
+from .masknet import MaskNetModule
 
 
 def mlp_kwargs(msg) -> Dict[str, object]:
@@ -380,8 +381,52 @@ class ConfigXDeepFM(RankModel):
         return self._output_to_prediction(self.output_mlp(y))
 
 
+class ConfigMaskNet(RankModel):
+    """`mask_net {...}` (tzrec/models/masknet.py:25-65): the MaskNet module over the (single) feature group, a logits layer
+    without bias over `top_mlp.hidden_units[-1]`.  `mask_net_module { n_mask_blocks mask_block { reduction_ratio aggregation_dim
+    hidden_dim } top_mlp {...} use_parallel }` (protos/module.proto:62-80): `reduction_ratio` defaults to 1.0 and
+    `use_parallel` to true; `top_mlp` is optional in the proto, but the reference's model indexes its last hidden unit."""
+
+    _FIELDS = {"mask_net": ("mask_net_module",), "mask_net_module": ("n_mask_blocks", "mask_block", "top_mlp", "use_parallel"),
+               "mask_block": ("reduction_ratio", "aggregation_dim", "hidden_dim")}
+
+    @classmethod
+    def _block(cls, parent, where: str, name: str):
+        other = sorted(k for k in parent if k not in cls._FIELDS[where])
+        if other:
+            raise ValueError(f"mask_net: {where} has no field {other[0]!r} (fields: {', '.join(cls._FIELDS[where])})")
+        if not parent.has(name):
+            raise ValueError(f"mask_net: {where} needs `{name}`")
+        return parent.one(name)
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg = self.embedding_group
+        self._group = eg.group_names()[0]
+        mod = self._block(spec.model, "mask_net", "mask_net_module")
+        n_blocks = self._block(mod, "mask_net_module", "n_mask_blocks")
+        blk = self._block(mod, "mask_net_module", "mask_block")
+        hidden_dim = self._block(blk, "mask_block", "hidden_dim")
+        if not mod.has("top_mlp") or not mod.one("top_mlp").many("hidden_units"):
+            raise ValueError("mask_net: mask_net_module needs `top_mlp { hidden_units: ... }` (the logits layer reads its last width)")
+        mask_block = {"hidden_dim": int(hidden_dim), "reduction_ratio": float(blk.one("reduction_ratio", 1.0))}
+        if blk.has("aggregation_dim"):
+            mask_block["aggregation_dim"] = int(blk.one("aggregation_dim"))
+        top = mlp_kwargs(mod.one("top_mlp"))
+        self.mask_net_layer = MaskNetModule(eg.group_total_dim(self._group), int(n_blocks), mask_block, top_mlp=top,
+                                            use_parallel=bool(mod.one("use_parallel", True)))
+        self.output_linear = OutputLinear(top["hidden_units"][-1], spec.num_class, bias=False)
+        if device is not None:
+            for m in (self.mask_net_layer, self.output_linear):
+                m.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        features = self.build_input(batch)[self._group]
+        return self._output_to_prediction(self.output_linear(self.mask_net_layer(features)))
+
+
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1,
-           "xdeepfm": ConfigXDeepFM}
+           "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
