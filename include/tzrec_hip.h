@@ -653,7 +653,7 @@ int tzr_dense_adam(const TzrAdamTensor* h_tensors, int n_tensors, const float* d
  * finish launches and the slice reduction of the DLRM step (tzrec/models/dlrm.py:101-135 behind tzrec/optim/optimizer.py:56-68)
  * disappear into the optimizer's launch.  The sums are bit-identical to the separate launches where the order of additions is
  * theirs: tzr_mlp2_bwd's finish (16 contiguous ranges of the G rows, then the 16 range sums) and the slice reduction of
- * tzr_dot_interaction_top_wgrad.  Partial rows that tzr_colsum_finish_kernel would finish (tzr_relu_bwd_colsum_parts,
+ * tzr_dot_interaction_top_wgrad.  Partial rows whose separate finish is the interleaved one of csrc/parts_sum.h (tzr_relu_bwd_colsum_parts,
  * tzr_skinny_linear_bwd_parts) are added in THIS order too, not in that kernel's interleaved slices: equal to it up to fp32
  * rounding, and equal between every consumer of this summation (tzr_dense_adam_fused, tzr_dense_optim_fused, store-only calls).
  * Refused: TZR_ERR_UNSUPPORTED for a source that would need more than 1024 workgroups (the arrival counters of a state row);

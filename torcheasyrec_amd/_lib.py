@@ -396,6 +396,11 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def ptr_array(tensors):
+    """a C array of the tensors' addresses (the `const float* const*` arguments)"""
+    return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
 def stream_ptr(device: torch.device) -> Optional[int]:
     """raw handle of torch's current stream on `device` (one C call: `torch.cuda.current_stream(device).cuda_stream` builds
     a Stream object through three layers of Python per kernel launch -- 35 us of a sharded step whose host time is its

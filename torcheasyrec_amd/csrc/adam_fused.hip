@@ -7,9 +7,9 @@
 // launches that used to stand between the backward and it in the DLRM step (models/dlrm.py:101-135): two column-sum
 // finishes, the weight gradient's slice reduction and the optimizer's own step-counter launch were 4 of the step's 17
 // launches, 20 us of dependent round trips for < 14 MB (profiles/r05final3/kernel_stats.csv).  Here a gradient element is
-// summed by the threads that then update its parameter (csrc/fused_grad.h: in the order of tzr_mlp2_bwd's finish and of the
-// slice reduction -- bit-identical to those two; the column sums that tzr_colsum_finish_kernel adds in interleaved slices
-// differ from it by fp32 rounding); the step counter of a tensor is read by every workgroup and moved on by the LAST of the
+// summed by the threads that then update its parameter (csrc/fused_grad.h: partial-sum rows in the blocked order of
+// csrc/parts_sum.h, as tzr_mlp2_bwd's finish, and the slice reduction's own order -- bit-identical to those two; the column sums
+// whose separate finish is the interleaved order differ from it by fp32 rounding); the step counter of a tensor is read by every workgroup and moved on by the LAST of the
 // tensor's workgroups to finish.
 #include "fused_grad.h"
 #include "interaction_pack.h"

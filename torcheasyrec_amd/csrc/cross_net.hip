@@ -19,8 +19,9 @@
 // together) are read per sample and stay in the caches.
 //
 // Reduction order: a wave adds its samples in the order of the grid-stride loop, a workgroup its four waves 0..3, and the
-// finishing launch the workgroups' rows 0..G-1 (sixteen interleaved chains, then 0..15): a function of (B, D, L) alone.  No atomics.
-#include "tzr_common.h"
+// finishing launch the workgroups' rows 0..G-1 in the interleaved order of parts_sum.h: a function of (B, D, L) alone.  No atomics.
+#include "parts_sum.h"
+#include "row_kernels.h"
 
 #define CN_THREADS 256
 #define CN_WAVES (CN_THREADS / TZR_WAVE)
@@ -32,11 +33,6 @@ struct CnParams {  // the layers' parameters: L separate [1, D] / [D] tensors, p
   const float* w[CN_MAXL];
   const float* b[CN_MAXL];
 };
-
-__device__ __forceinline__ float cn_wave_sum(float v) {  // (fixed tree)
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 template <int KR>
 __global__ __launch_bounds__(CN_THREADS) void tzr_cross_fwd_kernel(const float* __restrict__ x, int64_t xs, CnParams P, int L, int64_t B,
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(CN_THREADS) void tzr_cross_fwd_kernel(const float* 
       float dot = 0.f;
 #pragma unroll
       for (int k = 0; k < KR; ++k) dot = fmaf(x1[k], wl[k], dot);
-      const float sl = cn_wave_sum(dot);
+      const float sl = tzr_wave_sum(dot);
 #pragma unroll
       for (int k = 0; k < KR; ++k) x1[k] = fmaf(sl, x0[k], bl[k]) + x1[k];
       if (s && lane == 0) s[b * L + l] = sl;
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(CN_THREADS) void tzr_cross_fwd_kernel(const float* 
 // floats of one workgroup's row of partial sums: [A_0 .. A_{L-1} | G] (D each), then T_0 .. T_{L-1}
 __host__ __device__ static inline size_t cn_row_len(int D, int L) { return (size_t)(L + 1) * (size_t)D + (size_t)L; }
 
-static inline unsigned cn_grid(int64_t B) { return (unsigned)std::min<int64_t>(CN_MAXGRID, (B + CN_WAVES - 1) / CN_WAVES); }
+static inline unsigned cn_grid(int64_t B) { return tzr_row_grid(B, CN_WAVES, CN_MAXGRID); }
 
 // LL: compile-time bound of the layer loops (the smallest instantiated one covering L)
 template <int KR, int LL>
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(CN_THREADS) void tzr_cross_bwd_kernel(const float* 
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < KR; ++k) dot = fmaf(a[k], x0[k], dot);
-        const float t = cn_wave_sum(dot);
+        const float t = tzr_wave_sum(dot);
         const float u = t * cl[l];
         T[l] += t;
 #pragma unroll
@@ -165,15 +161,13 @@ __global__ __launch_bounds__(CN_THREADS) void tzr_cross_bwd_kernel(const float* 
   }
 }
 
-// grid (D / 64 rounded up, L + 1), CN_FIN_THREADS threads: workgroup (i, v) adds column tile i of vector v over the G rows of
-// partial sums -- wave k the rows k, k + 16, ..., eight loads in flight, then the waves 0..15 in order -- and writes dw_v
-// (v < L) or, from G, every db_l (v == L).  T_l: wave l adds the rows lane, lane + 64, ..., then a fixed tree over the lanes.
-#define CN_FIN_THREADS 1024
-#define CN_FIN_WAVES (CN_FIN_THREADS / TZR_WAVE)
-__global__ __launch_bounds__(CN_FIN_THREADS) void tzr_cross_bwd_finish_kernel(const float* __restrict__ parts, int G, CnParams P, int L,
-                                                                              int D, float* __restrict__ dw, float* __restrict__ db) {
+// grid (D / 64 rounded up, L + 1), TZR_FIN_THREADS threads: workgroup (i, v) adds column tile i of vector v over the G rows of
+// partial sums (parts_sum.h: interleaved) and writes dw_v (v < L) or, from G, every db_l (v == L).  T_l: wave l adds the rows
+// lane, lane + 64, ..., then a fixed tree over the lanes.
+__global__ __launch_bounds__(TZR_FIN_THREADS) void tzr_cross_bwd_finish_kernel(const float* __restrict__ parts, int G, CnParams P, int L,
+                                                                               int D, float* __restrict__ dw, float* __restrict__ db) {
   __shared__ float Ts[CN_MAXL];
-  __shared__ float red[CN_FIN_WAVES][TZR_WAVE];
+  __shared__ float red[TZR_FIN_THREADS];
   const int lane = threadIdx.x & (TZR_WAVE - 1);
   const int wv = threadIdx.x / TZR_WAVE;
   const int v = blockIdx.y;
@@ -184,21 +178,11 @@ __global__ __launch_bounds__(CN_FIN_THREADS) void tzr_cross_bwd_finish_kernel(co
     float t = 0.f;
 #pragma unroll 8
     for (int w = lane; w < G; w += TZR_WAVE) t += src[(size_t)w * R];
-    t = cn_wave_sum(t);
+    t = tzr_wave_sum(t);
     if (lane == 0) Ts[wv] = t;
   }
-  float a = 0.f;
-  if (c < D) {
-    const float* src = parts + (size_t)v * D + c;
-#pragma unroll 8
-    for (int w = wv; w < G; w += CN_FIN_WAVES) a += src[(size_t)w * R];
-  }
-  red[wv][lane] = a;
-  __syncthreads();
+  const float tot = tzr_parts_sum_interleaved<true>(c < D ? parts + (size_t)v * D + c : nullptr, G, R, red);  // (Ts: behind its barrier)
   if (wv != 0 || c >= D) return;
-  float tot = red[0][lane];
-#pragma unroll
-  for (int k = 1; k < CN_FIN_WAVES; ++k) tot += red[k][lane];
   if (v < L) {  // dw_v = A_v + T_v (b_0 + .. + b_{v-1})
     float bs = 0.f;
 #pragma unroll
@@ -232,15 +216,6 @@ static int cn_params(const float* const* h_w, const float* const* h_b, int L, Cn
   return TZR_OK;
 }
 
-#define CN_BY_KR(LAUNCH)           \
-  do {                             \
-    if (D <= 64) LAUNCH(1);        \
-    else if (D <= 128) LAUNCH(2);  \
-    else if (D <= 256) LAUNCH(4);  \
-    else if (D <= 512) LAUNCH(8);  \
-    else LAUNCH(16);               \
-  } while (0)
-
 extern "C" int tzr_cross_fwd(const float* d_x, int64_t x_stride, const float* const* h_w, const float* const* h_b, int L, int64_t B,
                              int D, float* d_y, int64_t y_stride, float* d_s, void* stream) {
   if (const int rc = cn_check(B, D, L)) return rc;
@@ -251,7 +226,7 @@ extern "C" int tzr_cross_fwd(const float* d_x, int64_t x_stride, const float* co
 #define CN_FWD(KR_)                                                                                                               \
   hipLaunchKernelGGL((tzr_cross_fwd_kernel<KR_>), dim3(cn_grid(B)), dim3(CN_THREADS), 0, static_cast<hipStream_t>(stream), d_x, x_stride, \
                      P, L, B, D, d_y, y_stride, d_s)
-  CN_BY_KR(CN_FWD);
+  TZR_BY_KR(CN_FWD);
 #undef CN_FWD
   TZR_CHECK_LAUNCH();
   return TZR_OK;
@@ -285,11 +260,11 @@ extern "C" int tzr_cross_bwd(const float* d_grad_y, int64_t gy_stride, const flo
     else if (L <= 4) CN_BWD_L(KR_, 4); \
     else CN_BWD_L(KR_, 8);             \
   } while (0)
-  CN_BY_KR(CN_BWD);
+  TZR_BY_KR(CN_BWD);
 #undef CN_BWD
 #undef CN_BWD_L
   TZR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tzr_cross_bwd_finish_kernel, dim3((unsigned)((D + TZR_WAVE - 1) / TZR_WAVE), (unsigned)(L + 1)), dim3(CN_FIN_THREADS), 0,
+  hipLaunchKernelGGL(tzr_cross_bwd_finish_kernel, dim3((unsigned)((D + TZR_WAVE - 1) / TZR_WAVE), (unsigned)(L + 1)), dim3(TZR_FIN_THREADS), 0,
                      st, parts, (int)grid, P, L, D, d_dw, d_db);
   TZR_CHECK_LAUNCH();
   return TZR_OK;

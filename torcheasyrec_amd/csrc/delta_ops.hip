@@ -46,7 +46,7 @@ __global__ __launch_bounds__(DL_THREADS) void tzr_delta_mark_kernel(
 
 // Sum over the workgroup; result valid in every thread.  `red`: DL_THREADS / TZR_WAVE slots of LDS.
 __device__ __forceinline__ unsigned dl_block_sum(unsigned v, unsigned* red) {
-  for (int d = TZR_WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  v = tzr_wave_sum(v);
   const int wave = threadIdx.x / TZR_WAVE;
   __syncthreads();  // red may still be read by the previous call
   if ((threadIdx.x & (TZR_WAVE - 1)) == 0) red[wave] = v;

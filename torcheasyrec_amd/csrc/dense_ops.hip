@@ -13,6 +13,7 @@
 //
 // They are bandwidth-light; what they buy is launch count and one re-read of the gradient.  Deterministic: fixed-order
 // reductions, no float atomics.
+#include "parts_sum.h"
 #include "tzr_common.h"
 
 #define DN_THREADS 256
@@ -120,7 +121,7 @@ extern "C" int tzr_bce_logits(const float* d_logits, const void* d_labels, int l
 // ---- ReLU backward + bias gradient ---------------------------------------------------------------
 // g = gy * (y > 0) and colsum[n] = sum_b g[b, n] from one pass over gy / y (PyTorch: threshold_backward
 // then a separate column reduction that re-reads g).  Row tiles accumulate per-thread column sums in a
-// fixed order, workgroup partials go to the workspace, a second launch adds them in index order.
+// fixed order, workgroup partials go to the workspace, a second launch adds them in the interleaved order of parts_sum.h.
 #define RB_THREADS 256
 #define RB_MAX_WG 1024
 
@@ -171,38 +172,6 @@ __global__ __launch_bounds__(RB_THREADS) void tzr_relu_bwd_colsum_kernel(
   }
 }
 
-// Column sums of parts[n_wg][N]: one workgroup per 64 columns, 16 slices of the partials per column
-// summed concurrently with 8 independent loads in flight each (a serial walk over 1024 partials is
-// 60 us of pure latency), then combined in slice order.
-#define RB_FIN_THREADS 1024
-__global__ __launch_bounds__(RB_FIN_THREADS) void tzr_colsum_finish_kernel(const float* __restrict__ parts,
-                                                                            int n_wg, int N,
-                                                                            float* __restrict__ out) {
-  __shared__ float red[RB_FIN_THREADS];
-  const int col = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int slice = threadIdx.x >> 6;  // 0..15
-  float t = 0.f;
-  if (col < N) {
-    for (int k0 = slice; k0 < n_wg; k0 += 16 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int k = k0 + 16 * u;
-        v[u] = k < n_wg ? parts[(size_t)k * N + col] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t += v[u];
-    }
-  }
-  red[threadIdx.x] = t;
-  __syncthreads();
-  if (slice == 0 && col < N) {
-    float r = 0.f;
-    for (int sl = 0; sl < 16; ++sl) r += red[sl * 64 + (threadIdx.x & 63)];
-    out[col] = r;
-  }
-}
-
 extern "C" size_t tzr_relu_bwd_colsum_workspace(int64_t B, int N) {
   (void)B;
   return (size_t)RB_MAX_WG * (size_t)std::max(N, 4) * sizeof(float) + 256;
@@ -231,7 +200,7 @@ static int relu_bwd_colsum_impl(const float* d_grad_y, int64_t grad_y_stride, co
   hipLaunchKernelGGL(tzr_relu_bwd_colsum_kernel, dim3((unsigned)n_wg), dim3(RB_THREADS), 0, s, d_grad_y,
                      grad_y_stride, d_y, y_stride, B, N, rows_per_wg, d_grad, grad_stride, parts);
   if (d_colsum)
-    hipLaunchKernelGGL(tzr_colsum_finish_kernel, dim3((unsigned)((N + 63) / 64)), dim3(RB_FIN_THREADS), 0, s, parts,
+    hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((N + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s, parts,
                        (int)n_wg, N, d_colsum);
   if (out_G) *out_G = (int)n_wg;
   TZR_CHECK_LAUNCH();
@@ -330,7 +299,7 @@ extern "C" int tzr_head_bwd(const float* d_grad_y, int64_t grad_y_stride, const 
   float* parts = static_cast<float*>(ws);
   hipLaunchKernelGGL(tzr_head_bwd_kernel, dim3((unsigned)n_wg), dim3(RB_THREADS), 0, s, d_grad_y, grad_y_stride,
                      d_x, x_stride, d_w, B, N, rows_per_wg, d_grad_x, grad_x_stride, parts);
-  hipLaunchKernelGGL(tzr_colsum_finish_kernel, dim3((unsigned)((N + 4 + 63) / 64)), dim3(RB_FIN_THREADS), 0, s,
+  hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((N + 4 + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s,
                      parts, (int)n_wg, N + 4, d_grad_wb);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
@@ -428,7 +397,7 @@ extern "C" int tzr_head_bwd_relu(const float* d_grad_y, int64_t grad_y_stride, c
   float* parts = static_cast<float*>(ws);
   hipLaunchKernelGGL(tzr_head_bwd_relu_kernel, dim3((unsigned)n_wg), dim3(RB_THREADS), 0, s, d_grad_y, grad_y_stride,
                      d_x, x_stride, d_w, B, N, rows_per_wg, d_grad, grad_stride, parts);
-  hipLaunchKernelGGL(tzr_colsum_finish_kernel, dim3((unsigned)((2 * N + 4 + 63) / 64)), dim3(RB_FIN_THREADS), 0, s,
+  hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((2 * N + 4 + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s,
                      parts, (int)n_wg, 2 * N + 4, d_sums);
   TZR_CHECK_LAUNCH();
   return TZR_OK;
@@ -631,7 +600,7 @@ static int skinny_linear_bwd_impl(const float* d_grad_y, int64_t grad_y_stride, 
   else SK_BWD(8);
 #undef SK_BWD
   if (d_grad_wb)
-    hipLaunchKernelGGL(tzr_colsum_finish_kernel, dim3((unsigned)((row_len + 63) / 64)), dim3(RB_FIN_THREADS), 0, s, parts, (int)n_wg,
+    hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((row_len + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s, parts, (int)n_wg,
                        row_len, d_grad_wb);
   if (out_G) *out_G = (int)n_wg;
   if (out_P) *out_P = row_len;

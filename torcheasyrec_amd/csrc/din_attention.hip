@@ -219,14 +219,6 @@ __device__ __forceinline__ float da_group16_sum(float v) {
   v += __shfl_xor(v, 8);
   return v;
 }
-__device__ __forceinline__ float da_wave_max(float v) {
-  for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-  return v;
-}
-__device__ __forceinline__ float da_wave_sum(float v) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // row_n . w for the positions [s, s + len) of one sample -> sc[0 .. len) (LDS of this wave); lanes (g = lane / 16, j = lane % 16)
 __device__ __forceinline__ void da_row_dots(const float* __restrict__ rows, int64_t stride, int64_t s, int len, int cols4,
@@ -274,14 +266,14 @@ __global__ __launch_bounds__(DA_THREADS) void tzr_din_attn_fwd_kernel(
     __builtin_amdgcn_wave_barrier();
     float mx = -3.402823466e38f;
     for (int i = lane; i < len; i += TZR_WAVE) mx = fmaxf(mx, sc[i]);
-    mx = da_wave_max(mx);
+    mx = tzr_wave_max(mx);
     float sum = 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) {
       const float ex = expf(sc[i] - mx);
       sc[i] = ex;
       sum += ex;
     }
-    sum = da_wave_sum(sum);  // (fixed tree)
+    sum = tzr_wave_sum(sum);  // (fixed tree)
     const float inv = len > 0 ? 1.0f / sum : 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) {
       const float pi = sc[i] * inv;
@@ -348,7 +340,7 @@ __global__ __launch_bounds__(DA_THREADS) void tzr_din_attn_bwd_kernel(
     __builtin_amdgcn_wave_barrier();
     float dot = 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) dot = fmaf(p[s + i], sc[i], dot);
-    dot = da_wave_sum(dot);
+    dot = tzr_wave_sum(dot);
     for (int i = lane; i < len; i += TZR_WAVE) ds[s + i] = p[s + i] * (sc[i] - dot);
     for (int k = lane; k < len * lg; k += TZR_WAVE) {
       const int i = k / lg, c = k - i * lg;

@@ -1,13 +1,14 @@
 // What the one-launch dense optimizers (csrc/adam_fused.hip, csrc/dense_optim_fused.hip) share: the table of gradient sources
 // of a launch, the host code that lays a launch out, the summation of a gradient element out of its source, Adam's element and
-// the arrival tree that moves a tensor's step count on.  The summation exists ONCE, here: both entries add a gradient up in the
-// same order.
+// the arrival tree that moves a tensor's step count on.  Both entries add a gradient up through fused_grad_each, and that adds
+// partial-sum rows by parts_sum.h's blocked order: the summation exists once.
 #pragma once
 #include <tzr_gfx950.h>
 
 #include <algorithm>
 #include <cstring>
 
+#include "parts_sum.h"
 #include "tzr_common.h"
 #include "wgrad_reduce.h"
 
@@ -58,31 +59,10 @@ __device__ __forceinline__ void fused_grad_each(const FusedSrc& src, const WgRed
     const float* __restrict__ g = src.parts ? src.parts : grad;
     for (int64_t i = (int64_t)lb * 256 + threadIdx.x; i < numel; i += (int64_t)nblk * 256) f(i, g[i]);
   } else if (src.kind == 1) {
-    // tzr_mlp_finish_kernel's sum: 16 outputs per workgroup x 16 slices of the partial rows, a thread adds its slice's partials
-    // (8 loads in flight), thread (o, slice 0) adds the 16 slice sums in slice order
-    const int ol = threadIdx.x & 15, sq = threadIdx.x >> 4;
-    const int64_t o = (int64_t)lb * 16 + ol;
-    const int per = (src.G + 15) / 16;
-    const int g0 = sq * per, g1 = min(src.G, g0 + per);
-    float v = 0.f;
-    if (o < numel) {
-      const float* col = src.parts + src.col + o;
-      for (int g = g0; g < g1; g += 8) {
-        float t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = g + j < g1 ? col[(size_t)(g + j) * src.P] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v += t[j];
-      }
-    }
-    sl[sq][ol] = v;
-    __syncthreads();
-    if (sq == 0 && o < numel) {
-      v = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v += sl[q][ol];
-      f(o, v);
-    }
+    // 16 outputs per workgroup, added in the blocked order of parts_sum.h (tzr_mlp_finish_kernel's too)
+    const int64_t o = (int64_t)lb * 16 + (threadIdx.x & 15);
+    const float v = tzr_parts_sum_blocked(o < numel ? src.parts + src.col + o : nullptr, src.G, (size_t)src.P, sl);
+    if (threadIdx.x < 16 && o < numel) f(o, v);
   } else {
     const int lane = threadIdx.x & 63;
     const int o = (lb * 4 + (int)(threadIdx.x >> 6)) * 16 + (lane & 15);

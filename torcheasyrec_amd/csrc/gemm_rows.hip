@@ -24,6 +24,7 @@
 //   the workgroups' partial sums in workgroup order: no float atomics, bit-reproducible.
 #include <tzr_gfx950.h>
 
+#include "parts_sum.h"
 #include "tzr_common.h"
 
 #define GR_TS 16
@@ -300,33 +301,14 @@ __global__ __launch_bounds__(WAVES* TZR_WAVE) TZR_WAVES_PER_EU(WPE) void tzr_gem
       for (int j = 0; j < 4; ++j) tzr_stg(mine + (size_t)(16 * (wv * HBW + i) + 4 * q + j) * K + 16 * kb + r, acc[i][kb][j]);
 }
 
-// dW[e] = sum over the workgroups of parts[.][e], in workgroup order (16 slices summed concurrently with 8 loads in flight each,
-// combined in slice order -- tzr_linear_bwd_finish_kernel's arrangement)
-#define GR_FIN_THREADS 1024
-__global__ __launch_bounds__(GR_FIN_THREADS) void tzr_gemm_tn_finish_kernel(const float* __restrict__ parts, int n_wg, int H, int K,
-                                                                            float* __restrict__ dw, int64_t dw_stride, int accumulate) {
-  __shared__ float red[GR_FIN_THREADS];
+// dW[e] = sum over the workgroups of parts[.][e] (the interleaved order of parts_sum.h), stored into the caller's rows
+__global__ __launch_bounds__(TZR_FIN_THREADS) void tzr_gemm_tn_finish_kernel(const float* __restrict__ parts, int n_wg, int H, int K,
+                                                                             float* __restrict__ dw, int64_t dw_stride, int accumulate) {
+  __shared__ float red[TZR_FIN_THREADS];
   const int E = H * K;
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int slice = threadIdx.x >> 6;
-  float t = 0.f;
-  if (e < E) {
-    for (int k0 = slice; k0 < n_wg; k0 += 16 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int k = k0 + 16 * u;
-        v[u] = k < n_wg ? tzr_ldg(parts + (size_t)k * E + e) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t += v[u];
-    }
-  }
-  red[threadIdx.x] = t;
-  __syncthreads();
-  if (slice == 0 && e < E) {
-    float s = 0.f;
-    for (int sl = 0; sl < 16; ++sl) s += red[sl * 64 + (threadIdx.x & 63)];
+  const int e = blockIdx.x * TZR_WAVE + (threadIdx.x & (TZR_WAVE - 1));
+  const float s = tzr_parts_sum_interleaved(e < E ? parts + e : nullptr, n_wg, (size_t)E, red);
+  if (threadIdx.x < TZR_WAVE && e < E) {
     float* const o = dw + (int64_t)(e / K) * dw_stride + e % K;
     *o = accumulate ? *o + s : s;
   }
@@ -488,7 +470,7 @@ extern "C" int tzr_linear_rows_wgrad(const float* d_g, int64_t g_stride, const f
   TN_CASE(128, 128, 2, 8, 4) TN_CASE(128, 144, 2, 9, 4) TN_CASE(128, 192, 2, 12, 4) TN_CASE(128, 256, 2, 16, 4) TN_CASE(256, 48, 4, 3, 4)
   TN_CASE(256, 64, 4, 4, 4) TN_CASE(256, 96, 4, 6, 4) TN_CASE(256, 128, 4, 8, 4) TN_CASE(256, 144, 4, 9, 4) { return TZR_ERR_UNSUPPORTED; }
 #undef TN_CASE
-  hipLaunchKernelGGL(tzr_gemm_tn_finish_kernel, dim3((unsigned)((H * K + 63) / 64)), dim3(GR_FIN_THREADS), 0, s, parts, grid, H, K, d_dw,
+  hipLaunchKernelGGL(tzr_gemm_tn_finish_kernel, dim3((unsigned)((H * K + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s, parts, grid, H, K, d_dw,
                      dw_stride, accumulate);
   TZR_CHECK_LAUNCH();
   return TZR_OK;

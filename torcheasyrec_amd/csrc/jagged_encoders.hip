@@ -38,14 +38,6 @@ __device__ __forceinline__ float4 je_across_groups(float4 a, int P) {  // same p
   }
   return a;
 }
-__device__ __forceinline__ float je_wave_max(float v) {
-  for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-  return v;
-}
-__device__ __forceinline__ float je_wave_sum(float v) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 __device__ __forceinline__ float je_dot4(float4 a, float4 b) {
   float d = a.x * b.x;
   d = fmaf(a.y, b.y, d); d = fmaf(a.z, b.z, d); d = fmaf(a.w, b.w, d);
@@ -96,14 +88,14 @@ __global__ __launch_bounds__(JE_THREADS) void tzr_jagged_dot_attn_fwd_kernel(
     __builtin_amdgcn_wave_barrier();
     float mx = -3.402823466e38f;
     for (int i = lane; i < len; i += TZR_WAVE) mx = fmaxf(mx, sc[i]);
-    mx = je_wave_max(mx);
+    mx = tzr_wave_max(mx);
     float sum = 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) {
       const float ex = expf(sc[i] - mx);
       sc[i] = ex;
       sum += ex;
     }
-    sum = je_wave_sum(sum);  // (fixed tree)
+    sum = tzr_wave_sum(sum);  // (fixed tree)
     const float inv = len > 0 ? 1.0f / sum : 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) {
       const float pi = sc[i] * inv;
@@ -188,7 +180,7 @@ __global__ __launch_bounds__(JE_THREADS) void tzr_jagged_dot_attn_bwd_kernel(
     __builtin_amdgcn_wave_barrier();
     float dot = 0.f;
     for (int i = lane; i < len; i += TZR_WAVE) dot = fmaf(p[s + i], sc[i], dot);
-    dot = je_wave_sum(dot);
+    dot = tzr_wave_sum(dot);
     for (int i = lane; i < len; i += TZR_WAVE) sc[i] = p[s + i] * (sc[i] - dot);  // ds_i
     __builtin_amdgcn_wave_barrier();
     // dk_i = p_i g_b + ds_i q_b;  dq_b = sum_i ds_i k_i (a group in position order, the groups by a fixed tree)

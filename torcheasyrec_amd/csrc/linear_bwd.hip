@@ -21,9 +21,10 @@
 // workgroup barrier per tile, the next tile's global load in flight across it).
 //
 // Column sums: per-lane running sums over the workgroup's tiles, reduced over the 16 row lanes at the end, one row of
-// partial sums per workgroup, added in workgroup order by a second launch: no float atomics, bit-reproducible.
+// partial sums per workgroup, added by a second launch (the interleaved order of parts_sum.h): no float atomics, bit-reproducible.
 #include <tzr_gfx950.h>
 
+#include "parts_sum.h"
 #include "tzr_common.h"
 
 #define LB_WAVES 4
@@ -121,36 +122,6 @@ __global__ __launch_bounds__(LB_THREADS) TZR_WAVES_PER_EU(3) void tzr_linear_bwd
   }
 }
 
-// out[c] = sum over the workgroups' rows of parts[.][c], in row order (16 slices of the rows summed concurrently with 8
-// loads in flight each, then combined in slice order: the arrangement of tzr_colsum_finish_kernel, dense_ops.hip)
-#define LB_FIN_THREADS 1024
-__global__ __launch_bounds__(LB_FIN_THREADS) void tzr_linear_bwd_finish_kernel(const float* __restrict__ parts, int n_wg, int H,
-                                                                                float* __restrict__ out) {
-  __shared__ float red[LB_FIN_THREADS];
-  const int col = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int slice = threadIdx.x >> 6;
-  float t = 0.f;
-  if (col < H) {
-    for (int k0 = slice; k0 < n_wg; k0 += 16 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int k = k0 + 16 * u;
-        v[u] = k < n_wg ? parts[(size_t)k * H + col] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t += v[u];
-    }
-  }
-  red[threadIdx.x] = t;
-  __syncthreads();
-  if (slice == 0 && col < H) {
-    float s = 0.f;
-    for (int sl = 0; sl < 16; ++sl) s += red[sl * 64 + (threadIdx.x & 63)];
-    out[col] = s;
-  }
-}
-
 extern "C" int tzr_linear_bwd_relu_supported(int K, int H) {
   return (K == 16 || K == 32 || K == 64) && (H == 64 || H == 128 || H == 256) ? 1 : 0;
 }
@@ -190,7 +161,7 @@ extern "C" int tzr_linear_bwd_relu(const float* d_grad_in, int64_t grad_in_strid
     return TZR_ERR_UNSUPPORTED;
   }
 #undef LB_CASE
-  hipLaunchKernelGGL(tzr_linear_bwd_finish_kernel, dim3((unsigned)((H + 63) / 64)), dim3(LB_FIN_THREADS), 0, s, parts, grid, H,
+  hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((H + 63) / 64)), dim3(TZR_FIN_THREADS), 0, s, parts, grid, H,
                      d_colsum);
   TZR_CHECK_LAUNCH();
   return TZR_OK;

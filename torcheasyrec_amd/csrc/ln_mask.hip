@@ -21,9 +21,10 @@
 // on the same x, the stored mean and rstd, gamma and beta, so y > 0 decides the same way in both.
 //
 // Reduction order: a wave adds its samples in the order of the grid-stride loop, a workgroup its four waves 0..3, and the
-// finishing launch the workgroups' rows 0..G-1 (sixteen interleaved chains, then 0..15): a function of (B, D, n_out, shared_x)
+// finishing launch the workgroups' rows 0..G-1 in the interleaved order of parts_sum.h: a function of (B, D, n_out, shared_x)
 // alone.  No atomics.
-#include "tzr_common.h"
+#include "parts_sum.h"
+#include "row_kernels.h"
 
 #define LM_THREADS 256
 #define LM_WAVES (LM_THREADS / TZR_WAVE)
@@ -66,11 +67,6 @@ __device__ __forceinline__ T lm_pick(const T (&a)[LM_MAXOUT], int j) {  // a[j],
   return r;
 }
 
-__device__ __forceinline__ float lm_wave_sum(float v) {  // (fixed tree; every lane ends with the same sum)
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // the normalised element and the pre-activation: the forward's and the backward's one sequence
 __device__ __forceinline__ float lm_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
 __device__ __forceinline__ float lm_norm(float xh, float gamma, float beta) { return fmaf(xh, gamma, beta); }
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(LM_THREADS) void tzr_ln_mask_fwd_kernel(LmFwdParams
       f[k] = c < D ? x[b * xs + c] : 0.f;
       sum += f[k];
     }
-    const float mean = lm_wave_sum(sum) * inv_d;
+    const float mean = tzr_wave_sum(sum) * inv_d;
     float sq = 0.f;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(LM_THREADS) void tzr_ln_mask_fwd_kernel(LmFwdParams
       const float d = c < D ? f[k] - mean : 0.f;
       sq = fmaf(d, d, sq);
     }
-    const float rstd = 1.0f / sqrtf(lm_wave_sum(sq) * inv_d + eps);
+    const float rstd = 1.0f / sqrtf(tzr_wave_sum(sq) * inv_d + eps);
     if (lane == 0) {
       stats[(b * n_stat + slot) * 2] = mean;
       stats[(b * n_stat + slot) * 2 + 1] = rstd;
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(LM_THREADS) void tzr_ln_mask_fwd_kernel(LmFwdParams
   }
 }
 
-static inline unsigned lm_grid(int64_t B) { return (unsigned)std::min<int64_t>(LM_MAXGRID, (B + LM_WAVES - 1) / LM_WAVES); }
+static inline unsigned lm_grid(int64_t B) { return tzr_row_grid(B, LM_WAVES, LM_MAXGRID); }
 
 // floats of one workgroup's row of partial sums: [dgamma | dbeta]; the rows of slot s are s G .. s G + G - 1
 __host__ __device__ static inline size_t lm_row_len(int D) { return 2 * (size_t)D; }
@@ -206,8 +202,8 @@ __global__ __launch_bounds__(LM_THREADS) void tzr_ln_mask_bwd_kernel(LmBwdParams
       s1 += gf[k];
       s2 = fmaf(gf[k], xh[k], s2);
     }
-    s1 = lm_wave_sum(s1) * inv_d;
-    s2 = lm_wave_sum(s2) * inv_d;
+    s1 = tzr_wave_sum(s1) * inv_d;
+    s2 = tzr_wave_sum(s2) * inv_d;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
       const int c = lane + TZR_WAVE * k;
@@ -226,31 +222,16 @@ __global__ __launch_bounds__(LM_THREADS) void tzr_ln_mask_bwd_kernel(LmBwdParams
   }
 }
 
-// grid (D / 64 rounded up, 2, n_stat), LM_FIN_THREADS threads: workgroup (i, v, s) adds column tile i of vector v (0: dgamma,
-// 1: dbeta) of slot s over the G rows of partial sums -- wave k the rows k, k + 16, ..., then the waves 0..15 in order.
-#define LM_FIN_THREADS 1024
-#define LM_FIN_WAVES (LM_FIN_THREADS / TZR_WAVE)
-__global__ __launch_bounds__(LM_FIN_THREADS) void tzr_ln_mask_bwd_finish_kernel(const float* __restrict__ parts, int G, int D,
-                                                                                float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  __shared__ float red[LM_FIN_WAVES][TZR_WAVE];
-  const int lane = threadIdx.x & (TZR_WAVE - 1);
-  const int wv = threadIdx.x / TZR_WAVE;
+// grid (D / 64 rounded up, 2, n_stat), TZR_FIN_THREADS threads: workgroup (i, v, s) adds column tile i of vector v (0: dgamma,
+// 1: dbeta) of slot s over the G rows of partial sums (parts_sum.h: interleaved).
+__global__ __launch_bounds__(TZR_FIN_THREADS) void tzr_ln_mask_bwd_finish_kernel(const float* __restrict__ parts, int G, int D,
+                                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  __shared__ float red[TZR_FIN_THREADS];
   const int v = blockIdx.y, slot = blockIdx.z;
-  const int c = blockIdx.x * TZR_WAVE + lane;
+  const int c = blockIdx.x * TZR_WAVE + (threadIdx.x & (TZR_WAVE - 1));
   const size_t R = lm_row_len(D);
-  float a = 0.f;
-  if (c < D) {
-    const float* src = parts + (size_t)slot * G * R + (size_t)v * D + c;
-#pragma unroll 8
-    for (int w = wv; w < G; w += LM_FIN_WAVES) a += src[(size_t)w * R];
-  }
-  red[wv][lane] = a;
-  __syncthreads();
-  if (wv != 0 || c >= D) return;
-  float tot = red[0][lane];
-#pragma unroll
-  for (int k = 1; k < LM_FIN_WAVES; ++k) tot += red[k][lane];
-  (v == 0 ? dgamma : dbeta)[(size_t)slot * D + c] = tot;
+  const float tot = tzr_parts_sum_interleaved(c < D ? parts + (size_t)slot * G * R + (size_t)v * D + c : nullptr, G, R, red);
+  if (threadIdx.x < TZR_WAVE && c < D) (v == 0 ? dgamma : dbeta)[(size_t)slot * D + c] = tot;
 }
 
 static int lm_check(int64_t B, int D, int n_out) {
@@ -288,15 +269,6 @@ static int lm_vectors(const float* const* h_g, const float* const* h_b, int n, c
   return TZR_OK;
 }
 
-#define LM_BY_KR(LAUNCH)           \
-  do {                             \
-    if (D <= 64) LAUNCH(1);        \
-    else if (D <= 128) LAUNCH(2);  \
-    else if (D <= 256) LAUNCH(4);  \
-    else if (D <= 512) LAUNCH(8);  \
-    else LAUNCH(16);               \
-  } while (0)
-
 extern "C" int tzr_ln_mask_fwd(const float* const* h_x, const int64_t* h_x_stride, const float* const* h_gamma,
                                const float* const* h_beta, const float* const* h_m, const int64_t* h_m_stride, float* const* h_out,
                                const int64_t* h_out_stride, int n_out, int shared_x, int relu, float eps, int64_t B, int D,
@@ -319,7 +291,7 @@ extern "C" int tzr_ln_mask_fwd(const float* const* h_x, const int64_t* h_x_strid
 #define LM_FWD(KR_)                                                                                                              \
   hipLaunchKernelGGL((tzr_ln_mask_fwd_kernel<KR_>), grid, dim3(LM_THREADS), 0, static_cast<hipStream_t>(stream), P, n_out, shared_x ? 1 : 0, \
                      h_m ? 1 : 0, relu ? 1 : 0, eps, B, D, d_stats)
-  LM_BY_KR(LM_FWD);
+  TZR_BY_KR(LM_FWD);
 #undef LM_FWD
   TZR_CHECK_LAUNCH();
   return TZR_OK;
@@ -360,10 +332,10 @@ extern "C" int tzr_ln_mask_bwd(const float* const* h_gout, const int64_t* h_gout
 #define LM_BWD(KR_)                                                                                                               \
   hipLaunchKernelGGL((tzr_ln_mask_bwd_kernel<KR_>), grid, dim3(LM_THREADS), 0, st, P, n_out, shared_x ? 1 : 0, h_m ? 1 : 0, relu ? 1 : 0, B, \
                      D, d_stats, parts)
-  LM_BY_KR(LM_BWD);
+  TZR_BY_KR(LM_BWD);
 #undef LM_BWD
   TZR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tzr_ln_mask_bwd_finish_kernel, dim3((unsigned)((D + TZR_WAVE - 1) / TZR_WAVE), 2u, (unsigned)n_x), dim3(LM_FIN_THREADS),
+  hipLaunchKernelGGL(tzr_ln_mask_bwd_finish_kernel, dim3((unsigned)((D + TZR_WAVE - 1) / TZR_WAVE), 2u, (unsigned)n_x), dim3(TZR_FIN_THREADS),
                      0, st, parts, (int)G, D, d_dgamma, d_dbeta);
   TZR_CHECK_LAUNCH();
   return TZR_OK;

@@ -17,6 +17,7 @@
 // VALU kernels (no MFMA: K <= 64 products on tiles of 64 samples, operands in LDS, weights read as LDS broadcasts);
 // every reduction over the batch runs in a fixed order (per-workgroup partial sums over a fixed tile assignment, then
 // one finish pass in workgroup order): bit-reproducible, no float atomics.
+#include "parts_sum.h"
 #include "tzr_common.h"
 
 int g_tzr_mlp_mfma = 0;  // tzr_tune("mlp_mfma"): -1 = the general LDS-tiled kernels for every shape (A/B, tests); 0 = MFMA kernels where the shape fits
@@ -202,32 +203,13 @@ struct MlParts {
   float* dst[6];
   int n[6];
 };
-// 16 outputs per workgroup x 16 slices of the workgroup range: a thread adds its slice's partials (independent
-// loads, 8 in flight), thread (o, slice 0) then adds the 16 slice sums in slice order.  (One thread per output walking
-// all G partials was a chain of G dependent adds on strided loads: 120 us for G = 512.)
+// 16 outputs per workgroup, added in the blocked order of parts_sum.h
 __global__ __launch_bounds__(ML_THREADS) void tzr_mlp_finish_kernel(const float* __restrict__ parts, int G, int P,
                                                                     MlParts out) {
   __shared__ float sl[16][17];
-  const int ol = threadIdx.x & 15, sq = threadIdx.x >> 4;
-  const int o = blockIdx.x * 16 + ol;
-  const int per = (G + 15) / 16;
-  const int g0 = sq * per, g1 = min(G, g0 + per);
-  float v = 0.f;
-  if (o < P) {
-    for (int g = g0; g < g1; g += 8) {
-      float t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t[j] = g + j < g1 ? parts[(size_t)(g + j) * P + o] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v += t[j];
-    }
-  }
-  sl[sq][ol] = v;
-  __syncthreads();
-  if (sq != 0 || o >= P) return;
-  v = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) v += sl[q][ol];
+  const int o = blockIdx.x * 16 + (threadIdx.x & 15);
+  const float v = tzr_parts_sum_blocked(o < P ? parts + o : nullptr, G, (size_t)P, sl);
+  if (threadIdx.x >= 16 || o >= P) return;
   int base = 0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) {

@@ -70,6 +70,17 @@ __device__ __forceinline__ float4 tzr_add4(float4 a, float4 b) {
 }
 __device__ __forceinline__ float4 tzr_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
+// Sum / maximum over the 64 lanes of a wave by a fixed xor tree (masks 32, 16, .., 1): every lane ends with the same value.
+template <class T>
+__device__ __forceinline__ T tzr_wave_sum(T v) {
+  for (int m = TZR_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ float tzr_wave_max(float v) {
+  for (int m = TZR_WAVE / 2; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+
 // upper_bound(a[0..n), v) - 1 for a non-decreasing int64 array with a[0] <= v: index of the last
 // element <= v.
 __device__ __forceinline__ int64_t tzr_last_le(const int64_t* a, int64_t n, int64_t v) {

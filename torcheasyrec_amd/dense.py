@@ -373,7 +373,7 @@ def _loss_is_root(gl: Optional[torch.Tensor] = None) -> bool:
 # gradient do not run their finishing launches: the tensors they return to autograd are UNWRITTEN, and what they stand for is
 # noted here under the tensor's address; `FusedDenseAdam.step` adds the partial sums up on its way to the parameter update
 # (the order of additions of tzr_mlp2_bwd's finish and of the slice reduction: bit-identical to those; column sums that
-# tzr_colsum_finish_kernel would finish differ from it by fp32 rounding) and anything left over is written out by `materialize_pending`.  Who else reads such a
+# the interleaved finish of csrc/parts_sum.h would add differ from it by fp32 rounding) and anything left over is written out by `materialize_pending`.  Who else reads such a
 # gradient before the optimizer has run -- clipping, a collective, gradient accumulation -- calls `materialize_pending()` first;
 # the flag is the caller's statement that nothing does.
 FUSE_FINISH = False
@@ -517,7 +517,7 @@ PACKED_PARTIALS = [0]
 def pack_gradients(grads) -> Optional[torch.Tensor]:
     """torch.cat([g.reshape(-1) for g in grads]) in ONE launch that takes each gradient as it lies -- a finished tensor (copied) or
     the partial sums a backward left for the optimizer (added up on the way: bit-identical to the finishing launch for tzr_mlp2_bwd's
-    rows and the weight-gradient slices, equal up to fp32 rounding for rows tzr_colsum_finish_kernel would finish) -- the flat
+    rows and the weight-gradient slices, equal up to fp32 rounding for rows the interleaved finish of csrc/parts_sum.h would add) -- the flat
     buffer of the sharded step's dense all-reduce.  None: not a case for it (the caller concatenates)."""
     grads = list(grads)
     if not grads or any(g.dtype != torch.float32 or not g.is_contiguous() for g in grads) or _one_launch(grads) < len(grads):

@@ -140,10 +140,6 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(1) == 1 and _row_stride(t) >= t.shape[1] else t.contiguous()
 
 
-def _pointer_array(tensors):
-    return (C.c_void_p * len(tensors))(*[_lib.ptr(t) for t in tensors])
-
-
 class _CrossFn(torch.autograd.Function):
     """y = x_L of x_{l+1} = (x_l . w_l) x_0 + b_l + x_l: tzr_cross_fwd keeps the scalars x_l . w_l ([B, L]), tzr_cross_bwd
     returns the input gradient and the finished gradients of every w_l and b_l (rows of one [2, L, D] buffer)."""
@@ -155,7 +151,7 @@ class _CrossFn(torch.autograd.Function):
         params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
         y = torch.empty(B, D, dtype=torch.float32, device=x.device)
         s = torch.empty(B, L, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().tzr_cross_fwd(_lib.ptr(x), _row_stride(x), _pointer_array(params[:L]), _pointer_array(params[L:]), L, B, D,
+        rc = _lib.lib().tzr_cross_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), L, B, D,
                                       _lib.ptr(y), D, _lib.ptr(s), _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cross_fwd")
         ctx.save_for_backward(x, s, *params)
@@ -171,8 +167,8 @@ class _CrossFn(torch.autograd.Function):
         dwb = torch.empty(2, L, D, dtype=torch.float32, device=x.device)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_cross_bwd_workspace(B, D, L), x.device)
-        rc = lib.tzr_cross_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(s), _pointer_array(params[:L]),
-                               _pointer_array(params[L:]), L, B, D, _lib.ptr(dx), D, _lib.ptr(dwb[0]), _lib.ptr(dwb[1]), _lib.ptr(ws),
+        rc = lib.tzr_cross_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(s), _lib.ptr_array(params[:L]),
+                               _lib.ptr_array(params[L:]), L, B, D, _lib.ptr(dx), D, _lib.ptr(dwb[0]), _lib.ptr(dwb[1]), _lib.ptr(ws),
                                ws.numel(), _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cross_bwd")
         return (dx, None, *[dwb[0, l].view(1, D) for l in range(L)], *[dwb[1, l] for l in range(L)])
@@ -235,8 +231,8 @@ class _CINFn(torch.autograd.Function):
         save = any(ctx.needs_input_grad)
         xs = [torch.empty(B, o, D, dtype=torch.float32, device=x.device) for o in layers[:-1]] if save else []
         sizes = (C.c_int * L)(*layers)
-        rc = _lib.lib().tzr_cin_fwd(_lib.ptr(x), _row_stride(x), _pointer_array(params[:L]), _pointer_array(params[L:]), sizes, L, B, F, D,
-                                    _pointer_array(xs) if xs else None, _lib.ptr(y), y.shape[1], _lib.stream_ptr(x.device))
+        rc = _lib.lib().tzr_cin_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), sizes, L, B, F, D,
+                                    _lib.ptr_array(xs) if xs else None, _lib.ptr(y), y.shape[1], _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cin_fwd")
         ctx.save_for_backward(x, *params[:L], *xs)
         ctx.cfg, ctx.consumed = (F, D, tuple(layers)), False
@@ -260,8 +256,8 @@ class _CINFn(torch.autograd.Function):
         dwc = torch.empty(total, dtype=torch.float32, device=x.device)
         lib, sizes = _lib.lib(), (C.c_int * L)(*layers)
         ws = _lib.workspace(lib.tzr_cin_bwd_workspace(B, F, D, sizes, L), x.device)
-        rc = lib.tzr_cin_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _pointer_array(ws_), sizes, L, B, F, D,
-                             _pointer_array(xs) if xs else None, _lib.ptr(gx), F * D, _lib.ptr(dwc), _lib.ptr(ws), ws.numel(),
+        rc = lib.tzr_cin_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr_array(ws_), sizes, L, B, F, D,
+                             _lib.ptr_array(xs) if xs else None, _lib.ptr(gx), F * D, _lib.ptr(dwc), _lib.ptr(ws), ws.numel(),
                              _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cin_bwd")
         gws, gcs, off = [], [], 0

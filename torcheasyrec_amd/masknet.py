@@ -23,10 +23,6 @@ FUSED_MASKNET = True  # A/B switch: False = the reference's literal loop (nn.Lay
 LN_MASK_MAX_DIM, LN_MASK_MAX_OUT = 1024, 8  # LM_MAXDIM, LM_MAXOUT of csrc/ln_mask.hip
 
 
-def _pointers(ts: Sequence[torch.Tensor]):
-    return (C.c_void_p * len(ts))(*[_lib.ptr(t) for t in ts])
-
-
 def _strides(ts: Sequence[torch.Tensor]):
     return (C.c_int64 * len(ts))(*[_row_stride(t) for t in ts])
 
@@ -51,8 +47,8 @@ class _LnMaskFn(torch.autograd.Function):
         buf = torch.empty(B, n_out * D, dtype=torch.float32, device=dev)
         outs = [buf[:, j * D:(j + 1) * D] for j in range(n_out)]
         stats = torch.empty(B, n_x, 2, dtype=torch.float32, device=dev)
-        rc = _lib.lib().tzr_ln_mask_fwd(_pointers(xs), _strides(xs), _pointers(gammas), _pointers(betas), _pointers(ms) if ms else None,
-                                        _strides(ms) if ms else None, _pointers(outs), _strides(outs), n_out, int(shared), int(relu),
+        rc = _lib.lib().tzr_ln_mask_fwd(_lib.ptr_array(xs), _strides(xs), _lib.ptr_array(gammas), _lib.ptr_array(betas), _lib.ptr_array(ms) if ms else None,
+                                        _strides(ms) if ms else None, _lib.ptr_array(outs), _strides(outs), n_out, int(shared), int(relu),
                                         eps, B, D, _lib.ptr(stats), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_ln_mask_fwd")
         ctx.save_for_backward(stats, *xs, *gammas, *betas, *ms)
@@ -78,9 +74,9 @@ class _LnMaskFn(torch.autograd.Function):
         dgb = torch.empty(2, n_x, D, dtype=torch.float32, device=dev)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_ln_mask_bwd_workspace(B, D, n_out, int(shared)), dev)
-        rc = lib.tzr_ln_mask_bwd(_pointers(gouts), _strides(gouts), _pointers(xs), _strides(xs), _pointers(gammas), _pointers(betas),
-                                 _pointers(ms) if masked else None, _strides(ms) if masked else None, _lib.ptr(stats), n_out,
-                                 int(shared), int(relu), B, D, _pointers(gx), _strides(gx), _pointers(gm) if masked else None,
+        rc = lib.tzr_ln_mask_bwd(_lib.ptr_array(gouts), _strides(gouts), _lib.ptr_array(xs), _strides(xs), _lib.ptr_array(gammas), _lib.ptr_array(betas),
+                                 _lib.ptr_array(ms) if masked else None, _strides(ms) if masked else None, _lib.ptr(stats), n_out,
+                                 int(shared), int(relu), B, D, _lib.ptr_array(gx), _strides(gx), _lib.ptr_array(gm) if masked else None,
                                  _strides(gm) if masked else None, _lib.ptr(dgb[0]), _lib.ptr(dgb[1]), _lib.ptr(ws), ws.numel(),
                                  _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_ln_mask_bwd")
