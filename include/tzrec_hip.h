@@ -1013,6 +1013,44 @@ int tzr_cin_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, int6
                 const int* h_layers, int L, int64_t B, int F, int D, float* const* h_xs, float* d_gx, int64_t gx_stride,
                 float* d_dwc, void* ws, size_t ws_size, void* stream);
 
+/* The two per-sample operations of a WuKong layer outside its GEMMs (tzrec/modules/interaction.py:236-378).  csrc/wukong.hip.
+ * Per sample X [F, D] (row-major in x), k = compressed_feature_num, Fo = Ff + Fl (fmb_feature_num + lcb_feature_num):
+ *   tzr_wukong_fm_fwd   P = X^T W [D, k], Z = X P [F, k], d_out[b, :] = LN(vec(Z); gamma, beta, eps) over the F k values; W is
+ *                       fmb.weight [F, k], gamma / beta [F k].  d_stats [B, 2] contiguous takes (mean, rstd); P and Z never
+ *                       reach memory.  One launch.
+ *   tzr_wukong_fm_bwd   from gout, x, W, gamma and d_stats (P, Z recomputed): gX [B, F, D] into d_gx, and d_dparams =
+ *                       [dW F k | dgamma F k | dbeta F k] contiguous, finished.
+ *   tzr_wukong_mix_fwd  pre[o, :] = (o < Ff ? Fm[o, :] : 0) + sum_f Wc[f, o] X[f, :], Wc[f, o] = Wr[f, o] + (o >= Ff ? Wl[f, o - Ff] : 0),
+ *                       d_out[b, o, :] = LN(pre[o, :]; gamma, beta, eps) over D.  Fm [Ff, D] per sample in d_fm (feature_out_liner's
+ *                       row as it lies), Wl = lcb.weight [F, Fl], Wr = residual_projection.weight [F, Fo]; d_wr null: the
+ *                       identity residual (Wr[f, o] = (f == o), needs F == Fo).  d_stats [B, Fo, 2] contiguous.  One launch.
+ *   tzr_wukong_mix_bwd  from gout, x, fm, Wl, Wr, gamma and d_stats (pre recomputed): gX into d_gx, gFm [B, Ff, D] into d_gfm,
+ *                       and d_dparams = [dWr F Fo | dWl F Fl | dgamma D | dbeta D] contiguous, finished (dWr is written with a
+ *                       null d_wr too, and then means nothing).
+ * Each backward is two launches: the pass over the batch, which leaves one row of partial sums (the layout of d_dparams) per
+ * workgroup in `ws` (the *_bwd_workspace query's bytes, 256-byte aligned), and their sum in the interleaved order above.  LN is
+ * nn.LayerNorm's (biased variance, eps inside the root, the variance a second pass).  fp32; F, Fo, k in [1, 64], Ff, Fl >= 1, D in
+ * [1, 128], B < 2^30; strides are floats per sample, >= the sample's width (F D, F k, Ff D, Fo D); single-float loads and stores:
+ * 4-byte alignment, a column slice of a wider tensor is taken as it lies.  TZR_ERR_INVALID: a null pointer (d_wr excepted), B < 0,
+ * a size <= 0; TZR_ERR_UNSUPPORTED: outside the limits, a short stride, d_wr null with F != Fo; TZR_ERR_WORKSPACE: `ws` null,
+ * misaligned or shorter than the query less its 256 bytes of slack.  Every check precedes the first launch; B == 0 is TZR_OK
+ * without a launch.  No atomics; every sum's order is a function of the shapes alone: bit-reproducible.  Entry points only: the
+ * ABI version stays 15. */
+int tzr_wukong_fm_fwd(const float* d_x, int64_t x_stride, const float* d_w, const float* d_gamma, const float* d_beta, float eps,
+                      int64_t B, int F, int D, int k, float* d_out, int64_t out_stride, float* d_stats, void* stream);
+size_t tzr_wukong_fm_bwd_workspace(int64_t B, int F, int D, int k);
+int tzr_wukong_fm_bwd(const float* d_gout, int64_t gout_stride, const float* d_x, int64_t x_stride, const float* d_w,
+                      const float* d_gamma, const float* d_stats, int64_t B, int F, int D, int k, float* d_gx, int64_t gx_stride,
+                      float* d_dparams, void* ws, size_t ws_size, void* stream);
+int tzr_wukong_mix_fwd(const float* d_x, int64_t x_stride, const float* d_fm, int64_t fm_stride, const float* d_wl, const float* d_wr,
+                       const float* d_gamma, const float* d_beta, float eps, int64_t B, int F, int D, int Ff, int Fl, float* d_out,
+                       int64_t out_stride, float* d_stats, void* stream);
+size_t tzr_wukong_mix_bwd_workspace(int64_t B, int F, int D, int Ff, int Fl);
+int tzr_wukong_mix_bwd(const float* d_gout, int64_t gout_stride, const float* d_x, int64_t x_stride, const float* d_fm, int64_t fm_stride,
+                       const float* d_wl, const float* d_wr, const float* d_gamma, const float* d_stats, int64_t B, int F, int D, int Ff,
+                       int Fl, float* d_gx, int64_t gx_stride, float* d_gfm, int64_t gfm_stride, float* d_dparams, void* ws,
+                       size_t ws_size, void* stream);
+
 /* ---- native step driver (csrc/step_driver.hip) ------------------------------------------------------------------
  * Replaces the host side of a steady-state train step of tzrec's pipeline (tzrec/utils/dist_util.py:221-303: Python +
  * torch.distributed calls per collective) for a sharded step that was cut into captured hipGraphs: ONE call queues the

@@ -239,6 +239,13 @@ _SIGNATURES = {
     "tzr_ln_mask_bwd_workspace": (_sz, [_i64, _i32, _i32, _i32]),
     "tzr_ln_mask_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
+    "tzr_wukong_fm_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, C.c_float, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "tzr_wukong_fm_bwd_workspace": (_sz, [_i64, _i32, _i32, _i32]),
+    "tzr_wukong_fm_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "tzr_wukong_mix_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_float, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "tzr_wukong_mix_bwd_workspace": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "tzr_wukong_mix_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64,
+                                  _vp, _vp, _sz, _vp]),
     "tzr_comm_available": (_i32, [C.c_char_p]),
     "tzr_comm_version": (_i32, [C.c_char_p]),
     "tzr_comm_unique_id": (_i32, [C.c_char_p, _vp, _sz]),

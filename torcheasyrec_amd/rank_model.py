@@ -425,8 +425,78 @@ class ConfigMaskNet(RankModel):
         return self._output_to_prediction(self.output_linear(self.mask_net_layer(features)))
 
 
+class ConfigWuKong(RankModel):
+    """`wukong {...}` (tzrec/models/wukong.py:36-130): the sparse group as [B, F, D] rows -- the only group, or group `sparse`
+    beside an optional group `dense` whose `dense_mlp` output goes first as one more row -- through the WuKong layers, a
+    `final` MLP over the flattened last layer, a logits layer with bias.  `wukong { dense_mlp wukong_layers { lcb_feature_num
+    fmb_feature_num compressed_feature_num feature_num_mlp } final }` (protos/models/rank_model.proto, module.proto):
+    `compressed_feature_num` defaults to 16."""
+
+    _FIELDS = {"wukong": ("dense_mlp", "wukong_layers", "final"),
+               "wukong_layers": ("lcb_feature_num", "fmb_feature_num", "compressed_feature_num", "feature_num_mlp")}
+
+    @classmethod
+    def _block(cls, parent, where: str, name: str):
+        other = sorted(k for k in parent if k not in cls._FIELDS[where])
+        if other:
+            raise ValueError(f"wukong: {where} has no field {other[0]!r} (fields: {', '.join(cls._FIELDS[where])})")
+        if not parent.has(name):
+            raise ValueError(f"wukong: {where} needs `{name}`")
+        return parent.one(name)
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        names = eg.group_names()
+        self._sparse_group = names[0] if len(names) == 1 else "sparse"
+        self._dense_group = "dense"
+        final = self._block(m, "wukong", "final")
+        if not m.many("wukong_layers"):
+            raise ValueError("wukong: wukong needs `wukong_layers`")
+        self.dense_mlp = None
+        if len(names) > 1 and eg.has_group(self._dense_group):
+            if any("seq_encoder" in n for n in eg.group_feature_dims(self._dense_group)):
+                raise Exception("dense group not have sequence features.")
+            self.dense_mlp = mlp_from_msg(eg.group_total_dim(self._dense_group), self._block(m, "wukong", "dense_mlp"))
+        sparse_dims = eg.group_feature_dims(self._sparse_group)
+        if any("seq_encoder" in n for n in sparse_dims):
+            raise Exception("sparse group not have sequence features.")
+        dims = set(sparse_dims.values())
+        if len(dims) > 1:
+            raise Exception(f"sparse group feature dims must be the same, but we find {dims}")
+        self._dim = dims.pop()
+        self._num_sparse = len(sparse_dims)
+        if self.dense_mlp and self._dim != self.dense_mlp.output_dim():
+            raise Exception("dense mlp last hidden_unit must be the same sparse feature dim")
+        from .wukong import WuKongLayer
+
+        self._wukong_layers = nn.ModuleList()
+        feature_num = self._num_sparse + (1 if self.dense_mlp else 0)
+        for layer in m.many("wukong_layers"):
+            layer = WuKongLayer(self._dim, feature_num, int(self._block(layer, "wukong_layers", "lcb_feature_num")),
+                                int(self._block(layer, "wukong_layers", "fmb_feature_num")), int(layer.one("compressed_feature_num", 16)),
+                                mlp_kwargs(self._block(layer, "wukong_layers", "feature_num_mlp")))
+            self._wukong_layers.append(layer)
+            feature_num = layer.output_feature_num()
+        self.final_mlp = mlp_from_msg(feature_num * self._dim, final)
+        self.output_mlp = OutputLinear(self.final_mlp.output_dim(), spec.num_class)
+        if device is not None:
+            for mod in (self.dense_mlp, self._wukong_layers, self.final_mlp, self.output_mlp):
+                if mod is not None:
+                    mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        g = self.build_input(batch)
+        feat = g[self._sparse_group].reshape(-1, self._num_sparse, self._dim)
+        if self.dense_mlp:
+            feat = torch.cat([self.dense_mlp(g[self._dense_group]).unsqueeze(1), feat], dim=1)
+        for layer in self._wukong_layers:
+            feat = layer(feat)
+        return self._output_to_prediction(self.output_mlp(self.final_mlp(feat.reshape(feat.size(0), -1))))
+
+
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1,
-           "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet}
+           "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
