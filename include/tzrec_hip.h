@@ -955,6 +955,32 @@ int tzr_cross_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, in
                   const float* const* h_w, const float* const* h_b, int L, int64_t B, int D, float* d_dx, int64_t dx_stride,
                   float* d_dw, float* d_db, void* ws, size_t ws_size, void* stream);
 
+/* The low-rank cross network of Deep & Cross v2, all L layers in one launch forward and two launches backward: replaces
+ * CrossV2.forward and its autograd (tzrec/modules/interaction.py:135-180).  csrc/cross_v2.hip.
+ *   tzr_cross_v2_fwd  x_0 = x; t_l = x_l U_l^T [B, R]; y_l = t_l V_l^T + c_l; x_{l+1} = x_0 * y_l + x_l; d_y = x_L.  One launch; no
+ *                     x_l passes through memory between layers.  Saved for the backward (both nullable: inference):
+ *                     d_xs [L-1, B, D] contiguous = x_1 .. x_{L-1} (not read or written when L == 1), d_t [L, B, R] contiguous =
+ *                     t_0 .. t_{L-1}.  y_l is never stored.
+ *   tzr_cross_v2_bwd  from g = d(loss)/d(y), x, d_xs and d_t: d_dx [B, D], d_du [L, R, D], d_dv [L, D, R] and d_dc [L, D]
+ *                     (contiguous; slice l is the finished gradient of U_l / V_l / c_l).  Two launches: the row pass, which
+ *                     recomputes y_l from t_l, writes d_dx and leaves dy_l [L, B, D] and dt_l [L, B, R] in `ws`
+ *                     (tzr_cross_v2_bwd_workspace(B, D, R, L) bytes, 256-byte aligned); and the weight-gradient pass, whose
+ *                     workgroups each own a 16-wide strip of one dV_l (with dc_l) or dU_l over the whole batch.
+ * h_u / h_v / h_c: HOST arrays of L device pointers (the reference's L separate [R, D] and [D, R] weights and [D] biases), read
+ * by the call and passed to the kernels by value.  fp32; any D in [1, 1024], R in [1, 64], L in [1, 8], row strides (in floats)
+ * >= D; rows and parameters need 4-byte alignment only.  TZR_ERR_INVALID: a null pointer (a misaligned workspace), B < 0,
+ * D <= 0, R <= 0, L <= 0; TZR_ERR_UNSUPPORTED: D > 1024, R > 64, L > 8, a stride below D, a workspace shorter than the query;
+ * B == 0 is TZR_OK without a launch.  Blocks of 16 rows per 256-thread workgroup, every product on the exact-fp32 MFMA.  No
+ * atomics and no partial rows; reduction order: t_l and dt_l a wave its quarter of K = D on eight interleaved chains added as a fixed tree, then the waves 0..3; dV_l,
+ * dU_l and dc_l a wave the 4-row steps w, w + 8, .. of the batch in order, then the waves 0..7 (dc_l: then the row residues
+ * 0..3) -- fixed by (B, D, R, L): bit-reproducible.  Entry points only, no struct or constant changes: the ABI version stays 15. */
+int tzr_cross_v2_fwd(const float* d_x, int64_t x_stride, const float* const* h_u, const float* const* h_v, const float* const* h_c,
+                     int L, int64_t B, int D, int R, float* d_y, int64_t y_stride, float* d_xs, float* d_t, void* stream);
+size_t tzr_cross_v2_bwd_workspace(int64_t B, int D, int R, int L);
+int tzr_cross_v2_bwd(const float* d_grad_y, int64_t gy_stride, const float* d_x, int64_t x_stride, const float* d_xs, const float* d_t,
+                     const float* const* h_u, const float* const* h_v, const float* const* h_c, int L, int64_t B, int D, int R,
+                     float* d_dx, int64_t dx_stride, float* d_du, float* d_dv, float* d_dc, void* ws, size_t ws_size, void* stream);
+
 /* LayerNorm, an optional ReLU and an optional elementwise mask over rows, up to eight outputs per launch: the non-GEMM work of
  * MaskNet (tzrec/modules/masknet.py:77-85, 142-161).  csrc/ln_mask.hip.
  *   tzr_ln_mask_fwd  f_j = act(LN(x_j; gamma_j, beta_j, eps)), act = ReLU (relu != 0) or identity; out_j = f_j * m_j, or f_j

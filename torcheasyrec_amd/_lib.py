@@ -232,6 +232,10 @@ _SIGNATURES = {
     "tzr_cross_fwd": (_i32, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp]),
     "tzr_cross_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_cross_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tzr_cross_v2_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "tzr_cross_v2_bwd_workspace": (_sz, [_i64, _i32, _i32, _i32]),
+    "tzr_cross_v2_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
+                                _vp]),
     "tzr_cin_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "tzr_cin_bwd_workspace": (_sz, [_i64, _i32, _i32, _vp, _i32]),
     "tzr_cin_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),

@@ -7,6 +7,8 @@ sparse block separately (no ``cat`` to build [B, 27, 16]) and writes
 ``[interactions | dense | sparse]`` in one pass (/root/reference/tzrec/models/dlrm.py:123-130).
 ``Cross`` is the cross network of Deep & Cross v1 with the reference's parameters (interaction.py:94-132), every layer
 of it in one launch per direction (csrc/cross_net.hip).
+``CrossV2`` is the low-rank cross network of Deep & Cross v2 with the reference's parameters (interaction.py:135-180), every
+layer of it in one launch forward and two backward (csrc/cross_v2.hip).
 ``CIN`` is the compressed interaction network of xDeepFM with the reference's parameters (interaction.py:183-233); the
 [B, H F, D] product tensor the reference builds per layer never exists (csrc/cin.hip).
 """
@@ -211,6 +213,88 @@ class Cross(nn.Module):
         for i in range(self.cross_num):  # the reference's literal form
             x1 = self.w[i](x1) * x + self.b[i] + x1
         return x1
+
+
+FUSED_CROSS_V2 = True  # A/B switch: False = the reference's literal loop (two GEMMs, a bias add, a multiply and an add per layer)
+CROSS_V2_MAX_DIM, CROSS_V2_MAX_RANK, CROSS_V2_MAX_LAYERS = 1024, 64, 8  # CV_MAXDIM, CV_MAXR, CV_MAXL of csrc/cross_v2.hip
+
+
+class _CrossV2Fn(torch.autograd.Function):
+    """y = x_L of x_{l+1} = x_0 * (x_l U_l^T V_l^T + c_l) + x_l: tzr_cross_v2_fwd keeps x_1 .. x_{L-1} ([L-1, B, D]) and every
+    t_l = x_l U_l^T ([L, B, r]) -- nothing when `save` is false (no gradient will be asked for); tzr_cross_v2_bwd returns the input gradient and the
+    finished gradients of every U_l, V_l and c_l (slices of three buffers)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, L: int, save: bool, *params: torch.Tensor):
+        x = _rows(x)
+        B, D = x.shape
+        params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
+        R = params[0].shape[0]
+        y = torch.empty(B, D, dtype=torch.float32, device=x.device)
+        xs = torch.empty(L - 1, B, D, dtype=torch.float32, device=x.device) if save else None
+        t = torch.empty(L, B, R, dtype=torch.float32, device=x.device) if save else None
+        rc = _lib.lib().tzr_cross_v2_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:2 * L]),
+                                         _lib.ptr_array(params[2 * L:]), L, B, D, R, _lib.ptr(y), D, _lib.ptr(xs), _lib.ptr(t),
+                                         _lib.stream_ptr(x.device))
+        _lib.check(rc, "tzr_cross_v2_fwd")
+        if save:
+            ctx.save_for_backward(x, xs, t, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        x, xs, t, *params = ctx.saved_tensors
+        B, D = x.shape
+        L = len(params) // 3
+        R = params[0].shape[0]
+        gy = _rows(gy)
+        dev = x.device
+        dx = torch.empty(B, D, dtype=torch.float32, device=dev)
+        du = torch.empty(L, R, D, dtype=torch.float32, device=dev)
+        dv = torch.empty(L, D, R, dtype=torch.float32, device=dev)
+        dc = torch.empty(L, D, dtype=torch.float32, device=dev)
+        lib = _lib.lib()
+        ws = _lib.workspace(lib.tzr_cross_v2_bwd_workspace(B, D, R, L), dev)
+        rc = lib.tzr_cross_v2_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(xs), _lib.ptr(t),
+                                  _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:2 * L]), _lib.ptr_array(params[2 * L:]), L, B, D, R,
+                                  _lib.ptr(dx), D, _lib.ptr(du), _lib.ptr(dv), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "tzr_cross_v2_bwd")
+        return (dx, None, None, *[du[l] for l in range(L)], *[dv[l] for l in range(L)], *[dc[l] for l in range(L)])
+
+
+class CrossV2(nn.Module):
+    """Cross layers of Deep & Cross v2 with low-rank kernels (https://arxiv.org/pdf/2008.13535), the reference module's
+    constructor, parameters, initialisation (nn.Linear's default) and forward (tzrec/modules/interaction.py:135-180):
+    `u_kernels.<i>.weight` [low_rank, input_dim], `v_kernels.<i>.weight` [input_dim, low_rank], `v_kernels.<i>.bias` [input_dim]."""
+
+    def __init__(self, input_dim: int, cross_num: int = 3, low_rank: int = 32) -> None:
+        super().__init__()
+        self.cross_num = cross_num
+        self._low_rank = low_rank
+        self._input_dim = input_dim
+        self.u_kernels = nn.ModuleList([nn.Linear(input_dim, low_rank, bias=False) for _ in range(cross_num)])
+        self.v_kernels = nn.ModuleList([nn.Linear(low_rank, input_dim, bias=True) for _ in range(cross_num)])
+
+    def output_dim(self) -> int:
+        return self._input_dim
+
+    def _fused_ok(self, x: torch.Tensor) -> bool:
+        from .dlrm import _on_emulator
+
+        return bool(FUSED_CROSS_V2 and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
+                    and 1 <= self.cross_num <= CROSS_V2_MAX_LAYERS and 1 <= x.shape[1] <= CROSS_V2_MAX_DIM
+                    and x.shape[1] == self._input_dim and 1 <= self._low_rank <= CROSS_V2_MAX_RANK
+                    and self.u_kernels[0].weight.dtype == torch.float32 and (x.is_cuda or _on_emulator()))
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if self._fused_ok(input):
+            params = [m.weight for m in self.u_kernels] + [m.weight for m in self.v_kernels] + [m.bias for m in self.v_kernels]
+            save = torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in params))  # (inference: nothing is kept)
+            return _CrossV2Fn.apply(input, self.cross_num, save, *params)
+        x_0 = x_l = input
+        for i in range(self.cross_num):  # the reference's literal form
+            x_l = x_0 * self.v_kernels[i](self.u_kernels[i](x_l)) + x_l
+        return x_l
 
 
 FUSED_CIN = True  # A/B switch: False = the reference's literal loop (einsum to [B, H F, D], Conv1d, sum per layer)

@@ -18,7 +18,7 @@ from .config import PipelineSpec
 from .dlrm import MLP, OutputLinear, _on_emulator
 from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
-from .interaction import CIN, Cross, FactorizationMachine, dot_interaction
+from .interaction import CIN, Cross, CrossV2, FactorizationMachine, dot_interaction
 from .losses import build_losses, output_to_prediction
 from .masknet import MaskNetModule
 
@@ -346,6 +346,53 @@ class ConfigDCNV1(RankModel):
         return self._output_to_prediction(self.output_linear(self.final_dnn(y)))
 
 
+class ConfigDCNV2(RankModel):
+    """`dcn_v2 {...}` (tzrec/models/dcn_v2.py:26-88): an optional `backbone` MLP over the (single) feature group, the low-rank
+    cross network over its output (over the group itself without one), an optional `deep` MLP over the group whose output goes
+    behind the cross output, a `final` MLP, a logits layer without bias.  `cross { cross_num low_rank }`
+    (protos/module.proto:87-92) is required and defaults to 3 layers of rank 32."""
+
+    _FIELDS = {"dcn_v2": ("backbone", "cross", "deep", "final"), "cross": ("cross_num", "low_rank")}
+
+    @classmethod
+    def _block(cls, parent, where: str, name: str, required: bool = True):
+        other = sorted(k for k in parent if k not in cls._FIELDS[where])
+        if other:
+            raise ValueError(f"dcn_v2: {where} has no field {other[0]!r} (fields: {', '.join(cls._FIELDS[where])})")
+        if not parent.has(name):
+            if required:
+                raise ValueError(f"dcn_v2: {where} needs `{name}`")
+            return None
+        return parent.one(name)
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        self._group = eg.group_names()[0]
+        d_in = eg.group_total_dim(self._group)
+        cross = self._block(m, "dcn_v2", "cross")
+        final = self._block(m, "dcn_v2", "final")
+        self._block(cross, "cross", "cross_num", required=False)  # (the block's own fields, by name)
+        backbone, deep = self._block(m, "dcn_v2", "backbone", required=False), self._block(m, "dcn_v2", "deep", required=False)
+        self.backbone = mlp_from_msg(d_in, backbone) if backbone is not None else None
+        self.cross = CrossV2(self.backbone.output_dim() if self.backbone is not None else d_in,
+                             cross_num=int(cross.one("cross_num", 3)), low_rank=int(cross.one("low_rank", 32)))
+        self.deep = mlp_from_msg(d_in, deep) if deep is not None else None
+        self.final_dnn = mlp_from_msg(self.cross.output_dim() + (self.deep.output_dim() if self.deep is not None else 0), final)
+        self.output_linear = OutputLinear(self.final_dnn.output_dim(), spec.num_class, bias=False)
+        if device is not None:
+            for mod in (self.backbone, self.cross, self.deep, self.final_dnn, self.output_linear):
+                if mod is not None:
+                    mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        features = self.build_input(batch)[self._group]
+        net = self.cross(self.backbone(features) if self.backbone is not None else features)
+        if self.deep is not None:
+            net = torch.cat([net, self.deep(features)], dim=-1)
+        return self._output_to_prediction(self.output_linear(self.final_dnn(net)))
+
+
 class ConfigXDeepFM(RankModel):
     """`xdeepfm {...}` (tzrec/models/xdeepfm.py:44-86): the compressed interaction network over the WIDE group, reshaped to
     [B, F, wide_embedding_dim] (16 when the config omits it, protos/models/rank_model.proto:69), a deep MLP over group `deep`,
@@ -496,7 +543,7 @@ class ConfigWuKong(RankModel):
 
 
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1,
-           "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
+           "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
