@@ -577,6 +577,42 @@ typedef struct TzrMoeMix {
 int tzr_moe_mix_fwd(const TzrMoeMix* h_mix, void* stream);
 int tzr_moe_mix_bwd(const TzrMoeMix* h_mix, void* stream);
 
+/* The gate-and-mix step of one CGC level of PLE (tzrec/modules/extraction_net.py:98-139), EVERY gate in one launch; unlike
+ * tzr_moe_mix_* each gate g mixes its own subset of the experts, sel[g][0 .. n_sel[g]) in the order of its logit columns:
+ *   probs_g[b,:] = softmax(logits_g[b, 0:n_sel[g]]),   out_g[b,:] = sum_j probs_g[b,j] * expert[sel[g][j]][b,:]
+ * forward: reads logits / expert, writes out and probs ([B, n_sel[g]] contiguous per gate, kept for the backward);
+ * backward: reads grad_out / expert / probs, writes d_expert_e[b,:] = sum over the gates g that hold e, in ascending g, of
+ * probs_g[b, j(e)] * grad_out_g[b,:] (stored once; zeros for an expert of no gate) and d_logits_g[b,j] = probs_g[b,j] *
+ * (<grad_out_g[b,:], expert[sel[g][j]][b,:]> - sum_k probs_g[b,k] <grad_out_g[b,:], expert[sel[g][k]][b,:]>).  Deterministic.
+ * fp32; H multiple of 4, <= 4096.  TZR_ERR_INVALID: a null or misaligned pointer ([B, H] operands 16 bytes, the others 4), a
+ * negative B, a non-positive H / n_experts / n_gates / n_sel, a sel entry outside [0, n_experts) or twice in one gate.
+ * TZR_ERR_UNSUPPORTED: over a limit (H, n_experts, n_gates, n_sel), a [B, H] row stride that is no multiple of 4 or below H, a
+ * logits / d_logits stride below n_sel.  B == 0: TZR_OK, nothing is read or written.  A refused call launches nothing. */
+#define TZR_CGC_MAX_EXPERTS 16
+#define TZR_CGC_MAX_GATES 5
+typedef struct TzrCgcMix {
+  int64_t B;
+  int32_t H, n_experts, n_gates, reserved;
+  uint64_t expert[TZR_CGC_MAX_EXPERTS];          /* const float* [B, H]                       */
+  int64_t expert_stride[TZR_CGC_MAX_EXPERTS];
+  uint64_t d_expert[TZR_CGC_MAX_EXPERTS];        /* float* [B, H]            (backward)       */
+  int64_t d_expert_stride[TZR_CGC_MAX_EXPERTS];
+  int32_t n_sel[TZR_CGC_MAX_GATES];              /* members of gate g                         */
+  int32_t reserved2[3];
+  int32_t sel[TZR_CGC_MAX_GATES][TZR_CGC_MAX_EXPERTS]; /* expert index of logit column j of gate g */
+  uint64_t logits[TZR_CGC_MAX_GATES];            /* const float* [B, n_sel[g]]    (forward)   */
+  int64_t logits_stride[TZR_CGC_MAX_GATES];
+  uint64_t probs[TZR_CGC_MAX_GATES];             /* float* [B, n_sel[g]] contiguous           */
+  uint64_t out[TZR_CGC_MAX_GATES];               /* float* [B, H]                 (forward)   */
+  int64_t out_stride[TZR_CGC_MAX_GATES];
+  uint64_t grad_out[TZR_CGC_MAX_GATES];          /* const float* [B, H]           (backward)  */
+  int64_t grad_out_stride[TZR_CGC_MAX_GATES];
+  uint64_t d_logits[TZR_CGC_MAX_GATES];          /* float* [B, n_sel[g]]          (backward)  */
+  int64_t d_logits_stride[TZR_CGC_MAX_GATES];
+} TzrCgcMix;
+int tzr_cgc_mix_fwd(const TzrCgcMix* h_mix, void* stream);
+int tzr_cgc_mix_bwd(const TzrCgcMix* h_mix, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

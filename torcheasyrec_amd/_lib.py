@@ -69,6 +69,27 @@ class TzrMoeMix(C.Structure):
     ]
 
 
+CGC_MAX_EXPERTS, CGC_MAX_GATES = 16, 5
+
+
+class TzrCgcMix(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("H", C.c_int32), ("n_experts", C.c_int32), ("n_gates", C.c_int32), ("reserved", C.c_int32),
+        ("expert", C.c_uint64 * CGC_MAX_EXPERTS), ("expert_stride", C.c_int64 * CGC_MAX_EXPERTS),
+        ("d_expert", C.c_uint64 * CGC_MAX_EXPERTS), ("d_expert_stride", C.c_int64 * CGC_MAX_EXPERTS),
+        ("n_sel", C.c_int32 * CGC_MAX_GATES), ("reserved2", C.c_int32 * 3),
+        ("sel", (C.c_int32 * CGC_MAX_EXPERTS) * CGC_MAX_GATES),
+        ("logits", C.c_uint64 * CGC_MAX_GATES), ("logits_stride", C.c_int64 * CGC_MAX_GATES),
+        ("probs", C.c_uint64 * CGC_MAX_GATES),
+        ("out", C.c_uint64 * CGC_MAX_GATES), ("out_stride", C.c_int64 * CGC_MAX_GATES),
+        ("grad_out", C.c_uint64 * CGC_MAX_GATES), ("grad_out_stride", C.c_int64 * CGC_MAX_GATES),
+        ("d_logits", C.c_uint64 * CGC_MAX_GATES), ("d_logits_stride", C.c_int64 * CGC_MAX_GATES),
+    ]
+
+
+assert C.sizeof(TzrCgcMix) == 1248
+
+
 class TzrSparseOptim(C.Structure):
     _fields_ = [
         ("kind", C.c_int32),
@@ -285,6 +306,8 @@ _SIGNATURES = {
     "tzr_head_bwd_relu": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tzr_moe_mix_fwd": (_i32, [_vp, _vp]),
     "tzr_moe_mix_bwd": (_i32, [_vp, _vp]),
+    "tzr_cgc_mix_fwd": (_i32, [_vp, _vp]),
+    "tzr_cgc_mix_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

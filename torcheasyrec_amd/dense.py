@@ -172,6 +172,90 @@ def moe_mix(logits, experts):
     return list(_MoeMixFn.apply(len(logits), *logits, *experts))
 
 
+class _CgcMixFn(torch.autograd.Function):
+    """out_g = softmax(logits_g) . experts[sels[g]] for every gate of one CGC level of PLE in one launch per direction
+    (tzr_cgc_mix_fwd / _bwd, csrc/cgc_mix.hip); inputs: the member lists, G gate-logit tensors [B, n_g], then E expert outputs
+    [B, H].  Capturable: nothing reads the device, every buffer is torch's."""
+
+    @staticmethod
+    def _fill(m, B, H, experts, sels):
+        m.B, m.H, m.n_experts, m.n_gates = B, H, len(experts), len(sels)
+        for e, x in enumerate(experts):
+            m.expert[e], m.expert_stride[e] = _lib.ptr(x), x.stride(0)
+        for g, sel in enumerate(sels):
+            m.n_sel[g] = len(sel)
+            for j, e in enumerate(sel):
+                m.sel[g][j] = e
+
+    @staticmethod
+    def forward(ctx, sels, *tensors):
+        G = len(sels)
+        logits = [t.contiguous() for t in tensors[:G]]
+        experts = [_rows16(t) for t in tensors[G:]]
+        B, H = experts[0].shape
+        dev = experts[0].device
+        m = _lib.TzrCgcMix()
+        _CgcMixFn._fill(m, B, H, experts, sels)
+        outs = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(G)]
+        probs = [torch.empty(B, len(sel), dtype=torch.float32, device=dev) for sel in sels]
+        for g in range(G):
+            m.logits[g], m.logits_stride[g] = _lib.ptr(logits[g]), logits[g].stride(0)
+            m.probs[g] = _lib.ptr(probs[g])
+            m.out[g], m.out_stride[g] = _lib.ptr(outs[g]), outs[g].stride(0)
+        _lib.check(_lib.lib().tzr_cgc_mix_fwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_cgc_mix_fwd")
+        ctx.save_for_backward(*probs, *experts)
+        ctx.sels = sels
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        sels = ctx.sels
+        G = len(sels)
+        probs, experts = ctx.saved_tensors[:G], ctx.saved_tensors[G:]
+        B, H = experts[0].shape
+        dev = experts[0].device
+        gs = [torch.zeros(B, H, dtype=torch.float32, device=dev) if g is None else _rows16(g.float()) for g in gouts]
+        m = _lib.TzrCgcMix()
+        _CgcMixFn._fill(m, B, H, experts, sels)
+        dx = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in experts]
+        dl = [torch.empty(B, len(sel), dtype=torch.float32, device=dev) for sel in sels]
+        for e in range(len(experts)):
+            m.d_expert[e], m.d_expert_stride[e] = _lib.ptr(dx[e]), dx[e].stride(0)
+        for g in range(G):
+            m.probs[g] = _lib.ptr(probs[g])
+            m.grad_out[g], m.grad_out_stride[g] = _lib.ptr(gs[g]), gs[g].stride(0)
+            m.d_logits[g], m.d_logits_stride[g] = _lib.ptr(dl[g]), dl[g].stride(0)
+        _lib.check(_lib.lib().tzr_cgc_mix_bwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_cgc_mix_bwd")
+        return (None, *dl, *dx)
+
+
+def cgc_mix_ok(logits, experts, sels) -> bool:
+    """what tzr_cgc_mix_* takes: fp32 experts [B, H] (H % 4 == 0, <= 4096, at most 16), at most 5 gates, gate g with logits
+    [B, len(sels[g])] over distinct experts sels[g], everything on the device of the loaded library"""
+    if not (0 < len(experts) <= _lib.CGC_MAX_EXPERTS and 0 < len(logits) <= _lib.CGC_MAX_GATES and len(sels) == len(logits)):
+        return False
+    x = experts[0]
+    if not (x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 4096):
+        return False
+    if not all(t.dtype == torch.float32 and t.shape == x.shape and t.device == x.device for t in experts):
+        return False
+    if (x.device.type == "cpu") != (_lib.backend() == "emu"):
+        return False
+    for lg, sel in zip(logits, sels):
+        if not (lg.dtype == torch.float32 and lg.device == x.device and lg.shape == (x.shape[0], len(sel)) and len(sel) > 0):
+            return False
+        if len(set(sel)) != len(sel) or not all(0 <= int(e) < len(experts) for e in sel):
+            return False
+    return True
+
+
+def cgc_mix(logits, experts, sels):
+    """[softmax(logits_g) . [experts[e] for e in sels[g]] for g] -- the gate-and-mix step of one CGC level of PLE
+    (tzrec/modules/extraction_net.py:98-139) -- one launch for all gates; an expert of several gates is read once."""
+    sels = tuple(tuple(int(e) for e in sel) for sel in sels)
+    return list(_CgcMixFn.apply(sels, *logits, *experts))
+
+
 SKINNY_MAX_OUT = 8  # output units up to which a Linear layer takes tzr_skinny_linear_* (csrc/dense_ops.hip)
 
 

@@ -268,38 +268,25 @@ class MMoE(nn.Module):
         return [torch.matmul(torch.softmax(lg, dim=1).unsqueeze(1), experts).squeeze(1) for lg in logits]
 
 
-class ConfigMMoE(RankModel):
-    """`mmoe {...}` (tzrec/models/mmoe.py:36-96): the MMoE module over the (single) feature group and
-    a task tower (MLP + logits layer) per task.  Predictions and losses carry the tower name as
-    suffix, as the reference's multi-task models do."""
+class MultiTaskRankModel(RankModel):
+    """What the multi-task models share (tzrec/models/multi_task_rank.py): a task tower (optional MLP + logits layer) per
+    `task_towers` block; predictions and losses carry the tower name as suffix."""
 
-    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
-        super().__init__(spec, device, sparse_optimizer)
-        eg, m = self.embedding_group, spec.model
-        self._group = eg.group_names()[0]
-        d_in = eg.group_total_dim(self._group)
-        expert = mlp_kwargs(m.one("expert_mlp"))
-        hidden = expert["hidden_units"]
-        gate = mlp_kwargs(m.one("gate_mlp")) if m.has("gate_mlp") else None
+    def _build_towers(self, m, in_dims) -> None:
+        """`in_dims[i]`: width of the tensor tower i reads"""
         self._towers = [(str(t.one("tower_name")), str(t.one("label_name"))) for t in m.many("task_towers")]
-        self.mmoe = MMoE(d_in, expert, int(m.one("num_expert")), len(self._towers), gate)
         self.task_mlps = nn.ModuleList()
         self.task_outputs = nn.ModuleList()
         self._tower_losses = [[l for l in self._losses if l.tower is not None and l.tower.tower_name == name] for name, _ in self._towers]
-        for t in m.many("task_towers"):
-            d = hidden[-1]
+        for t, d in zip(m.many("task_towers"), in_dims):
             if t.has("mlp"):
                 self.task_mlps.append(mlp_from_msg(d, t.one("mlp")))
                 d = self.task_mlps[-1].output_dim()
             else:
                 self.task_mlps.append(nn.Identity())
             self.task_outputs.append(OutputLinear(d, int(t.one("num_class", 1))))
-        if device is not None:
-            for mod in (self.mmoe, self.task_mlps, self.task_outputs):
-                mod.to(device)
 
-    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
-        task_inputs = self.mmoe(self.build_input(batch)[self._group])
+    def _tower_predictions(self, task_inputs) -> Dict[str, torch.Tensor]:
         out: Dict[str, torch.Tensor] = {}
         for i, (tower, _) in enumerate(self._towers):
             y = self.task_outputs[i](self.task_mlps[i](task_inputs[i]))
@@ -317,6 +304,89 @@ class ConfigMMoE(RankModel):
                 else:
                     out[l.name] = l(predictions, batch)
         return out
+
+
+class ConfigMMoE(MultiTaskRankModel):
+    """`mmoe {...}` (tzrec/models/mmoe.py:36-96): the MMoE module over the (single) feature group and
+    a task tower (MLP + logits layer) per task.  Predictions and losses carry the tower name as
+    suffix, as the reference's multi-task models do."""
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        self._group = eg.group_names()[0]
+        d_in = eg.group_total_dim(self._group)
+        expert = mlp_kwargs(m.one("expert_mlp"))
+        hidden = expert["hidden_units"]
+        gate = mlp_kwargs(m.one("gate_mlp")) if m.has("gate_mlp") else None
+        n_task = len(m.many("task_towers"))
+        self.mmoe = MMoE(d_in, expert, int(m.one("num_expert")), n_task, gate)
+        self._build_towers(m, [hidden[-1]] * n_task)
+        if device is not None:
+            for mod in (self.mmoe, self.task_mlps, self.task_outputs):
+                mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        return self._tower_predictions(self.mmoe(self.build_input(batch)[self._group]))
+
+
+class ConfigPLE(MultiTaskRankModel):
+    """`ple {...}` (tzrec/models/ple.py:27-109): stacked CGC levels (`extraction_networks`, ple.ExtractionNet) over the (single)
+    feature group -- level 0 feeds it to every task's experts and to the shared ones, the last level has no shared gate -- and
+    a task tower per task on the last level's task outputs.  Refused when built, by the level's name, what the reference
+    itself cannot run: a level without shared experts (`share_num` absent or 0) or without task experts, a level without
+    `share_expert_net` (the reference reads it unconditionally) or `task_expert_net`, task and shared experts of one level that
+    end in different widths (its `torch.stack` fails on the first batch), a field the block does not have."""
+
+    _LEVEL_FIELDS = ("network_name", "expert_num_per_task", "share_num", "task_expert_net", "share_expert_net")
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        from .ple import ExtractionNet
+
+        eg, m = self.embedding_group, spec.model
+        self._group = eg.group_names()[0]
+        d_in = eg.group_total_dim(self._group)
+        n_task = len(m.many("task_towers"))
+        levels = m.many("extraction_networks")
+        if not levels or n_task == 0:
+            raise ValueError("ple: needs at least one `extraction_networks` block and one `task_towers` block")
+        self._extraction_nets = nn.ModuleList()
+        in_tasks, in_shared = [d_in] * n_task, d_in
+        for i, lv in enumerate(levels):
+            name = str(lv.one("network_name", f"level{i}"))
+            other = sorted(k for k in lv if k not in self._LEVEL_FIELDS)
+            if other:
+                raise ValueError(f"ple: extraction_networks {name!r} has no field {other[0]!r} (fields: {', '.join(self._LEVEL_FIELDS)})")
+            share_num, per_task = int(lv.one("share_num", 0)), int(lv.one("expert_num_per_task", 0))
+            if share_num <= 0:
+                raise ValueError(f"ple: extraction_networks {name!r} needs share_num >= 1 (the reference cannot run a level without shared experts)")
+            if per_task <= 0:
+                raise ValueError(f"ple: extraction_networks {name!r} needs expert_num_per_task >= 1")
+            for blk in ("share_expert_net", "task_expert_net"):
+                if not lv.has(blk):
+                    raise ValueError(f"ple: extraction_networks {name!r} needs `{blk}`")
+            share_net, task_net = mlp_kwargs(lv.one("share_expert_net")), mlp_kwargs(lv.one("task_expert_net"))
+            if not share_net["hidden_units"] or not task_net["hidden_units"]:
+                raise ValueError(f"ple: extraction_networks {name!r}: an expert net needs hidden_units")
+            if share_net["hidden_units"][-1] != task_net["hidden_units"][-1]:
+                raise ValueError(f"ple: extraction_networks {name!r}: task experts end {task_net['hidden_units'][-1]} wide, shared experts "
+                                 f"{share_net['hidden_units'][-1]}: one gate mixes both, the widths must be equal")
+            net = ExtractionNet(in_tasks, in_shared, name, share_num, per_task, share_net, task_net, final_flag=i == len(levels) - 1)
+            self._extraction_nets.append(net)
+            dims = net.output_dim()
+            in_tasks, in_shared = dims[:-1], dims[-1]
+        self._build_towers(m, in_tasks)
+        if device is not None:
+            for mod in (self._extraction_nets, self.task_mlps, self.task_outputs):
+                mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        net = self.build_input(batch)[self._group]
+        task_fea, shared_fea = [net] * len(self._towers), net
+        for level in self._extraction_nets:
+            task_fea, shared_fea = level(task_fea, shared_fea)
+        return self._tower_predictions(task_fea)
 
 
 class ConfigDCNV1(RankModel):
@@ -542,8 +612,8 @@ class ConfigWuKong(RankModel):
         return self._output_to_prediction(self.output_mlp(self.final_mlp(feat.reshape(feat.size(0), -1))))
 
 
-_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "dcn_v1": ConfigDCNV1,
-           "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
+_MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "ple": ConfigPLE,
+           "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
