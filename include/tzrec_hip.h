@@ -1309,6 +1309,29 @@ int tzr_dot_interaction_top_wgrad(const float* d_dense, int64_t dense_stride, co
                                   int H, const float* d_scale, float* d_dW1, int64_t ldw, void* d_ws, int64_t ws_bytes,
                                   void* stream);
 
+/* Two pairs of those launches as ONE launch each (csrc/interaction_phases.hip), DLRM-Criteo shape only (26 sparse vectors + the
+ * dense one, D = 16, H = 64): the neighbour runs as a phase of the persistent interaction kernel, on the samples the workgroup
+ * owns anyway.  Same bodies, same order of every addition: outputs bit-identical to the two calls they stand for.  (Added without
+ * a change to an existing signature or struct: the version stays, a library without them fails to bind.)
+ *   _top_fwd_mlp2: tzr_mlp2_fwd (its arguments first, without the stream) then tzr_dot_interaction_top_fwd_packed (its arguments,
+ *             without B) with the bottom MLP's output as the dense vector: d_dense == d_hb and dense_stride == hb_stride.  Writes
+ *             ha, hb and y1.  TZR_ERR_UNSUPPORTED for anything else than K0 <= 16, H1 = 64, H2 = 16 (16-byte aligned Wb and ha
+ *             rows), F = 26, d_z = null and a packed copy of W1.
+ *   _top_bwd_wgrad_parts: tzr_dot_interaction_top_bwd_packed (its arguments, without the stream) then the workspace and the
+ *             blob of tzr_dot_interaction_top_wgrad_parts: grad_dense / grad_sparse, and the weight gradient's batch slices in
+ *             d_ws described by *h_out for tzr_dense_adam_fused.  d_scale applies to both.  B > 0; d_dense non-null, F = 26. */
+int tzr_dot_interaction_top_fwd_mlp2(const float* d_x, int64_t x_stride, int64_t B, int K0, const float* d_Wa, const float* d_ba, int H1,
+                                     const float* d_Wb, const float* d_bb, int H2, float* d_ha, int64_t ha_stride, float* d_hb,
+                                     int64_t hb_stride, const float* d_dense, int64_t dense_stride, const float* d_sparse,
+                                     int64_t sparse_stride, int F, int D, const float* d_W1, int64_t ldw, const float* d_bias, int H,
+                                     int relu, float* d_z, int64_t z_stride, float* d_y1, int64_t y1_stride,
+                                     const float* d_W1_fwd_packed, void* stream);
+int tzr_dot_interaction_top_bwd_wgrad_parts(const float* d_dense, int64_t dense_stride, const float* d_sparse, int64_t sparse_stride,
+                                            int F, int D, int64_t B, const float* d_g1, int64_t g1_stride, int H, const float* d_W1,
+                                            int64_t ldw, const float* d_scale, float* d_grad_dense, int64_t grad_dense_stride,
+                                            float* d_grad_sparse, int64_t grad_sparse_stride, const float* d_W1_bwd_packed, void* d_ws,
+                                            int64_t ws_bytes, TzrWgradParts* h_out, void* stream);
+
 /* K10: FM second order.  Replaces tzrec FactorizationMachine.forward
  * (tzrec/modules/fm.py:27-42): out[b,:] = 0.5*((sum_f x_f)^2 - sum_f x_f^2), x:[B,F,D]. */
 int tzr_fm_fwd(const float* d_x, int64_t x_stride, int F, int D, int64_t B, float* d_out,

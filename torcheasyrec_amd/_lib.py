@@ -230,6 +230,11 @@ _SIGNATURES = {
                                                   _vp, _i64, _vp, _vp]),
     "tzr_dot_interaction_top_bwd_packed": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
                                                   _i64, _vp, _i64, _vp, _vp]),
+    "tzr_dot_interaction_top_fwd_mlp2": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _i64,
+                                                _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _i64,
+                                                _vp, _i64, _vp, _vp]),
+    "tzr_dot_interaction_top_bwd_wgrad_parts": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp,
+                                                       _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(TzrWgradParts), _vp]),
     "tzr_dot_interaction_top_wgrad_workspace": (_i64, [_i32, _i32, _i32, _i32]),
     "tzr_dot_interaction_top_wgrad": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp,
                                              _i64, _vp]),

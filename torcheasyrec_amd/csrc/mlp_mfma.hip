@@ -9,15 +9,13 @@
 // accumulator reg j of lane (r = l & 15, q = l >> 4) is D[row 4 q + j][col r].  A contraction index may be permuted freely
 // as long as both operands agree: rows of activations are read as one ds_read_b128 per four k-steps.
 #include "tzr_common.h"
+#include "mlp2_fwd16_body.h"  // MM_TS, MT_H1, MT_P1, MB_*, mm_f32x4 and the bottom MLP's forward body
 
 #define MM_WAVES 4
 #define MM_THREADS (MM_WAVES * TZR_WAVE)
-#define MM_TS 16
 #define MM_MAX_WG 512  // = ML_MAX_WG of mlp_ops.hip: rows of the partial-sum workspace
 
 extern int g_tzr_mlp_mfma;  // mlp_ops.hip: > 0 also caps the workgroups (tests: many tiles per wave on small batches)
-
-typedef float mm_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float mm_sum16(float v) {  // over the 16 lanes that share l >> 4 (all of them get the sum)
   v += __shfl_xor(v, 1);
@@ -36,9 +34,7 @@ __device__ __forceinline__ float mm_sum_q(float v) {  // over the 4 lanes that s
 // H1 = 64, H2 = 32.  Per tile: 32 + 32 + 32 MFMAs (y2; dW2 += g2^T y1; g1 = g2 W2), layouts changed through two
 // wave-private LDS tiles.  Partial-sum row of a workgroup (the layout tzr_mlp_finish_kernel reduces):
 // [dW2 (32 x 64) | db2 (32) | dw3 (32) | db3, loss (2) | db1 (64)].
-#define MT_H1 64
 #define MT_H2 32
-#define MT_P1 (MT_H1 + 4)  // row pitches: 16-byte aligned rows, b128 reads of 16 rows spread over the banks
 #define MT_P2 (MT_H2 + 4)
 #define MT_ROW (MT_H2 * MT_H1 + 2 * MT_H2 + 2 + MT_H1)
 
@@ -262,11 +258,7 @@ int tzr_mlp_tail64_launch(const float* d_y1, int64_t y1_stride, const void* d_la
   return G;
 }
 
-// ---- bottom MLP: ha = relu(x Wa^T + ba) [B, 64], hb = relu(ha Wb^T + bb) [B, 16]; K0 <= 16 ---------------------------------
-#define MB_H1 64
-#define MB_H2 16
-#define MB_PX 20  // row pitch of the [16 x 16] tiles (x, masked dhb)
-
+// ---- bottom MLP: ha = relu(x Wa^T + ba) [B, 64], hb = relu(ha Wb^T + bb) [B, 16]; K0 <= 16 (mlp2_fwd16_body.h) ---------------
 __global__ __launch_bounds__(MM_THREADS) void tzr_mlp2_fwd16_kernel(
     const float* __restrict__ x, int64_t xs, int64_t B, int K0, const float* __restrict__ Wa, const float* __restrict__ ba,
     const float* __restrict__ Wb, const float* __restrict__ bb, float* __restrict__ ha, int64_t has, float* __restrict__ hb,
@@ -274,72 +266,8 @@ __global__ __launch_bounds__(MM_THREADS) void tzr_mlp2_fwd16_kernel(
   __shared__ __attribute__((aligned(16))) float T1s[MM_WAVES][MM_TS * MT_P1];  // ha tile
   const int lane = threadIdx.x & (TZR_WAVE - 1);
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / TZR_WAVE));
-  const int r = lane & 15, q = lane >> 4;
-  float* T1 = &T1s[wv][0];
-  // B operands: first layer k = 4 ks + q over the inputs (zero beyond K0): Wa[16 hb + r][k]; second layer k = 16 q + ks over
-  // the 64 hidden units: Wb[r][k]
-  float Wfa[4][4], Wfb[16], bav[4];
-#pragma unroll
-  for (int hbk = 0; hbk < 4; ++hbk) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int k = 4 * ks + q;
-      const float w = Wa[(16 * hbk + r) * K0 + (k < K0 ? k : 0)];
-      Wfa[hbk][ks] = k < K0 ? w : 0.f;
-    }
-    bav[hbk] = ba ? ba[16 * hbk + r] : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float4 v = tzr_ld4(Wb + r * MB_H1 + 16 * q + 4 * i);
-    Wfb[4 * i] = v.x; Wfb[4 * i + 1] = v.y; Wfb[4 * i + 2] = v.z; Wfb[4 * i + 3] = v.w;
-  }
-  const float bbv = bb ? bb[r] : 0.f;
-  const int64_t tiles = (B + MM_TS - 1) / MM_TS;
-  const int64_t nw = (int64_t)gridDim.x * MM_WAVES;
-  for (int64_t t = (int64_t)blockIdx.x * MM_WAVES + wv; t < tiles; t += nw) {
-    const int64_t b0 = t * MM_TS;
-    // ---- A = x[sample r][4 ks + q] straight from HBM (the whole tile is 16 x K0 floats)
-    float xa[4];
-    {
-      const int64_t b = b0 + r < B ? b0 + r : B - 1;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int k = 4 * ks + q;
-        const float v = x[b * xs + (k < K0 ? k : 0)];
-        xa[ks] = (k < K0 && b0 + r < B) ? v : 0.f;
-      }
-    }
-    mm_f32x4 acc[4];
-#pragma unroll
-    for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks], Wfa[hbk][ks], acc[hbk], 0, 0, 0);
-    // reg j of lane (r, q): sample 4 q + j, unit 16 hbk + r -> the ha tile in LDS
-#pragma unroll
-    for (int hbk = 0; hbk < 4; ++hbk)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) T1[(4 * q + j) * MT_P1 + 16 * hbk + r] = fmaxf(acc[hbk][j] + bav[hbk], 0.f);
-    __builtin_amdgcn_wave_barrier();
-    // ---- ha out (rows of 256 bytes, 16 bytes per lane) and hb = relu(ha Wb^T + bb): A = ha[sample r][16 q + ks]
-    mm_f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = lane + TZR_WAVE * i, row = e >> 4, c4 = e & 15;
-      if (b0 + row < B) tzr_st4(ha + (b0 + row) * has + 4 * c4, tzr_ld4(T1 + row * MT_P1 + 4 * c4));
-      const float4 av = tzr_ld4(T1 + r * MT_P1 + 16 * q + 4 * i);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, Wfb[4 * i], acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, Wfb[4 * i + 1], acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, Wfb[4 * i + 2], acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, Wfb[4 * i + 3], acc2, 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (b0 + 4 * q + j < B) hb[(b0 + 4 * q + j) * hbs + r] = fmaxf(acc2[j] + bbv, 0.f);
-    __builtin_amdgcn_wave_barrier();  // (the next tile overwrites T1)
-  }
+  mb_fwd16_tiles(x, xs, B, K0, Wa, ba, Wb, bb, ha, has, hb, hbs, &T1s[wv][0], lane, (int64_t)blockIdx.x * MM_WAVES + wv,
+                 (int64_t)gridDim.x * MM_WAVES);
 }
 
 void tzr_mlp2_fwd16_launch(const float* d_x, int64_t xs, int64_t B, int K0, const float* d_Wa, const float* d_ba, const float* d_Wb,

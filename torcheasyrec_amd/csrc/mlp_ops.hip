@@ -19,6 +19,7 @@
 // one finish pass in workgroup order): bit-reproducible, no float atomics.
 #include "parts_sum.h"
 #include "tzr_common.h"
+#include "mlp2_fwd16_body.h"  // mb_fwd16_fits
 
 int g_tzr_mlp_mfma = 0;  // tzr_tune("mlp_mfma"): -1 = the general LDS-tiled kernels for every shape (A/B, tests); 0 = MFMA kernels where the shape fits
 int tzr_mlp_tail64_launch(const float* d_y1, int64_t y1_stride, const void* d_labels, int labels_itemsize, int labels_are_float,
@@ -181,8 +182,7 @@ extern "C" int tzr_mlp2_fwd(const float* d_x, int64_t x_stride, int64_t B, int K
   if (K0 > ML_K0 || H1 > ML_H1 || H2 > ML_H2) return TZR_ERR_UNSUPPORTED;
   if (B == 0) return TZR_OK;
   // the DLRM-Criteo shape runs on the matrix cores, one wave per 16-sample tile (mlp_mfma.hip)
-  if (g_tzr_mlp_mfma >= 0 && K0 <= 16 && H1 == 64 && H2 == 16 && !(ha_stride & 3) && !(reinterpret_cast<uintptr_t>(d_ha) & 15) &&
-      !(reinterpret_cast<uintptr_t>(d_Wb) & 15)) {
+  if (g_tzr_mlp_mfma >= 0 && mb_fwd16_fits(K0, H1, H2, d_Wb, d_ha, ha_stride)) {
     tzr_mlp2_fwd16_launch(d_x, x_stride, B, K0, d_Wa, d_ba, d_Wb, d_bb, d_ha, ha_stride, d_hb, hb_stride,
                           static_cast<hipStream_t>(stream));
     TZR_CHECK_LAUNCH();

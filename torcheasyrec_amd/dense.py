@@ -629,48 +629,60 @@ class _Mlp2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Wa, ba, Wb, bb):
-        B, K0 = x.shape
-        H1, H2 = Wa.shape[0], Wb.shape[0]
-        xs = x if (x.dtype == torch.float32 and x.stride(1) == 1) else x.contiguous().float()
-        ha = torch.empty(B, H1, dtype=torch.float32, device=x.device)
-        hb = torch.empty(B, H2, dtype=torch.float32, device=x.device)
-        Wa_, Wb_, ba_, bb_ = _f32c(Wa), _f32c(Wb), _f32c(ba), _f32c(bb)
-        _lib.check(_lib.lib().tzr_mlp2_fwd(_lib.ptr(xs), xs.stride(0), B, K0, _lib.ptr(Wa_), _lib.ptr(ba_), H1, _lib.ptr(Wb_),
-                                           _lib.ptr(bb_), H2, _lib.ptr(ha), ha.stride(0), _lib.ptr(hb), hb.stride(0),
-                                           _lib.stream_ptr(x.device)), "tzr_mlp2_fwd")
+        xs, ha, hb, Wa_, ba_, Wb_, bb_ = _mlp2_operands(x, Wa, ba, Wb, bb)
+        _lib.check(_lib.lib().tzr_mlp2_fwd(*_mlp2_fwd_args(xs, ha, hb, Wa_, ba_, Wb_, bb_), _lib.stream_ptr(x.device)), "tzr_mlp2_fwd")
         ctx.save_for_backward(xs, ha, hb, Wb_)
-        ctx.dims = (K0, H1, H2)
         ctx.param_refs = (Wa, ba, Wb, bb)  # (backward looks at their `.grad`: see FUSE_FINISH)
         return hb
 
     @staticmethod
     def backward(ctx, dhb):
         xs, ha, hb, Wb_ = ctx.saved_tensors
-        K0, H1, H2 = ctx.dims
-        B = xs.shape[0]
-        g = _rows16(dhb) if dhb.dtype == torch.float32 else dhb.float().contiguous()
-        dWa = torch.empty(H1, K0, dtype=torch.float32, device=xs.device)
-        dba = torch.empty(H1, dtype=torch.float32, device=xs.device)
-        dWb = torch.empty(H2, H1, dtype=torch.float32, device=xs.device)
-        dbb = torch.empty(H2, dtype=torch.float32, device=xs.device)
-        L = _lib.lib()
-        ws = _lib.workspace(L.tzr_mlp_workspace(), xs.device)
-        if _defer_finish(xs.device, ctx.param_refs):
-            # no finish launch: the four tensors stay unwritten, the optimizer's launch adds the partial rows up (row layout:
-            # [dWb | dbb | dWa | dba], include/tzrec_hip.h)
-            G, P = C.c_int(0), C.c_int(0)
-            _lib.check(L.tzr_mlp2_bwd_parts(_lib.ptr(g), g.stride(0), _lib.ptr(hb), hb.stride(0), _lib.ptr(ha), ha.stride(0), _lib.ptr(xs),
-                                            xs.stride(0), B, K0, H1, H2, _lib.ptr(Wb_), _lib.ptr(ws), ws.numel(), C.byref(G), C.byref(P),
-                                            _lib.stream_ptr(xs.device)), "tzr_mlp2_bwd_parts")
-            col = 0
-            for t in (dWb, dbb, dWa, dba):
-                _defer(t, "rows", (ws,), (G.value, P.value, col), ctx.param_refs)
-                col += t.numel()
-            return None, dWa, dba, dWb, dbb
-        _lib.check(L.tzr_mlp2_bwd(_lib.ptr(g), g.stride(0), _lib.ptr(hb), hb.stride(0), _lib.ptr(ha), ha.stride(0), _lib.ptr(xs),
-                                  xs.stride(0), B, K0, H1, H2, _lib.ptr(Wb_), _lib.ptr(dWa), _lib.ptr(dba), _lib.ptr(dWb),
-                                  _lib.ptr(dbb), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(xs.device)), "tzr_mlp2_bwd")
-        return None, dWa, dba, dWb, dbb
+        return (None, *_mlp2_backward(xs, ha, hb, Wb_, ctx.param_refs, dhb))
+
+
+def _mlp2_operands(x, Wa, ba, Wb, bb):
+    """(x as rows of fp32, unwritten ha [B, H1] and hb [B, H2], the four parameters as contiguous fp32) of tzr_mlp2_fwd"""
+    B = x.shape[0]
+    xs = x if (x.dtype == torch.float32 and x.stride(1) == 1) else x.contiguous().float()
+    ha = torch.empty(B, Wa.shape[0], dtype=torch.float32, device=x.device)
+    hb = torch.empty(B, Wb.shape[0], dtype=torch.float32, device=x.device)
+    return xs, ha, hb, _f32c(Wa), _f32c(ba), _f32c(Wb), _f32c(bb)
+
+
+def _mlp2_fwd_args(xs, ha, hb, Wa_, ba_, Wb_, bb_) -> tuple:
+    """the arguments of tzr_mlp2_fwd in front of its stream"""
+    return (_lib.ptr(xs), xs.stride(0), xs.shape[0], xs.shape[1], _lib.ptr(Wa_), _lib.ptr(ba_), Wa_.shape[0], _lib.ptr(Wb_),
+            _lib.ptr(bb_), Wb_.shape[0], _lib.ptr(ha), ha.stride(0), _lib.ptr(hb), hb.stride(0))
+
+
+def _mlp2_backward(xs, ha, hb, Wb_, param_refs, dhb):
+    """(dWa, dba, dWb, dbb) of the bottom MLP from dhb = d(loss)/d(hb): tzr_mlp2_bwd, or -- FUSE_FINISH -- its partial rows"""
+    B, K0 = xs.shape
+    H1, H2 = ha.shape[1], hb.shape[1]
+    g = _rows16(dhb) if dhb.dtype == torch.float32 else dhb.float().contiguous()
+    dWa = torch.empty(H1, K0, dtype=torch.float32, device=xs.device)
+    dba = torch.empty(H1, dtype=torch.float32, device=xs.device)
+    dWb = torch.empty(H2, H1, dtype=torch.float32, device=xs.device)
+    dbb = torch.empty(H2, dtype=torch.float32, device=xs.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.tzr_mlp_workspace(), xs.device)
+    if _defer_finish(xs.device, param_refs):
+        # no finish launch: the four tensors stay unwritten, the optimizer's launch adds the partial rows up (row layout:
+        # [dWb | dbb | dWa | dba], include/tzrec_hip.h)
+        G, P = C.c_int(0), C.c_int(0)
+        _lib.check(L.tzr_mlp2_bwd_parts(_lib.ptr(g), g.stride(0), _lib.ptr(hb), hb.stride(0), _lib.ptr(ha), ha.stride(0), _lib.ptr(xs),
+                                        xs.stride(0), B, K0, H1, H2, _lib.ptr(Wb_), _lib.ptr(ws), ws.numel(), C.byref(G), C.byref(P),
+                                        _lib.stream_ptr(xs.device)), "tzr_mlp2_bwd_parts")
+        col = 0
+        for t in (dWb, dbb, dWa, dba):
+            _defer(t, "rows", (ws,), (G.value, P.value, col), param_refs)
+            col += t.numel()
+        return dWa, dba, dWb, dbb
+    _lib.check(L.tzr_mlp2_bwd(_lib.ptr(g), g.stride(0), _lib.ptr(hb), hb.stride(0), _lib.ptr(ha), ha.stride(0), _lib.ptr(xs),
+                              xs.stride(0), B, K0, H1, H2, _lib.ptr(Wb_), _lib.ptr(dWa), _lib.ptr(dba), _lib.ptr(dWb),
+                              _lib.ptr(dbb), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(xs.device)), "tzr_mlp2_bwd")
+    return dWa, dba, dWb, dbb
 
 
 def mlp2(x, Wa, ba, Wb, bb):
@@ -867,10 +879,8 @@ class _InteractionTopLossFn(torch.autograd.Function):
         z = None if _owned_wgrad(B, sparse.shape[1]) else torch.empty(B, width, dtype=torch.float32, device=dev)
         W1_, b1_ = _f32c(W1), _f32c(b1)
         pk = _fresh_packed_w1(W1_) if (n == 27 and D == 16 and H1 == 64) else None
-        _lib.check(_lib.lib().tzr_dot_interaction_top_fwd_packed(
-            _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(W1_), W1_.stride(0),
-            _lib.ptr(b1_), H1, 1, _lib.ptr(z), width, _lib.ptr(y1), y1.stride(0), _lib.ptr(pk.fwd) if pk is not None else None,
-            _lib.stream_ptr(dev)), "tzr_dot_interaction_top_fwd_packed")
+        head, tail = _ia_top_fwd_args(dense, sparse, F, D, W1_, b1_, z, width, y1, pk)
+        _lib.check(_lib.lib().tzr_dot_interaction_top_fwd_packed(*head, B, *tail, _lib.stream_ptr(dev)), "tzr_dot_interaction_top_fwd_packed")
         ctx.w1_packed = pk
         logits, g1, dW2, db2, dw3, scal, db1 = _mlp_tail(y1, labels, W2, b2, w3, b3)
         ctx.save_for_backward(dense, sparse, W1_, g1, dW2, db2, dw3, scal, db1)
@@ -892,11 +902,9 @@ class _InteractionTopLossFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gs = torch.empty_like(sparse)
             gd = torch.empty_like(dense)
-            pk = ctx.w1_packed  # (as fresh as the saved W1: autograd refuses a W1 changed since the forward)
+            # (the packed copy is as fresh as the saved W1: autograd refuses a W1 changed since the forward)
             _lib.check(_lib.lib().tzr_dot_interaction_top_bwd_packed(
-                _lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, B, _lib.ptr(g1), g1.stride(0),
-                g1.shape[1], _lib.ptr(W1), W1.stride(0), _lib.ptr(gl32), _lib.ptr(gd), gd.stride(0), _lib.ptr(gs),
-                gs.stride(0), _lib.ptr(pk.bwd) if pk is not None else None, _lib.stream_ptr(sparse.device)),
+                *_ia_top_bwd_args(dense, sparse, F, D, g1, W1, gl32, gd, gs, ctx.w1_packed), _lib.stream_ptr(sparse.device)),
                 "tzr_dot_interaction_top_bwd_packed")
         if not ctx.needs_input_grad[3]:
             dW1 = None
@@ -908,6 +916,20 @@ class _InteractionTopLossFn(torch.autograd.Function):
             return (gd, gs, None, dW1, db1, dW2, db2, dw3, scal[0:1], None)
         outs = torch._foreach_mul([db1, dW2, db2, dw3, scal[0:1]], gl)
         return (gd, gs, None, dW1, *outs, None)
+
+
+def _ia_top_fwd_args(dense, sparse, F, D, W1_, b1_, z, width, y1, pk) -> Tuple[tuple, tuple]:
+    """the arguments of tzr_dot_interaction_top_fwd_packed in front of B, and between B and the stream"""
+    return ((_lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D),
+            (_lib.ptr(W1_), W1_.stride(0), _lib.ptr(b1_), W1_.shape[0], 1, _lib.ptr(z), width, _lib.ptr(y1), y1.stride(0),
+             _lib.ptr(pk.fwd) if pk is not None else None))
+
+
+def _ia_top_bwd_args(dense, sparse, F, D, g1, W1, gl32, gd, gs, pk) -> tuple:
+    """the arguments of tzr_dot_interaction_top_bwd_packed in front of its stream"""
+    return (_lib.ptr(dense), dense.stride(0), _lib.ptr(sparse), sparse.stride(0), F, D, sparse.shape[0], _lib.ptr(g1), g1.stride(0),
+            g1.shape[1], _lib.ptr(W1), W1.stride(0), _lib.ptr(gl32), _lib.ptr(gd), gd.stride(0), _lib.ptr(gs), gs.stride(0),
+            _lib.ptr(pk.bwd) if pk is not None else None)
 
 
 def interaction_top_wgrad(dense: torch.Tensor, sparse: torch.Tensor, D: int, g1: torch.Tensor,
@@ -941,9 +963,16 @@ def interaction_top_wgrad(dense: torch.Tensor, sparse: torch.Tensor, D: int, g1:
 
 def interaction_top_fits(dense: torch.Tensor, sparse: torch.Tensor, D: int, first_linear) -> bool:
     """Whether the fused interaction + first-layer kernels take this shape (D = 16, H = 64, n <= 32, fp32)."""
-    if dense is None or sparse.dim() != 2 or dense.dim() != 2 or dense.shape[1] != D or sparse.shape[1] % D:
+    if dense is None or dense.dim() != 2:
         return False
-    if sparse.dtype != torch.float32 or dense.dtype != torch.float32 or first_linear.weight.dtype != torch.float32:
+    return _ia_top_fits(dense.shape[1], dense.dtype, sparse, D, first_linear)
+
+
+def _ia_top_fits(dense_width: int, dense_dtype, sparse: torch.Tensor, D: int, first_linear) -> bool:
+    """... for a dense vector known by its width and type only (the bottom MLP's output before it has run)"""
+    if sparse.dim() != 2 or dense_width != D or sparse.shape[1] % D:
+        return False
+    if sparse.dtype != torch.float32 or dense_dtype != torch.float32 or first_linear.weight.dtype != torch.float32:
         return False
     F = sparse.shape[1] // D
     n = F + 1
@@ -972,6 +1001,116 @@ def interaction_top_loss(dense, sparse, D, l1, l2, out_linear, labels):
     top_loss(dot_interaction(dense, sparse), ...) with the interaction row's gradient kept on chip."""
     return _InteractionTopLossFn.apply(dense, sparse, D, l1.weight, l1.bias, l2.weight, l2.bias, out_linear.weight,
                                        out_linear.bias, labels)
+
+
+# ---- two launches of that step as phases of the interaction launches (csrc/interaction_phases.hip) -------------------------
+# A/B switches, one per phase: the bottom MLP's forward inside the interaction forward's launch (TZR_PHASE_MLP2_FWD), the
+# weight gradient of W1 inside the interaction backward's (TZR_PHASE_WGRAD).  Off, or for a shape the one-launch entries
+# refuse: the two launches each stands for -- same kernel bodies, bit-identical results.
+PHASE_MLP2_FWD = os.environ.get("TZR_PHASE_MLP2_FWD", "1") == "1"
+PHASE_WGRAD = os.environ.get("TZR_PHASE_WGRAD", "1") == "1"
+PHASE_LAUNCHES = [0, 0]  # one-launch forwards / backwards issued (tests)
+
+
+class _HeadLossFn(torch.autograd.Function):
+    """DLRM from the dense features and the pooled sparse block to the loss: `_Mlp2Fn` (the bottom MLP on data) feeding
+    `_InteractionTopLossFn`, as ONE autograd node -- which is what lets the bottom MLP's forward run as a phase of the interaction
+    forward's launch and the weight gradient of W1 as a phase of the interaction backward's.  Same returns as _TopLossFn."""
+
+    @staticmethod
+    def forward(ctx, x, Wa, ba, Wb, bb, sparse, D, W1, b1, W2, b2, w3, b3, labels):
+        xs, ha, hb, Wa_, ba_, Wb_, bb_ = _mlp2_operands(x, Wa, ba, Wb, bb)
+        B = sparse.shape[0]
+        F = sparse.shape[1] // D
+        sparse = sparse.contiguous()
+        n = F + 1
+        width = n * (n - 1) // 2 + D * n
+        H1 = W1.shape[0]
+        dev = sparse.device
+        y1 = torch.empty(B, H1, dtype=torch.float32, device=dev)
+        z = None if _owned_wgrad(B, sparse.shape[1]) else torch.empty(B, width, dtype=torch.float32, device=dev)
+        W1_, b1_ = _f32c(W1), _f32c(b1)
+        pk = _fresh_packed_w1(W1_) if (n == 27 and D == 16 and H1 == 64) else None
+        L = _lib.lib()
+        mlp2_args = _mlp2_fwd_args(xs, ha, hb, Wa_, ba_, Wb_, bb_)
+        head, tail = _ia_top_fwd_args(hb, sparse, F, D, W1_, b1_, z, width, y1, pk)
+        rc = _lib.TZR_ERR_UNSUPPORTED
+        if PHASE_MLP2_FWD and pk is not None and z is None:
+            rc = L.tzr_dot_interaction_top_fwd_mlp2(*mlp2_args, *head, *tail, _lib.stream_ptr(dev))
+        if rc == _lib.TZR_ERR_UNSUPPORTED:  # (switched off, no packed W1, another shape, the MFMA kernels tuned off: the two launches)
+            _lib.check(L.tzr_mlp2_fwd(*mlp2_args, _lib.stream_ptr(dev)), "tzr_mlp2_fwd")
+            _lib.check(L.tzr_dot_interaction_top_fwd_packed(*head, B, *tail, _lib.stream_ptr(dev)), "tzr_dot_interaction_top_fwd_packed")
+        else:
+            _lib.check(rc, "tzr_dot_interaction_top_fwd_mlp2")
+            PHASE_LAUNCHES[0] += 1
+        logits, g1, dW2, db2, dw3, scal, db1 = _mlp_tail(y1, labels, W2, b2, w3, b3)
+        ctx.save_for_backward(xs, ha, hb, Wb_, sparse, W1_, g1, dW2, db2, dw3, scal, db1)
+        ctx.z = z
+        ctx.cfg = (F, D)
+        ctx.w1_packed = pk
+        ctx.w1_ref = W1
+        ctx.bottom_refs = (Wa, ba, Wb, bb)
+        ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)  # (no zero tensor for the gradient of `logits`: a [B] fill per step)
+        return scal[1], logits
+
+    @staticmethod
+    def backward(ctx, gl, _glogits):
+        xs, ha, hb, Wb_, sparse, W1, g1, dW2, db2, dw3, scal, db1 = ctx.saved_tensors
+        F, D = ctx.cfg
+        B = sparse.shape[0]
+        dev = sparse.device
+        root = _loss_is_root(gl)  # gl is the unit gradient: no scale operand for the kernels, no multi-tensor scaling launch
+        gl32 = None if root else gl.reshape(1).to(torch.float32)
+        need_bottom = any(ctx.needs_input_grad[1:5])
+        need_x = need_bottom or ctx.needs_input_grad[5]
+        need_w1 = ctx.needs_input_grad[7]
+        gd = gs = dW1 = None
+        L = _lib.lib()
+        if need_x:
+            gs = torch.empty_like(sparse)
+            gd = torch.empty_like(hb)
+        # one launch: both input gradients and dW1 wanted, the weight gradient the owned one, its slices left to the optimizer
+        one = (PHASE_WGRAD and need_x and need_w1 and ctx.z is None and B > 0 and F == 26 and D == 16 and g1.shape[1] == 64
+               and _defer_finish(dev, (ctx.w1_ref,)))
+        if one:
+            dW1 = torch.empty(g1.shape[1], W1.shape[1], dtype=torch.float32, device=dev)
+            ws = _lib.workspace(L.tzr_dot_interaction_top_wgrad_workspace(F, D, 1, g1.shape[1]), dev)
+            blob = _lib.TzrWgradParts()
+            _lib.check(L.tzr_dot_interaction_top_bwd_wgrad_parts(
+                *_ia_top_bwd_args(hb, sparse, F, D, g1, W1, gl32, gd, gs, ctx.w1_packed), _lib.ptr(ws), ws.numel(), C.byref(blob),
+                _lib.stream_ptr(dev)), "tzr_dot_interaction_top_bwd_wgrad_parts")
+            _defer(dW1, "wgrad", (ws, gl32), blob, (ctx.w1_ref,))
+            PHASE_LAUNCHES[1] += 1
+        else:
+            if need_x:
+                _lib.check(L.tzr_dot_interaction_top_bwd_packed(
+                    *_ia_top_bwd_args(hb, sparse, F, D, g1, W1, gl32, gd, gs, ctx.w1_packed), _lib.stream_ptr(dev)),
+                    "tzr_dot_interaction_top_bwd_packed")
+            if need_w1 and ctx.z is None:
+                # (`_defer_finish` asked above and answering no has noted nothing: asking again is the same no)
+                dW1 = interaction_top_wgrad(hb, sparse, D, g1, gl32, defer_for=(ctx.w1_ref,))
+            elif need_w1:
+                dW1 = weight_grad(g1, ctx.z) if root else weight_grad(g1, ctx.z) * gl
+        bottom = _mlp2_backward(xs, ha, hb, Wb_, ctx.bottom_refs, gd) if need_bottom else (None, None, None, None)
+        if root:
+            return (None, *bottom, gs, None, dW1, db1, dW2, db2, dw3, scal[0:1], None)
+        outs = torch._foreach_mul([db1, dW2, db2, dw3, scal[0:1]], gl)
+        return (None, *bottom, gs, None, dW1, *outs, None)
+
+
+def head_phases_fit(x: torch.Tensor, bottom_linears, sparse: torch.Tensor, D: int, first_linear) -> bool:
+    """Whether `head_phases_loss` takes this head: the bottom MLP is `mlp2`'s, its output the dense vector of an interaction
+    `interaction_top_loss` takes, and a phase is switched on."""
+    if not (PHASE_MLP2_FWD or PHASE_WGRAD) or not mlp2_fits(x, bottom_linears) or bottom_linears[1].out_features != D:
+        return False
+    return x.shape[0] == sparse.shape[0] and _ia_top_fits(D, torch.float32, sparse, D, first_linear)
+
+
+def head_phases_loss(x, a, b, sparse, D, l1, l2, out_linear, labels):
+    """interaction_top_loss(mlp2(x, a, b), sparse, ...) as one autograd node: see _HeadLossFn."""
+    return _HeadLossFn.apply(x, a.weight, a.bias, b.weight, b.bias, sparse, D, l1.weight, l1.bias, l2.weight, l2.bias,
+                             out_linear.weight, out_linear.bias, labels)
 
 
 def _register_fused(opt, fuse_finish: bool) -> torch.device:

@@ -203,9 +203,18 @@ class MLP(nn.Module):
 def head_loss(model, dense: torch.Tensor, sparse: torch.Tensor, labels: torch.Tensor, d: Optional[torch.Tensor] = None):
     """(mean BCE-with-logits loss, logits [B]) of a DLRM head (`dense_mlp`, `final_mlp`, `output_mlp`, `dim`,
     `arch_with_sparse` of `model`) on the dense features and the pooled sparse block; shared by DLRM and ShardedDLRM."""
+    fused = _FUSED_TOP_LOSS and model.final_mlp._plain and (sparse.is_cuda or _on_emulator())
+    if (d is None and fused and _FUSED_IA_TOP and _FUSED_MLP2 and model.arch_with_sparse and sparse.shape[0] >= _FUSED_IA_TOP_MIN_B
+            and getattr(model.dense_mlp, "_plain", False) and dense.dim() == 2 and (dense.is_cuda or _on_emulator())):
+        from .dense import head_phases_fit, head_phases_loss, top_loss_fits
+
+        bot, lin = model.dense_mlp.linears(), model.final_mlp.linears()
+        # the bottom MLP and the interaction head as one autograd node: the bottom MLP's forward and the weight gradient of
+        # the first top layer run as phases of the interaction launches (dense._HeadLossFn)
+        if head_phases_fit(dense, bot, sparse, model.dim, lin[0]) and top_loss_fits(sparse, lin, model.output_mlp):
+            return head_phases_loss(dense, bot[0], bot[1], sparse, model.dim, lin[0], lin[1], model.output_mlp, labels)
     if d is None:  # (`d`: the bottom MLP's output when the caller already ran it, e.g. under the rows all-to-all)
         d = model.dense_mlp(dense)
-    fused = _FUSED_TOP_LOSS and model.final_mlp._plain and (sparse.is_cuda or _on_emulator())
     if fused and _FUSED_IA_TOP and model.arch_with_sparse and sparse.shape[0] >= _FUSED_IA_TOP_MIN_B:
         from .dense import interaction_top_fits, interaction_top_loss, top_loss_fits
 
