@@ -857,7 +857,14 @@ int tzr_zch_select_mark(const TzrZchModule* h_module, const int64_t* d_row_ids, 
  * tzr_mlp_tail: y2 = relu(y1 W2^T + b2), logit = y2 . w3 + b3, loss = mean BCE-with-logits(logit, label) -- and its
  * whole backward: g1 = d(loss)/d(pre-activation of y1) (y1 is a ReLU output: masked where y1 == 0), db1 = column sums
  * of g1 (the bias gradient of the layer that produced y1), dW2, db2, dw3, d_scalars = {d(loss)/d(b3), loss}.
- * ws: tzr_mlp_workspace() bytes.  Deterministic (fixed-order reductions). */
+ * ws: tzr_mlp_workspace() bytes.  Deterministic (fixed-order reductions).
+ * Every operand may sit at any 4-byte-aligned address with any row stride: the general LDS-tiled kernels take whatever the
+ * MFMA kernels (knob mlp_mfma) do not.  Those run when the shape is DLRM-Criteo's and their 16-byte accesses are aligned:
+ *   tzr_mlp2_fwd          K0 <= 16, H1 = 64, H2 = 16; ha_stride % 4 == 0; d_ha and d_Wb 16-byte aligned
+ *   tzr_mlp2_bwd / _parts K0 <= 16, H1 = 64, H2 = 16; ha_stride, hb_stride, dhb_stride % 4 == 0; d_ha, d_hb, d_dhb 16-byte aligned
+ *   tzr_mlp_tail          H1 = 64, H2 = 32; y1_stride, g1_stride % 4 == 0; d_y1, d_g1 and d_W2 16-byte aligned
+ * (x, x_stride, hb in the forward, the biases, w3, the labels and the outputs of the finish are read and written 4 bytes
+ * at a time by both families.)  The two families add in different orders: equal within rounding, not bit for bit. */
 size_t tzr_mlp_workspace(void);
 int tzr_mlp2_fwd(const float* d_x, int64_t x_stride, int64_t B, int K0, const float* d_Wa, const float* d_ba, int H1,
                  const float* d_Wb, const float* d_bb, int H2, float* d_ha, int64_t ha_stride, float* d_hb,
@@ -1224,7 +1231,9 @@ int tzr_delta_collect(uint32_t* d_bitmap, int64_t rows, int64_t id_base, int cle
  *   wg_debug            0; phase-skipping bits of tzr_dot_interaction_top_wgrad for timing experiments (wrong results).  Kept:
  *                       without the run-time guard around its product the kernel's tile loop compiles to a slower schedule
  *   mlp_mfma            0: the MFMA kernels of mlp_mfma.hip where the shape is DLRM-Criteo's; -1: tzr_mlp2_* / tzr_mlp_tail
- *                       use their general LDS-tiled kernels for every shape (tests only)
+ *                       use their general LDS-tiled kernels for every shape (tests only); > 0: as 0, and the MFMA kernels
+ *                       launch at most that many workgroups of four waves, one 16-sample tile per wave and turn (tests only:
+ *                       several turns per wave on small batches; the general kernels ignore it)
  *   linear_bwd_wg       0; > 0 caps the workgroups of tzr_linear_bwd_relu (many tiles per workgroup on small inputs; tests only)
  *   gemm_rows_wg        0; > 0 caps the workgroups of tzr_linear_rows and tzr_linear_rows_wgrad (tests only) */
 int tzr_tune(const char* name, int value);

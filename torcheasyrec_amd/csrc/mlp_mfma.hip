@@ -83,7 +83,10 @@ __global__ __launch_bounds__(MM_THREADS) TZR_WAVES_PER_EU(2) void tzr_mlp_tail64
   const int64_t nw = (int64_t)gridDim.x * MM_WAVES;
   // a wave's y1 tile (4 KB contiguous when y1 is dense: four 16-byte pieces per lane), fetched a turn ahead: a wave has two
   // or more turns at the step's batch, and each was a chain that began with an HBM round trip (rows behind the batch read
-  // row B - 1 and are zeroed when the tile is stored)
+  // row B - 1 and are zeroed when the tile is stored.  With finite inputs the zeroing changes no output: such a row has
+  // dl = 0, so g2 = 0 and every sum takes 0 x (a finite y1 or y2) from it, and its logit and g1 row are never stored.  It
+  // only keeps a non-finite row B - 1 -- which poisons the result through its own sample anyway -- from doing so 0 x inf = NaN
+  // more times: nothing relies on it, and no test can see it go)
   auto fetch = [&](float4 (&v)[4], int64_t tt) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -535,9 +535,9 @@ extern "C" int tzr_mlp_tail(const float* d_y1, int64_t y1_stride, const void* d_
   int G = (int)std::min<int64_t>(tiles, ML_MAX_WG);
   const int P = H2 * H1 + 2 * H2 + 2 + H1;
   float* parts = static_cast<float*>(ws);
-  // the DLRM-Criteo shape runs on the matrix cores, one wave per 16-sample tile (mlp_mfma.hip)
+  // the DLRM-Criteo shape runs on the matrix cores, one wave per 16-sample tile (mlp_mfma.hip: 16-byte accesses of y1, g1, W2)
   const bool mfma = g_tzr_mlp_mfma >= 0 && H1 == 64 && H2 == 32 && !((y1_stride | g1_stride) & 3) &&
-                    !((reinterpret_cast<uintptr_t>(d_y1) | reinterpret_cast<uintptr_t>(d_g1)) & 15);
+                    !((reinterpret_cast<uintptr_t>(d_y1) | reinterpret_cast<uintptr_t>(d_g1) | reinterpret_cast<uintptr_t>(d_W2)) & 15);
   if (mfma) {
     G = tzr_mlp_tail64_launch(d_y1, y1_stride, d_labels, labels_itemsize, labels_are_float, B, d_W2, d_b2, d_w3, d_b3, d_logits,
                               d_g1, g1_stride, parts, s);
