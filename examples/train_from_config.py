@@ -12,6 +12,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/masknet_mini.config      (mask_net: LayerNorm, masks and concat in two row launches)
     python examples/train_from_config.py tests/golden/wukong_mini.config       (wukong: each layer's FM front and mix in one launch each)
     python examples/train_from_config.py tests/golden/ple_mini.config          (ple: every gate of a CGC level mixed in one launch; per-tower metrics)
+    python examples/train_from_config.py tests/golden/pepnet_mini.config       (pepnet: EPNet / PPNet gates in one launch per level; a tower per task and domain)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""

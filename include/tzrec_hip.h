@@ -613,6 +613,49 @@ typedef struct TzrCgcMix {
 int tzr_cgc_mix_fwd(const TzrCgcMix* h_mix, void* stream);
 int tzr_cgc_mix_bwd(const TzrCgcMix* h_mix, void* stream);
 
+/* The gate-and-scale step of PEPNet (tzrec/modules/personalized_net.py), EVERY slot (a task of one PPNet level, or the one gate
+ * of EPNet) in one launch:
+ *   out_n[b,:] = act(z_n[b,:] + bz_n) * gamma * sigmoid(g_n[b,:] + bg_n),   act = ReLU (relu != 0) or identity
+ * z_n / g_n are the GEMM outputs WITHOUT bias; bz_n may be null (no bias), bg_n not.
+ * forward: reads z / bz / g / bg, writes out.
+ * backward: reads grad_out / z / bz / g / bg -- nothing else is kept from the forward: the sigmoid and, with the forward's own
+ * fp32 add, the ReLU mask are recomputed -- and writes dz_n = grad_out * gamma * s * [z + bz > 0] (identity: no mask),
+ * dg_n = grad_out * act(z + bz) * gamma * s * (1 - s), and d_bias = [n_slots][2][H] floats: per slot the column sums of dz_n,
+ * then of dg_n, over the batch (per-workgroup partial rows in `ws`, added by a second launch in the interleaved order of
+ * csrc/parts_sum.h).  grad_out[n] == 0: slot n has no output gradient, its dz / dg / d_bias are zeros.  dz[n] may be z[n] and
+ * dg[n] may be g[n] (in place).  The sigmoid is formed from exp(-|x|) without overflow or cancellation: finite for every finite x, and
+ * exactly 0 or 1 past |x| = 87.3 (exp(-|x|) below the smallest normal fp32 counts as 0), where dg is exactly 0.  Deterministic, no atomics.  fp32; H multiple of 4, <= 4096; at most TZR_GATE_SCALE_MAX_SLOTS slots.
+ * TZR_ERR_INVALID: a null or misaligned (16 bytes) pointer, B <= 0, a non-positive H / n_slots.  TZR_ERR_UNSUPPORTED: over a
+ * limit (H, n_slots), a row stride that is no multiple of 4 or below H.  TZR_ERR_WORKSPACE: `ws` null, not 256-byte aligned or
+ * below tzr_gate_scale_bwd_workspace (which includes 256 bytes of alignment slack).  A refused call launches nothing. */
+#define TZR_GATE_SCALE_MAX_SLOTS 8
+typedef struct TzrGateScale {
+  int64_t B;
+  int32_t H, n_slots, relu, reserved;
+  float gamma;
+  int32_t reserved2;
+  uint64_t z[TZR_GATE_SCALE_MAX_SLOTS];              /* const float* [B, H]                       */
+  int64_t z_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t bz[TZR_GATE_SCALE_MAX_SLOTS];             /* const float* [H], nullable                */
+  uint64_t g[TZR_GATE_SCALE_MAX_SLOTS];              /* const float* [B, H]                       */
+  int64_t g_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t bg[TZR_GATE_SCALE_MAX_SLOTS];             /* const float* [H]                          */
+  uint64_t out[TZR_GATE_SCALE_MAX_SLOTS];            /* float* [B, H]                 (forward)   */
+  int64_t out_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t grad_out[TZR_GATE_SCALE_MAX_SLOTS];       /* const float* [B, H], nullable (backward)  */
+  int64_t grad_out_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t dz[TZR_GATE_SCALE_MAX_SLOTS];             /* float* [B, H]                 (backward)  */
+  int64_t dz_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t dg[TZR_GATE_SCALE_MAX_SLOTS];             /* float* [B, H]                 (backward)  */
+  int64_t dg_stride[TZR_GATE_SCALE_MAX_SLOTS];
+  uint64_t d_bias;                                   /* float* [n_slots][2][H]        (backward)  */
+  uint64_t ws;                                       /* workspace                     (backward)  */
+  uint64_t ws_bytes;
+} TzrGateScale;
+int tzr_gate_scale_fwd(const TzrGateScale* h_gs, void* stream);
+size_t tzr_gate_scale_bwd_workspace(int64_t B, int H, int n_slots);
+int tzr_gate_scale_bwd(const TzrGateScale* h_gs, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

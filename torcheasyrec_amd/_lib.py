@@ -89,6 +89,27 @@ class TzrCgcMix(C.Structure):
 
 assert C.sizeof(TzrCgcMix) == 1248
 
+GATE_SCALE_MAX_SLOTS = 8
+
+
+class TzrGateScale(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("H", C.c_int32), ("n_slots", C.c_int32), ("relu", C.c_int32), ("reserved", C.c_int32),
+        ("gamma", C.c_float), ("reserved2", C.c_int32),
+        ("z", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("z_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("bz", C.c_uint64 * GATE_SCALE_MAX_SLOTS),
+        ("g", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("g_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("bg", C.c_uint64 * GATE_SCALE_MAX_SLOTS),
+        ("out", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("out_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("grad_out", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("grad_out_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("dz", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("dz_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("dg", C.c_uint64 * GATE_SCALE_MAX_SLOTS), ("dg_stride", C.c_int64 * GATE_SCALE_MAX_SLOTS),
+        ("d_bias", C.c_uint64), ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrGateScale) == 952
+
 
 class TzrSparseOptim(C.Structure):
     _fields_ = [
@@ -313,6 +334,9 @@ _SIGNATURES = {
     "tzr_moe_mix_bwd": (_i32, [_vp, _vp]),
     "tzr_cgc_mix_fwd": (_i32, [_vp, _vp]),
     "tzr_cgc_mix_bwd": (_i32, [_vp, _vp]),
+    "tzr_gate_scale_fwd": (_i32, [_vp, _vp]),
+    "tzr_gate_scale_bwd_workspace": (_sz, [_i64, _i32, _i32]),
+    "tzr_gate_scale_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

@@ -256,6 +256,100 @@ def cgc_mix(logits, experts, sels):
     return list(_CgcMixFn.apply(sels, *logits, *experts))
 
 
+class _GateScaleFn(torch.autograd.Function):
+    """out_n = act(z_n + bz_n) * gamma * sigmoid(g_n + bg_n) for every slot (task of one PPNet level, or EPNet's one gate) in one
+    launch per direction plus the bias gradients' finishing launch (tzr_gate_scale_fwd / _bwd, csrc/gate_scale.hip); inputs: N
+    tensors z [B, H], N biases bz ([H] or None), N tensors g [B, H], N biases bg [H].  Saved for the backward: the inputs, nothing
+    the forward computed.  Capturable: nothing reads the device, every buffer is torch's."""
+
+    @staticmethod
+    def _fill(m, B, H, gamma, relu, zs, bzs, gs, bgs):
+        m.B, m.H, m.n_slots, m.relu, m.gamma = B, H, len(zs), 1 if relu else 0, gamma
+        for n, (z, bz, g, bg) in enumerate(zip(zs, bzs, gs, bgs)):
+            m.z[n], m.z_stride[n] = _lib.ptr(z), z.stride(0)
+            m.g[n], m.g_stride[n] = _lib.ptr(g), g.stride(0)
+            m.bz[n], m.bg[n] = _lib.ptr(bz) or 0, _lib.ptr(bg)
+
+    @staticmethod
+    def forward(ctx, gamma, relu, N, *tensors):
+        zs, bzs, gs, bgs = tensors[:N], tensors[N:2 * N], tensors[2 * N:3 * N], tensors[3 * N:]
+        B, H = zs[0].shape
+        dev = zs[0].device
+        m = _lib.TzrGateScale()
+        _GateScaleFn._fill(m, B, H, gamma, relu, zs, bzs, gs, bgs)
+        outs = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(N)]
+        for n in range(N):
+            m.out[n], m.out_stride[n] = _lib.ptr(outs[n]), outs[n].stride(0)
+        _lib.check(_lib.lib().tzr_gate_scale_fwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_gate_scale_fwd")
+        ctx.save_for_backward(*zs, *bzs, *gs, *bgs)
+        ctx.gamma, ctx.relu, ctx.N = gamma, relu, N
+        ctx.set_materialize_grads(False)  # (a slot without an output gradient: a null pointer, not a [B, H] fill)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        N = ctx.N
+        t = ctx.saved_tensors
+        zs, bzs, gs, bgs = t[:N], t[N:2 * N], t[2 * N:3 * N], t[3 * N:]
+        B, H = zs[0].shape
+        dev = zs[0].device
+        gos = [None if g is None else _rows16(g.float()) for g in gouts]
+        m = _lib.TzrGateScale()
+        _GateScaleFn._fill(m, B, H, ctx.gamma, ctx.relu, zs, bzs, gs, bgs)
+        dz = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(N)]
+        dg = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(N)]
+        db = torch.empty(N, 2, H, dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        ws = _lib.workspace(L.tzr_gate_scale_bwd_workspace(B, H, N), dev)
+        for n in range(N):
+            if gos[n] is not None:
+                m.grad_out[n], m.grad_out_stride[n] = _lib.ptr(gos[n]), gos[n].stride(0)
+            m.dz[n], m.dz_stride[n] = _lib.ptr(dz[n]), dz[n].stride(0)
+            m.dg[n], m.dg_stride[n] = _lib.ptr(dg[n]), dg[n].stride(0)
+        m.d_bias, m.ws, m.ws_bytes = _lib.ptr(db), _lib.ptr(ws), ws.numel()
+        _lib.check(L.tzr_gate_scale_bwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_gate_scale_bwd")
+        dbz = [None if bzs[n] is None else db[n, 0] for n in range(N)]
+        return (None, None, None, *dz, *dbz, *dg, *[db[n, 1] for n in range(N)])
+
+
+def gate_scale_ok(zs, gs, bzs=None, bgs=None) -> bool:
+    """what tzr_gate_scale_* takes: 1 to 8 slots of fp32 z and g [B, H] (B > 0, H % 4 == 0, <= 4096) with unit column stride, row
+    strides that are multiples of 4 floats and 16-byte aligned rows -- column slices of wider buffers are fine --, contiguous
+    aligned fp32 biases [H] (a bz may be None), everything on the device of the loaded library"""
+    if not (0 < len(zs) <= _lib.GATE_SCALE_MAX_SLOTS and len(gs) == len(zs)):
+        return False
+    x = zs[0]
+    if not (x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 4096):
+        return False
+    if (x.device.type == "cpu") != (_lib.backend() == "emu"):
+        return False
+    for t in list(zs) + list(gs):
+        if not (t.dtype == torch.float32 and t.shape == x.shape and t.device == x.device and t.stride(1) == 1 and t.stride(0) % 4 == 0
+                and t.stride(0) >= x.shape[1] and t.data_ptr() % 16 == 0):
+            return False
+    for bs, nullable in ((bzs, True), (bgs, False)):
+        if bs is None:
+            continue
+        if len(bs) != len(zs):
+            return False
+        for b in bs:
+            if b is None:
+                if not nullable:
+                    return False
+            elif not (b.dtype == torch.float32 and b.shape == (x.shape[1],) and b.device == x.device and b.is_contiguous()
+                      and b.data_ptr() % 16 == 0):
+                return False
+    return True
+
+
+def gate_scale(zs, bzs, gs, bgs, gamma: float, relu: bool):
+    """[act(z_n + bz_n) * gamma * sigmoid(g_n + bg_n) for n] -- what follows the three GEMMs of every task of one PPNet level, or
+    of EPNet (tzrec/modules/personalized_net.py) -- one launch for all slots; `zs` / `gs` are the GEMM outputs WITHOUT bias.  The
+    caller checks `gate_scale_ok(zs, gs, bzs, bgs)` first."""
+    N = len(zs)
+    return list(_GateScaleFn.apply(float(gamma), bool(relu), N, *zs, *bzs, *gs, *bgs))
+
+
 SKINNY_MAX_OUT = 8  # output units up to which a Linear layer takes tzr_skinny_linear_* (csrc/dense_ops.hip)
 
 

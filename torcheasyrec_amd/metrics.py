@@ -238,6 +238,8 @@ class Evaluator:
 
     def __init__(self, model, spec: PipelineSpec, device=None, grouped_auc_capacity: int = 1 << 20) -> None:
         self._pg = getattr(model, "_pg", None)
+        # a model with several towers per task (pepnet's domains): the per-sample choice among them, as its loss makes it
+        self._select = getattr(model, "select_domain_predictions", None)
         self.device = torch.device(device) if device is not None else None
         self.metrics: Dict[str, object] = {}
         self._specs: Dict[str, MetricSpec] = {}
@@ -265,6 +267,8 @@ class Evaluator:
             self._probs_key[suffix] = ("probs1" if num_class == 2 else "probs") + suffix
 
     def update(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> None:
+        if self._select is not None:
+            predictions = self._select(predictions, batch)
         for suffix, names in self._towers.items():
             probs = predictions[self._probs_key[suffix]]
             by_kind = {self._specs[n].kind: n for n in names}

@@ -272,19 +272,22 @@ class MultiTaskRankModel(RankModel):
     """What the multi-task models share (tzrec/models/multi_task_rank.py): a task tower (optional MLP + logits layer) per
     `task_towers` block; predictions and losses carry the tower name as suffix."""
 
-    def _build_towers(self, m, in_dims) -> None:
-        """`in_dims[i]`: width of the tensor tower i reads"""
+    def _build_towers(self, m, in_dims, copies: int = 1) -> None:
+        """`in_dims[i]`: width of the tensor the tower(s) of block i read; `copies` towers per block, block-major (pepnet: one per
+        domain)"""
         self._towers = [(str(t.one("tower_name")), str(t.one("label_name"))) for t in m.many("task_towers")]
         self.task_mlps = nn.ModuleList()
         self.task_outputs = nn.ModuleList()
         self._tower_losses = [[l for l in self._losses if l.tower is not None and l.tower.tower_name == name] for name, _ in self._towers]
-        for t, d in zip(m.many("task_towers"), in_dims):
-            if t.has("mlp"):
-                self.task_mlps.append(mlp_from_msg(d, t.one("mlp")))
-                d = self.task_mlps[-1].output_dim()
-            else:
-                self.task_mlps.append(nn.Identity())
-            self.task_outputs.append(OutputLinear(d, int(t.one("num_class", 1))))
+        for t, d_in in zip(m.many("task_towers"), in_dims):
+            for _ in range(copies):
+                d = d_in
+                if t.has("mlp"):
+                    self.task_mlps.append(mlp_from_msg(d, t.one("mlp")))
+                    d = self.task_mlps[-1].output_dim()
+                else:
+                    self.task_mlps.append(nn.Identity())
+                self.task_outputs.append(OutputLinear(d, int(t.one("num_class", 1))))
 
     def _tower_predictions(self, task_inputs) -> Dict[str, torch.Tensor]:
         out: Dict[str, torch.Tensor] = {}
@@ -387,6 +390,114 @@ class ConfigPLE(MultiTaskRankModel):
         for level in self._extraction_nets:
             task_fea, shared_fea = level(task_fea, shared_fea)
         return self._tower_predictions(task_fea)
+
+
+class ConfigPEPNet(MultiTaskRankModel):
+    """`pepnet {...}` (tzrec/models/pepnet.py:27-245): feature group `all` is the main embedding; with a group `domain` EPNet
+    scales it by a gate over [domain | all.detach()]; with a group `uia` PPNet runs per task a gated stack over it
+    (personalized_net.EPNet / PPNet, the gate-and-scale step of every level in one launch); a task tower per task on PPNet's
+    output, or all towers on the EPNet output / the main embedding without it.
+
+    With `domain_input_name` every task has `task_domain_num` towers, in the order task * D + domain; the predictions carry the
+    keys `<kind>_<tower>_<domain>`, and loss and metrics read, per sample, the prediction of the domain
+    `batch.labels[domain_input_name]` names (`select_domain_predictions`).  The selection is a mask-and-sum over the D
+    predictions -- no gather, no device-side index check, capturable --, so a row whose id lies outside [0, D) selects nothing:
+    every selected value of that row (logit and probability alike) is 0 and no tower receives a gradient from it.  (The
+    reference's torch.gather faults on such a row.)
+
+    Refused when built, naming the field, what the reference cannot run: no `all` group (feature_groups), a `uia` group with
+    empty `ppnet_hidden_units`, a `ppnet_dropout_ratio` list whose length is neither 0, 1 nor that of `ppnet_hidden_units`,
+    `task_domain_num` < 1, a `domain_input_name` that is no `data_config.label_fields` entry, a field the block does not have."""
+
+    _FIELDS = ("epnet_hidden_unit", "epnet_gamma", "ppnet_hidden_units", "ppnet_activation", "ppnet_dropout_ratio", "ppnet_gamma",
+               "domain_input_name", "task_domain_num", "task_towers")
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        from .personalized_net import EPNet, PPNet
+
+        eg, m = self.embedding_group, spec.model
+        other = sorted(k for k in m if k not in self._FIELDS)
+        if other:
+            raise ValueError(f"pepnet: pepnet has no field {other[0]!r} (fields: {', '.join(self._FIELDS)})")
+        if not eg.has_group("all"):
+            raise ValueError("pepnet: feature_groups needs a group named 'all' (the main embedding)")
+        n_task = len(m.many("task_towers"))
+        if n_task == 0:
+            raise ValueError("pepnet: needs at least one `task_towers` block")
+        main_dim = eg.group_total_dim("all")
+        task_in = main_dim
+        self.epnet = None
+        if eg.has_group("domain"):
+            self.epnet = EPNet(main_dim, eg.group_total_dim("domain"), hidden_dim=int(m.one("epnet_hidden_unit", main_dim)),
+                               gamma=float(m.one("epnet_gamma", 2.0)))
+            task_in = self.epnet.output_dim()
+        self.ppnet = None
+        if eg.has_group("uia"):
+            hidden = [int(x) for x in m.many("ppnet_hidden_units")]
+            drops = [float(x) for x in m.many("ppnet_dropout_ratio")]
+            if not hidden:
+                raise ValueError("pepnet: a 'uia' feature group needs ppnet_hidden_units (PPNet without a layer has no output)")
+            if len(drops) not in (0, 1, len(hidden)):
+                raise ValueError(f"pepnet: ppnet_dropout_ratio has {len(drops)} entries, ppnet_hidden_units {len(hidden)}: none, one or one per layer")
+            self.ppnet = PPNet(main_dim, eg.group_total_dim("uia"), num_task=n_task, hidden_units=hidden,
+                               activation=str(m.one("ppnet_activation", "nn.ReLU")), dropout_ratio=drops, gamma=float(m.one("ppnet_gamma", 2.0)))
+            task_in = self.ppnet.task_output_dim()
+        self._domain_input_name = str(m.one("domain_input_name")) if m.has("domain_input_name") else None
+        self._task_domain_num = int(m.one("task_domain_num", 1))
+        if self._task_domain_num < 1:
+            raise ValueError(f"pepnet: task_domain_num is {self._task_domain_num}: at least 1")
+        if self._domain_input_name is not None and self._domain_input_name not in spec.label_fields:
+            raise ValueError(f"pepnet: domain_input_name {self._domain_input_name!r} is not one of data_config.label_fields "
+                             f"({', '.join(spec.label_fields)}): the domain id of a sample is read from batch.labels")
+        self._build_towers(m, [task_in] * n_task, copies=self._task_domain_num if self._domain_input_name else 1)
+        if device is not None:
+            for mod in (self.epnet, self.ppnet, self.task_mlps, self.task_outputs):
+                if mod is not None:
+                    mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        g = self.build_input(batch)
+        feat = g["all"]
+        if self.epnet is not None:
+            feat = self.epnet(feat, g["domain"])
+        n_task = len(self._towers)
+        task_inputs = self.ppnet(feat, g["uia"]) if self.ppnet is not None else [feat] * n_task
+        if self._domain_input_name is None:
+            return self._tower_predictions(task_inputs)
+        D = self._task_domain_num
+        out: Dict[str, torch.Tensor] = {}
+        for i, (tower, _) in enumerate(self._towers):
+            for d in range(D):
+                k = i * D + d
+                y = self.task_outputs[k](self.task_mlps[k](task_inputs[i]))
+                out.update(output_to_prediction(y, [l.spec for l in self._tower_losses[i]], self.task_outputs[k].out_features, f"_{tower}_{d}"))
+        return out
+
+    def select_domain_predictions(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
+        """`<kind>_<tower>`: per sample the `<kind>_<tower>_<d>` of d = batch.labels[domain_input_name] (the reference's
+        _select_domain_task_output); a row with d outside [0, D) gets 0.  Without `domain_input_name`: the predictions as
+        they are."""
+        if self._domain_input_name is None:
+            return predictions
+        D = self._task_domain_num
+        idx = batch.labels[self._domain_input_name].reshape(-1)
+        masks = [idx == d for d in range(D)]
+        out: Dict[str, torch.Tensor] = {}
+        for tower, _ in self._towers:
+            tail = f"_{tower}_0"
+            for key in [k for k in predictions if k.endswith(tail)]:
+                kind = key[:-len(tail)]
+                vals = [predictions[f"{kind}_{tower}_{d}"] for d in range(D)]
+                shape = (-1,) + (1,) * (vals[0].dim() - 1)
+                sel = vals[0] * masks[0].to(vals[0].dtype).view(shape)
+                for d in range(1, D):
+                    sel = sel + vals[d] * masks[d].to(vals[d].dtype).view(shape)
+                out[f"{kind}_{tower}"] = sel
+        return out
+
+    def loss(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
+        return super().loss(self.select_domain_predictions(predictions, batch), batch)
 
 
 class ConfigDCNV1(RankModel):
@@ -613,6 +724,7 @@ class ConfigWuKong(RankModel):
 
 
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "ple": ConfigPLE,
+           "pepnet": ConfigPEPNet,
            "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
