@@ -13,6 +13,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/wukong_mini.config       (wukong: each layer's FM front and mix in one launch each)
     python examples/train_from_config.py tests/golden/ple_mini.config          (ple: every gate of a CGC level mixed in one launch; per-tower metrics)
     python examples/train_from_config.py tests/golden/pepnet_mini.config       (pepnet: EPNet / PPNet gates in one launch per level; a tower per task and domain)
+    python examples/train_from_config.py tests/golden/dbmtl_mini.config        (dbmtl: every Bayesian relation tower in one launch, no concat tensor)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""

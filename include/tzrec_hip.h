@@ -656,6 +656,53 @@ int tzr_gate_scale_fwd(const TzrGateScale* h_gs, void* stream);
 size_t tzr_gate_scale_bwd_workspace(int64_t B, int H, int n_slots);
 int tzr_gate_scale_bwd(const TzrGateScale* h_gs, void* stream);
 
+/* The Bayesian relation towers of DBMTL (tzrec/models/dbmtl.py:90-112, 155-167), the WHOLE chain of a model in one launch
+ * forward and two backward.  Tower t of n_towers (config order) has an input x_t [B, x_width[t]], n_deps[t] EARLIER towers
+ * deps[t][..] (each at most once) and n_layers[t] in 0..4 layers (w [N, K], b [N], nn.Linear layout, N = width[t][l]):
+ *   n_layers[t] == 0:  r_t = x_t; nothing is computed or copied, consumers read x_t (its deps are ignored);
+ *   n_layers[t] >= 1:  r_t = relu(W_{L-1} .. relu(W_0 u_t + b_0) .. + b_{L-1}),  u_t = [x_t | r_d for d in deps[t]] -- a virtual
+ *                      concatenation, never written: K of layer 0 is x_width[t] plus the widths of the r_d.
+ * forward: reads x / w / b, writes every layer's post-ReLU output h[t][l] [B, N] contiguous; the last one is r_t.
+ * backward: reads grad_r[t] = dL/dr_t ([B, width of r_t]; 0: none; ignored for a tower without layers), x, w, h; writes
+ *   dx[t] [B, x_width[t]] -- a tower with layers: the x_t slice of dz_{t,0} W_{t,0}; a tower without: the sum of the slices its
+ *   consumers send, in descending consumer index (zeros without a consumer) --, dw[t][l] [N, K], db[t][l] [N].  The gradient of
+ *   r_t is grad_r[t] plus its consumers' slices in descending consumer index.  The pre-activation gradients live in `ws`.
+ * Two towers may name the same x; each has its own dx.  fp32; every width a multiple of 4; layer widths <=
+ * TZR_RELATION_CHAIN_MAX_WIDTH, x widths <= TZR_RELATION_CHAIN_MAX_X.  Deterministic, no atomics, two runs are bit-equal.
+ * TZR_ERR_INVALID: a null or misaligned (16 bytes) pointer, B <= 0, a non-positive n_towers / width, a negative n_layers /
+ * n_deps, a dep that is not an earlier tower or stands twice.  TZR_ERR_UNSUPPORTED: over a limit, a width that is no multiple of
+ * 4, a row stride that is no multiple of 4 or below the width.  TZR_ERR_WORKSPACE: `ws` null, not 256-byte aligned or below
+ * tzr_relation_chain_bwd_workspace (which includes 256 bytes of alignment slack).  A refused call launches nothing. */
+#define TZR_RELATION_CHAIN_MAX_TOWERS 8
+#define TZR_RELATION_CHAIN_MAX_LAYERS 4
+#define TZR_RELATION_CHAIN_MAX_WIDTH 128
+#define TZR_RELATION_CHAIN_MAX_X 1024
+typedef struct TzrRelationChain {
+  int64_t B;
+  int32_t n_towers, reserved;
+  int32_t x_width[TZR_RELATION_CHAIN_MAX_TOWERS];
+  int32_t n_layers[TZR_RELATION_CHAIN_MAX_TOWERS];
+  int32_t n_deps[TZR_RELATION_CHAIN_MAX_TOWERS];
+  int32_t deps[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_TOWERS];
+  int32_t width[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];
+  uint64_t x[TZR_RELATION_CHAIN_MAX_TOWERS];                                    /* const float* [B, x_width]          */
+  int64_t x_stride[TZR_RELATION_CHAIN_MAX_TOWERS];
+  uint64_t w[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];     /* const float* [N, K] contiguous     */
+  uint64_t b[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];     /* const float* [N]                   */
+  uint64_t h[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];     /* float* [B, N] contiguous           */
+  uint64_t grad_r[TZR_RELATION_CHAIN_MAX_TOWERS];                               /* const float*, nullable (backward)  */
+  int64_t grad_r_stride[TZR_RELATION_CHAIN_MAX_TOWERS];
+  uint64_t dx[TZR_RELATION_CHAIN_MAX_TOWERS];                                   /* float* [B, x_width]    (backward)  */
+  int64_t dx_stride[TZR_RELATION_CHAIN_MAX_TOWERS];
+  uint64_t dw[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];    /* float* [N, K]          (backward)  */
+  uint64_t db[TZR_RELATION_CHAIN_MAX_TOWERS][TZR_RELATION_CHAIN_MAX_LAYERS];    /* float* [N]             (backward)  */
+  uint64_t ws;                                                                  /* workspace              (backward)  */
+  uint64_t ws_bytes;
+} TzrRelationChain;
+int tzr_relation_chain_fwd(const TzrRelationChain* h_rc, void* stream);
+size_t tzr_relation_chain_bwd_workspace(const TzrRelationChain* h_rc);
+int tzr_relation_chain_bwd(const TzrRelationChain* h_rc, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

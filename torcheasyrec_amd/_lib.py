@@ -110,6 +110,27 @@ class TzrGateScale(C.Structure):
 
 assert C.sizeof(TzrGateScale) == 952
 
+# limits of tzr_relation_chain_* (include/tzrec_hip.h: TZR_RELATION_CHAIN_MAX_*)
+RELATION_CHAIN_MAX_TOWERS, RELATION_CHAIN_MAX_LAYERS, RELATION_CHAIN_MAX_WIDTH, RELATION_CHAIN_MAX_X = 8, 4, 128, 1024
+_RC_T, _RC_L = RELATION_CHAIN_MAX_TOWERS, RELATION_CHAIN_MAX_LAYERS
+
+
+class TzrRelationChain(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("n_towers", C.c_int32), ("reserved", C.c_int32),
+        ("x_width", C.c_int32 * _RC_T), ("n_layers", C.c_int32 * _RC_T), ("n_deps", C.c_int32 * _RC_T),
+        ("deps", (C.c_int32 * _RC_T) * _RC_T), ("width", (C.c_int32 * _RC_L) * _RC_T),
+        ("x", C.c_uint64 * _RC_T), ("x_stride", C.c_int64 * _RC_T),
+        ("w", (C.c_uint64 * _RC_L) * _RC_T), ("b", (C.c_uint64 * _RC_L) * _RC_T), ("h", (C.c_uint64 * _RC_L) * _RC_T),
+        ("grad_r", C.c_uint64 * _RC_T), ("grad_r_stride", C.c_int64 * _RC_T),
+        ("dx", C.c_uint64 * _RC_T), ("dx_stride", C.c_int64 * _RC_T),
+        ("dw", (C.c_uint64 * _RC_L) * _RC_T), ("db", (C.c_uint64 * _RC_L) * _RC_T),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrRelationChain) == 2176
+
 
 class TzrSparseOptim(C.Structure):
     _fields_ = [
@@ -337,6 +358,9 @@ _SIGNATURES = {
     "tzr_gate_scale_fwd": (_i32, [_vp, _vp]),
     "tzr_gate_scale_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_gate_scale_bwd": (_i32, [_vp, _vp]),
+    "tzr_relation_chain_fwd": (_i32, [_vp, _vp]),
+    "tzr_relation_chain_bwd_workspace": (_sz, [_vp]),
+    "tzr_relation_chain_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

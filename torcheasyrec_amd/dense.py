@@ -350,6 +350,127 @@ def gate_scale(zs, bzs, gs, bgs, gamma: float, relu: bool):
     return list(_GateScaleFn.apply(float(gamma), bool(relu), N, *zs, *bzs, *gs, *bgs))
 
 
+class _RelationChainFn(torch.autograd.Function):
+    """Every Bayesian relation tower of a DBMTL model in one launch forward and two backward (tzr_relation_chain_fwd / _bwd,
+    csrc/relation_chain.hip).  `deps[t]`: the earlier towers tower t reads; `n_layers[t]`: its layers (0: r_t = x_t).  Inputs: T
+    tensors x_t, then per tower with layers its (weight, bias) pairs in order.  Outputs: every layer's post-ReLU output, tower-
+    major; the last of a tower is r_t, the others carry no gradient.  Saved for the backward: the inputs and those outputs.
+    Capturable: the struct is read when the launch is recorded, every buffer is torch's."""
+
+    @staticmethod
+    def _fill(m, xs, deps, n_layers, params, hs):
+        B = xs[0].shape[0]
+        m.B, m.n_towers = B, len(xs)
+        k = 0
+        for t, x in enumerate(xs):
+            m.x[t], m.x_stride[t], m.x_width[t] = _lib.ptr(x), x.stride(0), x.shape[1]
+            m.n_layers[t], m.n_deps[t] = n_layers[t], len(deps[t])
+            for j, d in enumerate(deps[t]):
+                m.deps[t][j] = d
+            for l in range(n_layers[t]):
+                w, b = params[2 * k], params[2 * k + 1]
+                m.width[t][l] = w.shape[0]
+                m.w[t][l], m.b[t][l], m.h[t][l] = _lib.ptr(w), _lib.ptr(b), _lib.ptr(hs[k])
+                k += 1
+
+    @staticmethod
+    def forward(ctx, deps, n_layers, *tensors):
+        T = len(n_layers)
+        xs, params = tensors[:T], [p.contiguous() for p in tensors[T:]]
+        B, dev = xs[0].shape[0], xs[0].device
+        hs = [torch.empty(B, params[2 * k].shape[0], dtype=torch.float32, device=dev) for k in range(len(params) // 2)]
+        m = _lib.TzrRelationChain()
+        _RelationChainFn._fill(m, xs, deps, n_layers, params, hs)
+        _lib.check(_lib.lib().tzr_relation_chain_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_relation_chain_fwd")
+        ctx.save_for_backward(*xs, *params, *hs)
+        ctx.deps, ctx.n_layers = deps, n_layers
+        last = {sum(n_layers[:t + 1]) - 1 for t in range(T) if n_layers[t]}
+        hidden = [h for k, h in enumerate(hs) if k not in last]
+        if hidden:
+            ctx.mark_non_differentiable(*hidden)
+        ctx.set_materialize_grads(False)  # (a tower without an outside gradient: a null pointer, not a [B, N] fill)
+        return tuple(hs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        deps, n_layers = ctx.deps, ctx.n_layers
+        T, n = len(n_layers), sum(n_layers)
+        saved = ctx.saved_tensors
+        xs, params, hs = saved[:T], saved[T:T + 2 * n], saved[T + 2 * n:]
+        B, dev = xs[0].shape[0], xs[0].device
+        m = _lib.TzrRelationChain()
+        _RelationChainFn._fill(m, xs, deps, n_layers, params, hs)
+        dxs = [torch.empty(B, x.shape[1], dtype=torch.float32, device=dev) for x in xs]
+        dps = [torch.empty_like(p) for p in params]
+        keep, k = [], 0
+        for t in range(T):
+            m.dx[t], m.dx_stride[t] = _lib.ptr(dxs[t]), dxs[t].stride(0)
+            for l in range(n_layers[t]):
+                m.dw[t][l], m.db[t][l] = _lib.ptr(dps[2 * k]), _lib.ptr(dps[2 * k + 1])
+                k += 1
+            if n_layers[t] and gouts[k - 1] is not None:
+                g = _rows16(gouts[k - 1].float())
+                keep.append(g)
+                m.grad_r[t], m.grad_r_stride[t] = _lib.ptr(g), g.stride(0)
+        L = _lib.lib()
+        ws = _lib.workspace(L.tzr_relation_chain_bwd_workspace(C.byref(m)), dev)
+        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
+        _lib.check(L.tzr_relation_chain_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_relation_chain_bwd")
+        return (None, None, *dxs, *dps)
+
+
+def relation_chain_ok(xs, deps, layers) -> bool:
+    """what tzr_relation_chain_* takes: 1 to 8 towers; fp32 x_t [B, Hx] (B > 0, Hx % 4 == 0, <= 1024) with unit column stride, row
+    strides that are multiples of 4 floats and 16-byte aligned rows -- column slices of wider buffers are fine --; `deps[t]`
+    distinct earlier towers; `layers[t]` 0 to 4 (weight [N, K], bias [N]) pairs, fp32, N % 4 == 0, <= 128, K the width of the
+    layer's input (layer 0: Hx plus the widths of the deps' outputs); everything on the device of the loaded library"""
+    T = len(xs)
+    if not (0 < T <= _lib.RELATION_CHAIN_MAX_TOWERS and len(deps) == T and len(layers) == T):
+        return False
+    x0 = xs[0]
+    if not (x0.dim() == 2 and x0.shape[0] > 0) or (x0.device.type == "cpu") != (_lib.backend() == "emu"):
+        return False
+    widths = []
+    for t in range(T):
+        x, lay = xs[t], layers[t]
+        if not (x.dim() == 2 and x.dtype == torch.float32 and x.device == x0.device and x.shape[0] == x0.shape[0] and x.shape[1] % 4 == 0
+                and 0 < x.shape[1] <= _lib.RELATION_CHAIN_MAX_X and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= x.shape[1]
+                and x.data_ptr() % 16 == 0):
+            return False
+        if len(lay) > _lib.RELATION_CHAIN_MAX_LAYERS:
+            return False
+        ds = [int(d) for d in deps[t]]
+        if len(set(ds)) != len(ds) or not all(0 <= d < t for d in ds):
+            return False
+        K = x.shape[1] + sum(widths[d] for d in ds)
+        for w, b in lay:
+            N = w.shape[0]
+            if not (w.dim() == 2 and w.shape[1] == K and N % 4 == 0 and 0 < N <= _lib.RELATION_CHAIN_MAX_WIDTH and b is not None
+                    and b.shape == (N,) and w.dtype == torch.float32 and b.dtype == torch.float32 and w.device == x0.device
+                    and b.device == x0.device and w.is_contiguous() and b.is_contiguous() and w.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0):
+                return False
+            K = N
+        widths.append(K if lay else x.shape[1])
+    return True
+
+
+def relation_chain(xs, deps, layers, hidden: bool = False):
+    """[r_t for t]: r_t = xs[t] itself for a tower without layers, else the ReLU MLP `layers[t]` over the virtual concatenation
+    [xs[t] | r_d for d in deps[t]] -- the relation towers of DBMTL (tzrec/models/dbmtl.py:155-167) -- one launch for the whole
+    chain, no concat tensor.  `hidden`: also every layer's output, [[h_{t,l} for l] for t].  The caller checks
+    `relation_chain_ok(xs, deps, layers)` first."""
+    n_layers = tuple(len(lay) for lay in layers)
+    deps = tuple(tuple(int(d) for d in ds) if n else () for ds, n in zip(deps, n_layers))
+    flat = [p for lay in layers for wb in lay for p in wb]
+    hs = _RelationChainFn.apply(deps, n_layers, *xs, *flat) if sum(n_layers) else ()
+    out, per, k = [], [], 0
+    for t, n in enumerate(n_layers):
+        per.append(list(hs[k:k + n]))
+        k += n
+        out.append(hs[k - 1] if n else xs[t])
+    return (out, per) if hidden else out
+
+
 SKINNY_MAX_OUT = 8  # output units up to which a Linear layer takes tzr_skinny_linear_* (csrc/dense_ops.hip)
 
 

@@ -500,6 +500,161 @@ class ConfigPEPNet(MultiTaskRankModel):
         return super().loss(self.select_domain_predictions(predictions, batch), batch)
 
 
+FUSED_RELATION_CHAIN = True  # A/B switch: False = the reference's literal cat / MLP form of DBMTL's relation towers
+
+
+class ConfigDBMTL(MultiTaskRankModel):
+    """`dbmtl {...}` (tzrec/models/dbmtl.py:28-175): over the (single, first) feature group an optional `mask_net`
+    (masknet.MaskNetModule), an optional `bottom_mlp`, an optional MMoE (present iff `expert_mlp`; `num_expert` defaults to 3),
+    then per `task_towers` block an optional `mlp`, an optional `relation_mlp` over [the tower's own output | the relation
+    outputs of the towers `relation_tower_names` lists] and the logits layer.  A tower has a relation net only if it has
+    `relation_mlp` (`relation_tower_names` without it is ignored; `relation_mlp` without names runs over the tower's own
+    output); the relation output of a tower without one is its `mlp` output.  `task_mlps` and `relation_mlps` are ModuleDicts
+    keyed by tower name, `task_outputs` a ModuleList, as in the reference.
+
+    All relation MLPs of the model run in one launch forward and two backward (dense.relation_chain, csrc/relation_chain.hip)
+    with no concat tensor; the literal form runs with FUSED_RELATION_CHAIN off, with a relation MLP that is not plain Linear +
+    bias + ReLU, with a shape outside the kernel's limits, or off the GPU / the emulator.
+
+    Refused when built, naming tower and field, what the reference cannot run (it dies with a KeyError on the first batch): a
+    `relation_tower_names` entry that stands later in the config, does not exist or is the tower itself; a duplicate
+    `tower_name`; a field the block or a tower does not have.  `pareto_min_loss_weight` and `train_metrics` are refused by
+    name: not built."""
+
+    _FIELDS = ("mask_net", "bottom_mlp", "expert_mlp", "gate_mlp", "num_expert", "task_towers")
+    _TOWER_FIELDS = ("tower_name", "label_name", "metrics", "losses", "num_class", "mlp", "weight", "relation_tower_names", "relation_mlp",
+                     "sample_weight_name", "task_space_indicator_label", "in_task_space_weight", "out_task_space_weight")
+    _MASK_FIELDS = ("n_mask_blocks", "mask_block", "top_mlp", "use_parallel")
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        super().__init__(spec, device, sparse_optimizer)
+        eg, m = self.embedding_group, spec.model
+        other = sorted(k for k in m if k not in self._FIELDS)
+        if other:
+            raise ValueError(f"dbmtl: dbmtl has no field {other[0]!r} (fields: {', '.join(self._FIELDS)})")
+        towers = m.many("task_towers")
+        if not towers:
+            raise ValueError("dbmtl: needs at least one `task_towers` block")
+        names = []
+        for t in towers:
+            name = str(t.one("tower_name"))
+            for k in ("pareto_min_loss_weight", "train_metrics"):
+                if t.has(k):
+                    raise NotImplementedError(f"dbmtl: task_towers {name!r}: `{k}` is not built")
+            other = sorted(k for k in t if k not in self._TOWER_FIELDS)
+            if other:
+                raise ValueError(f"dbmtl: task_towers {name!r} has no field {other[0]!r} (fields: {', '.join(self._TOWER_FIELDS)})")
+            if name in names:
+                raise ValueError(f"dbmtl: tower_name {name!r} stands twice in task_towers")
+            names.append(name)
+        self._group = eg.group_names()[0]
+        d = eg.group_total_dim(self._group)
+        self.mask_net = None
+        if m.has("mask_net"):
+            mod = m.one("mask_net")
+            other = sorted(k for k in mod if k not in self._MASK_FIELDS)
+            if other:
+                raise ValueError(f"dbmtl: mask_net has no field {other[0]!r} (fields: {', '.join(self._MASK_FIELDS)})")
+            for k in ("n_mask_blocks", "mask_block"):
+                if not mod.has(k):
+                    raise ValueError(f"dbmtl: mask_net needs `{k}`")
+            blk = mod.one("mask_block")
+            if not blk.has("hidden_dim"):
+                raise ValueError("dbmtl: mask_net.mask_block needs `hidden_dim`")
+            mask_block = {"hidden_dim": int(blk.one("hidden_dim")), "reduction_ratio": float(blk.one("reduction_ratio", 1.0))}
+            if blk.has("aggregation_dim"):
+                mask_block["aggregation_dim"] = int(blk.one("aggregation_dim"))
+            self.mask_net = MaskNetModule(d, int(mod.one("n_mask_blocks")), mask_block,
+                                          top_mlp=mlp_kwargs(mod.one("top_mlp")) if mod.has("top_mlp") else None,
+                                          use_parallel=bool(mod.one("use_parallel", True)))
+            d = self.mask_net.output_dim()
+        self.bottom_mlp = None
+        if m.has("bottom_mlp"):
+            self.bottom_mlp = mlp_from_msg(d, m.one("bottom_mlp"))
+            d = self.bottom_mlp.output_dim()
+        self.mmoe = None
+        if m.has("expert_mlp"):
+            self.mmoe = MMoE(d, mlp_kwargs(m.one("expert_mlp")), int(m.one("num_expert", 3)), len(towers),
+                             mlp_kwargs(m.one("gate_mlp")) if m.has("gate_mlp") else None)
+            d = self.mmoe.output_dim()
+        self._build_bayes_towers(m, d)
+        if device is not None:
+            for mod in (self.mask_net, self.bottom_mlp, self.mmoe, self.task_mlps, self.relation_mlps, self.task_outputs):
+                if mod is not None:
+                    mod.to(device)
+
+    def _build_bayes_towers(self, m, d_in: int) -> None:
+        """task_mlps / relation_mlps by tower name, task_outputs by position (dbmtl.py:84-123); `_relations[i]`: the positions
+        of the towers whose relation output tower i's relation MLP reads"""
+        towers = m.many("task_towers")
+        self._towers = [(str(t.one("tower_name")), str(t.one("label_name"))) for t in towers]
+        self._tower_losses = [[l for l in self._losses if l.tower is not None and l.tower.tower_name == name] for name, _ in self._towers]
+        names = [name for name, _ in self._towers]
+        self.task_mlps = nn.ModuleDict()
+        self.relation_mlps = nn.ModuleDict()
+        self.task_outputs = nn.ModuleList()
+        self._relations = []
+        widths = []  # of every tower's relation output
+        for i, t in enumerate(towers):
+            name, d = names[i], d_in
+            if t.has("mlp"):
+                self.task_mlps[name] = mlp_from_msg(d, t.one("mlp"))
+                d = self.task_mlps[name].output_dim()
+            rel = []
+            if t.has("relation_mlp"):
+                for r in (str(x) for x in t.many("relation_tower_names")):
+                    if r == name:
+                        raise ValueError(f"dbmtl: task_towers {name!r}: relation_tower_names names the tower itself")
+                    if r not in names:
+                        raise ValueError(f"dbmtl: task_towers {name!r}: relation_tower_names entry {r!r} is no tower_name ({', '.join(names)})")
+                    if names.index(r) > i:
+                        raise ValueError(f"dbmtl: task_towers {name!r}: relation_tower_names entry {r!r} stands later in the config; "
+                                         "a relation MLP reads towers before it")
+                    rel.append(names.index(r))
+                self.relation_mlps[name] = mlp_from_msg(d + sum(widths[j] for j in rel), t.one("relation_mlp"))
+                d = self.relation_mlps[name].output_dim()
+            self._relations.append(rel)
+            widths.append(d)
+            self.task_outputs.append(OutputLinear(d, int(t.one("num_class", 1))))
+
+    def _relation_outputs(self, task_net):
+        """the relation output of every tower (dbmtl.py:155-167)"""
+        names = [name for name, _ in self._towers]
+        mlps = [self.relation_mlps[n] if n in self.relation_mlps else None for n in names]
+        x0 = task_net[0]
+        if FUSED_RELATION_CHAIN and any(m is not None for m in mlps) and x0.dim() == 2 and (x0.is_cuda or _on_emulator()) \
+                and all(m is None or m._plain for m in mlps):
+            from .dense import _rows16, relation_chain, relation_chain_ok
+
+            xs = [_rows16(x) for x in task_net]
+            for i in range(len(xs)):  # (towers that read one tensor: one object, as they came)
+                for j in range(i):
+                    if task_net[i] is task_net[j]:
+                        xs[i] = xs[j]
+            layers = [[] if m is None else [(lin.weight, lin.bias) for lin in m.linears()] for m in mlps]
+            if relation_chain_ok(xs, self._relations, layers):  # every relation MLP of the model in one launch, no concat tensor
+                return relation_chain(xs, self._relations, layers)
+        out = []
+        for i, m in enumerate(mlps):
+            out.append(task_net[i] if m is None else m(torch.cat([task_net[i]] + [out[j] for j in self._relations[i]], dim=1)))
+        return out
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        net = self.build_input(batch)[self._group]
+        if self.mask_net is not None:
+            net = self.mask_net(net)
+        if self.bottom_mlp is not None:
+            net = self.bottom_mlp(net)
+        task_in = self.mmoe(net) if self.mmoe is not None else [net] * len(self._towers)
+        task_net = [self.task_mlps[name](task_in[i]) if name in self.task_mlps else task_in[i] for i, (name, _) in enumerate(self._towers)]
+        out: Dict[str, torch.Tensor] = {}
+        for i, r in enumerate(self._relation_outputs(task_net)):
+            tower = self._towers[i][0]
+            out.update(output_to_prediction(self.task_outputs[i](r), [l.spec for l in self._tower_losses[i]], self.task_outputs[i].out_features,
+                                            f"_{tower}"))
+        return out
+
+
 class ConfigDCNV1(RankModel):
     """`dcn_v1 {...}` (tzrec/models/dcn.py:36-73): the cross network and a deep MLP over the (single) feature group, a final MLP
     over [cross | deep], a logits layer without bias.  `cross { cross_num }` (protos/module.proto:82-85) defaults to 3 layers."""
@@ -724,7 +879,7 @@ class ConfigWuKong(RankModel):
 
 
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "ple": ConfigPLE,
-           "pepnet": ConfigPEPNet,
+           "pepnet": ConfigPEPNet, "dbmtl": ConfigDBMTL,
            "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
