@@ -578,7 +578,9 @@ int tzr_moe_mix_fwd(const TzrMoeMix* h_mix, void* stream);
 int tzr_moe_mix_bwd(const TzrMoeMix* h_mix, void* stream);
 
 /* The gate-and-mix step of one CGC level of PLE (tzrec/modules/extraction_net.py:98-139), EVERY gate in one launch; unlike
- * tzr_moe_mix_* each gate g mixes its own subset of the experts, sel[g][0 .. n_sel[g]) in the order of its logit columns:
+ * tzr_moe_mix_* each gate g mixes its own subset of the experts, sel[g][0 .. n_sel[g]) in the order of its logit columns (one
+ * kernel body serves both, csrc/gate_mix.hip: with sel[g] = 0 .. n_experts-1 for every gate the results equal tzr_moe_mix_*'s
+ * bit for bit; the limits and the status codes of the two ABIs are their own):
  *   probs_g[b,:] = softmax(logits_g[b, 0:n_sel[g]]),   out_g[b,:] = sum_j probs_g[b,j] * expert[sel[g][j]][b,:]
  * forward: reads logits / expert, writes out and probs ([B, n_sel[g]] contiguous per gate, kept for the backward);
  * backward: reads grad_out / expert / probs, writes d_expert_e[b,:] = sum over the gates g that hold e, in ascending g, of

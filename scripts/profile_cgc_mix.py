@@ -1,4 +1,4 @@
-"""The gate-and-mix step of a CGC level of PLE (csrc/cgc_mix.hip) against the reference's literal stack / softmax / matmul form
+"""The gate-and-mix step of a CGC level of PLE (tzr_cgc_mix_*, csrc/gate_mix.hip) against the reference's literal stack / softmax / matmul form
 (ple.FUSED_CGC_MIX = False) on the same box in the same run, forward + backward at B = 8192, at the first two levels of the
 reference's docs example (docs/source/models/ple.md), both with a shared gate:
 

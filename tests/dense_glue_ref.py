@@ -1,4 +1,4 @@
-"""Restatement of the small row-streaming operations of csrc/dense_ops.hip, csrc/moe_ops.hip and csrc/linear_bwd.hip for the
+"""Restatement of the small row-streaming operations of csrc/dense_ops.hip, csrc/gate_mix.hip and csrc/linear_bwd.hip for the
 tests, in plain torch on the CPU in the dtype asked for.  Each operation is one `*_literal(inputs, dtype)`: in float64 it is the
 truth the kernels are held to; in float32 it is the yardstick (`gap`): the literal form's own distance to float64 on the same
 inputs.  Nothing here touches the package under test.

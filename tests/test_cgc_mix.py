@@ -1,4 +1,4 @@
-"""dense.cgc_mix (tzr_cgc_mix_fwd / _bwd, csrc/cgc_mix.hip): softmax + mixing of EVERY gate of one CGC level of PLE in one launch
+"""dense.cgc_mix (tzr_cgc_mix_fwd / _bwd, csrc/gate_mix.hip): softmax + mixing of EVERY gate of one CGC level of PLE in one launch
 per direction, each gate over its own subset of the experts, against the reference's stack / softmax / batched-matmul form
 (tzrec/modules/extraction_net.py:98-109) evaluated in float64 on the CPU.  Tolerances: those of
 tests/test_dense_glue.py::test_moe_mix_matches_the_stacked_form -- outputs and expert gradients rtol 1e-5, atol 1e-6; logit
@@ -123,3 +123,68 @@ def test_cgc_mix_ok_refuses_what_the_kernel_does_not_take(dev):
     assert not cgc_mix_ok(lg, xs, [[0, 1, 1], [0, 1, 2]]) and not cgc_mix_ok(lg, xs, [[0, 1, 3], [0, 1, 2]])  # twice; out of range
     assert not cgc_mix_ok(lg, xs, [[0, 1], [0, 1, 2]])  # logits wider than the member list
     assert _lib.CGC_MAX_EXPERTS == 16 and _lib.CGC_MAX_GATES == 5
+
+
+def run_abi(dev, xs, ls, gos, sels):
+    """forward then backward at the C entry points on column slices of wider NaN-filled tensors, the layout of
+    tests/test_dense_glue_kernels.py::run_moe; `sels` None: tzr_moe_mix_*, otherwise tzr_cgc_mix_* with these member lists"""
+    import ctypes as C
+
+    import test_dense_glue_kernels as glue
+
+    lib, p, st = _lib.lib(), _lib.ptr, _lib.stream_ptr(dev)
+    (B, H), E, G = xs[0].shape, len(xs), len(ls)
+    if sels is None:
+        m, stem = _lib.TzrMoeMix(), "tzr_moe_mix"
+        m.n_tasks = G
+    else:
+        m, stem = _lib.TzrCgcMix(), "tzr_cgc_mix"
+        m.n_gates = G
+        for g, sel in enumerate(sels):
+            m.n_sel[g] = len(sel)
+            for j, e in enumerate(sel):
+                m.sel[g][j] = e
+    m.B, m.H, m.n_experts = B, H, E
+    keep, outs = [], {"out": [], "probs": [], "d_logits": [], "d_expert": []}
+    for e, x in enumerate(xs):
+        xw, xv = glue._wide(x, dev, 4 * (e % 3))
+        dw, dv = glue._blank(B, H, dev, 4 * ((e + 1) % 3) + 12)
+        m.expert[e], m.expert_stride[e], m.d_expert[e], m.d_expert_stride[e] = p(xv), xv.stride(0), p(dv), dv.stride(0)
+        keep += [xw, (dw, dv)]
+        outs["d_expert"].append(dv)
+    for g in range(G):
+        lw, lv = glue._cols(ls[g], dev, E + 3, 1)
+        dlw, dlv = glue._cols((B, E), dev, E + 3, 1)
+        ow, ov = glue._blank(B, H, dev, 4 * g + 24)
+        gw, gv = glue._wide(gos[g], dev, 4 * g + 40)
+        probs = torch.full((B, E), float("nan"), dtype=torch.float32, device=dev)
+        m.logits[g], m.logits_stride[g], m.probs[g] = p(lv), lw.stride(0), p(probs)
+        m.out[g], m.out_stride[g] = p(ov), ov.stride(0)
+        m.grad_out[g], m.grad_out_stride[g] = p(gv), gv.stride(0)
+        m.d_logits[g], m.d_logits_stride[g] = p(dlv), dlw.stride(0)
+        keep += [lw, gw, (dlw, dlv), (ow, ov)]
+        outs["out"].append(ov)
+        outs["probs"].append(probs)
+        outs["d_logits"].append(dlv)
+    assert getattr(lib, stem + "_fwd")(C.byref(m), st) == 0
+    assert getattr(lib, stem + "_bwd")(C.byref(m), st) == 0
+    assert all(glue._untouched(*k) for k in keep if isinstance(k, tuple))
+    return outs
+
+
+# (B, H, E, T): a lane group with an idle lane at the smallest classes; B past one workgroup's rows, MoE <2, 4> against CGC
+# <3, 4>; lgp = 64 with 33 columns, CGC <5, 4>; the column loop runs twice, E across a class bound; MoE's largest class
+@pytest.mark.parametrize("B,H,E,T", [(33, 12, 2, 1), (70, 20, 3, 2), (33, 132, 4, 4), (70, 264, 5, 3), (33, 16, 8, 4)])
+def test_an_moe_mix_is_a_cgc_mix_of_every_expert_bit_for_bit(dev, B, H, E, T):
+    """tzr_moe_mix_* and tzr_cgc_mix_* with sel[g] = 0 .. E-1 for every gate are two instantiations of one kernel body
+    (csrc/gate_mix.hip) with every sum in the same order: the same bits in out, probs, d_logits and d_expert"""
+    import dense_glue_ref as ref
+
+    xs, ls, gos = ref.draw_moe(B, H, E, T, seed=B * 151 + H * 11 + E * 5 + T)
+    moe = run_abi(dev, xs, ls, gos, None)
+    cgc = run_abi(dev, xs, ls, gos, [list(range(E))] * T)
+    for kind in ("out", "probs", "d_logits", "d_expert"):
+        assert len(moe[kind]) == len(cgc[kind]) == (E if kind == "d_expert" else T)
+        for i, (a, b) in enumerate(zip(moe[kind], cgc[kind])):
+            assert bool(torch.isfinite(a).all()), f"{kind}[{i}] of tzr_moe_mix is not finite"
+            assert torch.equal(a, b), f"{kind}[{i}]: max abs difference {float((a - b).abs().max()):.3e}"

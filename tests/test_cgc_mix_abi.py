@@ -1,4 +1,4 @@
-"""Error behaviour of tzr_cgc_mix_fwd / tzr_cgc_mix_bwd (csrc/cgc_mix.hip), as tests/test_cross_v2_abi.py checks the cross
+"""Error behaviour of tzr_cgc_mix_fwd / tzr_cgc_mix_bwd (csrc/gate_mix.hip), as tests/test_cross_v2_abi.py checks the cross
 network's entry points: bad arguments come back as negative status codes -- never a crash, never a launch -- and B == 0 is a
 TZR_OK no-op that reads and writes nothing."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """The row-streaming glue kernels called directly at their C entry points -- csrc/dense_ops.hip (tzr_relu_bwd_colsum, tzr_head_bwd,
-tzr_head_bwd_relu, tzr_skinny_linear_fwd / _bwd and their _parts forms, tzr_bce_logits), csrc/moe_ops.hip (tzr_moe_mix_fwd / _bwd)
+tzr_head_bwd_relu, tzr_skinny_linear_fwd / _bwd and their _parts forms, tzr_bce_logits), csrc/gate_mix.hip (tzr_moe_mix_fwd / _bwd)
 and csrc/linear_bwd.hip (tzr_linear_bwd_relu) -- on column slices of wider NaN-filled tensors whose row strides differ from
 the slice widths, against the float64 restatement of each operation (tests/dense_glue_ref.py).
 
@@ -37,13 +37,13 @@ from torcheasyrec_amd import _lib
 NAN = float("nan")
 PAD = 4  # columns on either side of a slice: these kernels load and store 16 bytes at a time, a slice starts on a multiple of 4 floats
 
-# the launch geometry, restated (csrc/dense_ops.hip, csrc/moe_ops.hip, csrc/linear_bwd.hip)
+# the launch geometry, restated (csrc/dense_ops.hip, csrc/gate_mix.hip, csrc/linear_bwd.hip)
 RB_THREADS = 256  # dense_ops.hip:125
 RB_MAX_WG = 1024  # dense_ops.hip:126
 RB_UNROLL = 4  # dense_ops.hip:128
 SK_FWD_MAX_WG = 2048  # dense_ops.hip:482
-MX_THREADS = 256  # moe_ops.hip:17
-MX_MAX_WG = 4096  # moe_ops.hip:157
+MX_THREADS = 256  # gate_mix.hip:34 (GM_THREADS)
+MX_MAX_WG = 4096  # gate_mix.hip:37 (GM_MOE_MAX_GRID)
 DN_THREADS, DN_ITEMS, DN_MAX_PARTS = 256, 4, 4096  # dense_ops.hip:19-21
 LB_TS = 16  # linear_bwd.hip:32
 WAVE = 64
@@ -104,7 +104,7 @@ def rb_geometry(B, N):
 
 
 def lane_group(n4):
-    """dense_ops.hip:478-479, moe_ops.hip:152-153: the smallest power of two >= n4, at most a wave"""
+    """dense_ops.hip:478-479, gate_mix.hip:213-214: the smallest power of two >= n4, at most a wave"""
     lgp = 1
     while lgp < n4 and lgp < WAVE:
         lgp <<= 1
@@ -119,14 +119,14 @@ def sk_fwd_geometry(B, K):
 
 
 def mx_geometry(B, H):
-    """moe_ops.hip:151-158"""
+    """gate_mix.hip:212-219 (gm_geometry at GM_MOE_MAX_GRID)"""
     lgp = lane_group(H // 4)
     rows = (WAVE // lgp) * (MX_THREADS // WAVE)
     return {"lgp": lgp, "rows_per_wg": rows, "raw_wg": -(-B // rows)}
 
 
 def mx_dispatch(E, T):
-    """moe_ops.hip:163-174"""
+    """gate_mix.hip:198-210 (GM_DISPATCH), :253-254 (the classes of tzr_moe_mix_*)"""
     return (1 if T <= 1 else 2 if T <= 2 else 4), (2 if E <= 2 else 4 if E <= 4 else 8)
 
 

@@ -1,5 +1,5 @@
 """`ple {...}` from its config (tests/golden/ple_mini.config): the model the reference builds from the same file
-(tzrec/models/ple.py:27-109), the gate-and-mix step of each CGC level on csrc/cgc_mix.hip."""
+(tzrec/models/ple.py:27-109), the gate-and-mix step of each CGC level on csrc/gate_mix.hip."""
 import os
 
 import numpy as np

@@ -211,24 +211,13 @@ __global__ __launch_bounds__(GS_THREADS) void tzr_gate_scale_bwd_kernel(GsArgs A
   }
 }
 
-// a [B, H] operand: a null or misaligned pointer is an error, a row stride the float4 accesses cannot take is unsupported
-static int gs_rows(uint64_t ptr, int64_t stride, int H) {
-  if (!ptr || (ptr & 15)) return TZR_ERR_INVALID;
-  return ((stride & 3) || stride < H) ? TZR_ERR_UNSUPPORTED : TZR_OK;
-}
-#define GS_TRY(expr)               \
-  do {                             \
-    const int rc_ = (expr);        \
-    if (rc_ != TZR_OK) return rc_; \
-  } while (0)
-
 // sizes, limits, z / g and the biases: what both directions need
 static int gs_check(const TzrGateScale* m, GsArgs* A) {
   if (m->B <= 0 || m->H <= 0 || m->n_slots <= 0) return TZR_ERR_INVALID;
   if (m->n_slots > GS_N || (m->H & 3) || m->H > 4096) return TZR_ERR_UNSUPPORTED;
   for (int n = 0; n < m->n_slots; ++n) {
-    GS_TRY(gs_rows(m->z[n], m->z_stride[n], m->H));
-    GS_TRY(gs_rows(m->g[n], m->g_stride[n], m->H));
+    TZR_TRY(tzr_rows_operand(m->z[n], m->z_stride[n], m->H));
+    TZR_TRY(tzr_rows_operand(m->g[n], m->g_stride[n], m->H));
     if (!m->bg[n] || (m->bg[n] & 15) || (m->bz[n] & 15)) return TZR_ERR_INVALID;
     A->z[n] = reinterpret_cast<const float*>(m->z[n]);
     A->z_stride[n] = m->z_stride[n];
@@ -243,9 +232,9 @@ static int gs_check(const TzrGateScale* m, GsArgs* A) {
 extern "C" int tzr_gate_scale_fwd(const TzrGateScale* h_gs, void* stream) {
   if (!h_gs) return TZR_ERR_INVALID;
   GsArgs A = {};
-  GS_TRY(gs_check(h_gs, &A));
+  TZR_TRY(gs_check(h_gs, &A));
   for (int n = 0; n < h_gs->n_slots; ++n) {
-    GS_TRY(gs_rows(h_gs->out[n], h_gs->out_stride[n], h_gs->H));
+    TZR_TRY(tzr_rows_operand(h_gs->out[n], h_gs->out_stride[n], h_gs->H));
     A.out[n] = reinterpret_cast<float*>(h_gs->out[n]);
     A.out_stride[n] = h_gs->out_stride[n];
   }
@@ -268,11 +257,11 @@ extern "C" size_t tzr_gate_scale_bwd_workspace(int64_t B, int H, int n_slots) {
 extern "C" int tzr_gate_scale_bwd(const TzrGateScale* h_gs, void* stream) {
   if (!h_gs) return TZR_ERR_INVALID;
   GsArgs A = {};
-  GS_TRY(gs_check(h_gs, &A));
+  TZR_TRY(gs_check(h_gs, &A));
   for (int n = 0; n < h_gs->n_slots; ++n) {
-    GS_TRY(gs_rows(h_gs->dz[n], h_gs->dz_stride[n], h_gs->H));
-    GS_TRY(gs_rows(h_gs->dg[n], h_gs->dg_stride[n], h_gs->H));
-    if (h_gs->grad_out[n]) GS_TRY(gs_rows(h_gs->grad_out[n], h_gs->grad_out_stride[n], h_gs->H));
+    TZR_TRY(tzr_rows_operand(h_gs->dz[n], h_gs->dz_stride[n], h_gs->H));
+    TZR_TRY(tzr_rows_operand(h_gs->dg[n], h_gs->dg_stride[n], h_gs->H));
+    if (h_gs->grad_out[n]) TZR_TRY(tzr_rows_operand(h_gs->grad_out[n], h_gs->grad_out_stride[n], h_gs->H));
     A.dz[n] = reinterpret_cast<float*>(h_gs->dz[n]);
     A.dz_stride[n] = h_gs->dz_stride[n];
     A.dg[n] = reinterpret_cast<float*>(h_gs->dg[n]);

@@ -385,17 +385,6 @@ __global__ __launch_bounds__(RC_WG_THREADS) void tzr_relation_chain_wgrad_kernel
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-#define RC_TRY(expr)               \
-  do {                             \
-    const int rc_ = (expr);        \
-    if (rc_ != TZR_OK) return rc_; \
-  } while (0)
-
-static int rc_rows(uint64_t ptr, int64_t stride, int H) {
-  if (!ptr || (ptr & 15)) return TZR_ERR_INVALID;
-  return ((stride & 3) || stride < H) ? TZR_ERR_UNSUPPORTED : TZR_OK;
-}
-
 // sizes, limits, graph, x / W / b / h: what both directions need.  Errors first, limits second.
 static int rc_check(const TzrRelationChain* m, RcArgs* A, int* n_slots) {
   if (m->B <= 0 || m->n_towers <= 0) return TZR_ERR_INVALID;
@@ -423,7 +412,7 @@ static int rc_check(const TzrRelationChain* m, RcArgs* A, int* n_slots) {
   for (int t = T - 1; t >= 0; --t) {  // (descending: `first` marks the highest consumer of an L = 0 tower)
     RcTower& w = A->t[t];
     const int L = m->n_layers[t];
-    RC_TRY(rc_rows(m->x[t], m->x_stride[t], m->x_width[t]));
+    TZR_TRY(tzr_rows_operand(m->x[t], m->x_stride[t], m->x_width[t]));
     w.x = reinterpret_cast<const float*>(m->x[t]);
     w.xs = m->x_stride[t];
     w.hx = m->x_width[t];
@@ -472,7 +461,7 @@ extern "C" int tzr_relation_chain_fwd(const TzrRelationChain* h_rc, void* stream
   if (!h_rc) return TZR_ERR_INVALID;
   RcArgs A = {};
   int slots = 0;
-  RC_TRY(rc_check(h_rc, &A, &slots));
+  TZR_TRY(rc_check(h_rc, &A, &slots));
 #define RC_FWD(NR_) \
   hipLaunchKernelGGL((tzr_relation_chain_fwd_kernel<NR_>), dim3(rc_grid(h_rc->B)), dim3(RC_THREADS), 0, static_cast<hipStream_t>(stream), A, h_rc->B)
   RC_BY_CLASS(RC_FWD);
@@ -503,16 +492,16 @@ extern "C" int tzr_relation_chain_bwd(const TzrRelationChain* h_rc, void* stream
   if (!h_rc) return TZR_ERR_INVALID;
   RcArgs A = {};
   int slots = 0;
-  RC_TRY(rc_check(h_rc, &A, &slots));
+  TZR_TRY(rc_check(h_rc, &A, &slots));
   const int T = h_rc->n_towers;
   int tiles = 0;
   for (int t = 0; t < T; ++t) {
     RcTower& w = A.t[t];
-    RC_TRY(rc_rows(h_rc->dx[t], h_rc->dx_stride[t], w.hx));
+    TZR_TRY(tzr_rows_operand(h_rc->dx[t], h_rc->dx_stride[t], w.hx));
     w.dx = reinterpret_cast<float*>(h_rc->dx[t]);
     w.dxs = h_rc->dx_stride[t];
     if (w.L > 0 && h_rc->grad_r[t]) {
-      RC_TRY(rc_rows(h_rc->grad_r[t], h_rc->grad_r_stride[t], w.rw));
+      TZR_TRY(tzr_rows_operand(h_rc->grad_r[t], h_rc->grad_r_stride[t], w.rw));
       w.g = reinterpret_cast<const float*>(h_rc->grad_r[t]);
       w.gs = h_rc->grad_r_stride[t];
     }

@@ -15,6 +15,20 @@
     if (hipGetLastError() != hipSuccess) return TZR_ERR_LAUNCH; \
   } while (0)
 
+// return a callee's status unless it is TZR_OK
+#define TZR_TRY(expr)              \
+  do {                             \
+    const int rc_ = (expr);        \
+    if (rc_ != TZR_OK) return rc_; \
+  } while (0)
+
+// a [B, H] operand of a float4 row kernel: a null or misaligned pointer is an error, a row stride the float4 accesses cannot
+// take is unsupported
+static inline int tzr_rows_operand(uint64_t ptr, int64_t stride, int H) {
+  if (!ptr || (ptr & 15)) return TZR_ERR_INVALID;
+  return ((stride & 3) || stride < H) ? TZR_ERR_UNSUPPORTED : TZR_OK;
+}
+
 static inline size_t tzr_align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // Carve a 256-byte aligned region out of a caller workspace.

@@ -113,147 +113,105 @@ def head_bwd_relu(grad_y: torch.Tensor, x: torch.Tensor, weight: torch.Tensor):
     return g, sums[:N].unsqueeze(0), sums[N:N + 1], sums[N + 4:]
 
 
-class _MoeMixFn(torch.autograd.Function):
-    """out_t = softmax(logits_t) . experts for every task of a multi-gate mixture of experts in one launch per direction
-    (tzr_moe_mix_fwd / _bwd, csrc/moe_ops.hip); inputs: T gate-logit tensors [B, E], then E expert outputs [B, H]."""
+class _GateMixFn(torch.autograd.Function):
+    """out_g = softmax(logits_g) . experts[sels[g]] for every gate of a layer in one launch per direction (csrc/gate_mix.hip);
+    inputs: the member lists, the number of gates G, G gate-logit tensors [B, n_g], then E expert outputs [B, H].  `sels` None:
+    every gate over every expert in logit-column order, MMoE's mixing step (tzr_moe_mix_fwd / _bwd); otherwise the gates of one
+    CGC level of PLE (tzr_cgc_mix_fwd / _bwd).  Capturable: nothing reads the device, every buffer is torch's."""
 
     @staticmethod
-    def forward(ctx, n_tasks, *tensors):
-        logits = [t.contiguous() for t in tensors[:n_tasks]]
-        experts = [_rows16(t) for t in tensors[n_tasks:]]
-        B, H = experts[0].shape
-        E, dev = len(experts), experts[0].device
-        m = _lib.TzrMoeMix()
-        m.B, m.H, m.n_experts, m.n_tasks = B, H, E, n_tasks
-        outs = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(n_tasks)]
-        probs = [torch.empty(B, E, dtype=torch.float32, device=dev) for _ in range(n_tasks)]
+    def _begin(sels, G, experts):
+        """(the ABI's struct with sizes, experts and member lists filled, the stem of its entry points, the gates' widths)"""
+        if sels is None:
+            m, stem, widths = _lib.TzrMoeMix(), "tzr_moe_mix", [len(experts)] * G
+            m.n_tasks = G
+        else:
+            m, stem, widths = _lib.TzrCgcMix(), "tzr_cgc_mix", [len(sel) for sel in sels]
+            m.n_gates = G
+            for g, sel in enumerate(sels):
+                m.n_sel[g] = len(sel)
+                for j, e in enumerate(sel):
+                    m.sel[g][j] = e
+        m.B, m.H, m.n_experts = *experts[0].shape, len(experts)
         for e, x in enumerate(experts):
             m.expert[e], m.expert_stride[e] = _lib.ptr(x), x.stride(0)
-        for t in range(n_tasks):
-            m.logits[t], m.logits_stride[t] = _lib.ptr(logits[t]), logits[t].stride(0)
-            m.probs[t] = _lib.ptr(probs[t])
-            m.out[t], m.out_stride[t] = _lib.ptr(outs[t]), outs[t].stride(0)
-        _lib.check(_lib.lib().tzr_moe_mix_fwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_moe_mix_fwd")
-        ctx.save_for_backward(*probs, *experts)
-        ctx.n_tasks = n_tasks
-        return tuple(outs)
+        return m, stem, widths
 
     @staticmethod
-    def backward(ctx, *gouts):
-        T = ctx.n_tasks
-        probs, experts = ctx.saved_tensors[:T], ctx.saved_tensors[T:]
-        B, H = experts[0].shape
-        E, dev = len(experts), experts[0].device
-        gs = [torch.zeros(B, H, dtype=torch.float32, device=dev) if g is None else _rows16(g.float()) for g in gouts]
-        m = _lib.TzrMoeMix()
-        m.B, m.H, m.n_experts, m.n_tasks = B, H, E, T
-        dx = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(E)]
-        dl = [torch.empty(B, E, dtype=torch.float32, device=dev) for _ in range(T)]
-        for e, x in enumerate(experts):
-            m.expert[e], m.expert_stride[e] = _lib.ptr(x), x.stride(0)
-            m.d_expert[e], m.d_expert_stride[e] = _lib.ptr(dx[e]), dx[e].stride(0)
-        for t in range(T):
-            m.probs[t] = _lib.ptr(probs[t])
-            m.grad_out[t], m.grad_out_stride[t] = _lib.ptr(gs[t]), gs[t].stride(0)
-            m.d_logits[t], m.d_logits_stride[t] = _lib.ptr(dl[t]), dl[t].stride(0)
-        _lib.check(_lib.lib().tzr_moe_mix_bwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_moe_mix_bwd")
-        return (None, *dl, *dx)
-
-
-def moe_mix_ok(logits, experts) -> bool:
-    x = experts[0]
-    return bool(0 < len(experts) <= _lib.MOE_MAX_EXPERTS and 0 < len(logits) <= _lib.MOE_MAX_TASKS and x.dim() == 2 and x.shape[0] > 0
-                and x.shape[1] % 4 == 0 and x.shape[1] <= 4096 and all(t.dtype == torch.float32 and t.shape == x.shape for t in experts)
-                and all(t.dtype == torch.float32 and t.shape == (x.shape[0], len(experts)) for t in logits))
-
-
-def moe_mix(logits, experts):
-    """[softmax(logits_t) . experts for t] -- the mixing step of MMoE (tzrec/modules/mmoe.py:63-76) -- one launch for all tasks."""
-    return list(_MoeMixFn.apply(len(logits), *logits, *experts))
-
-
-class _CgcMixFn(torch.autograd.Function):
-    """out_g = softmax(logits_g) . experts[sels[g]] for every gate of one CGC level of PLE in one launch per direction
-    (tzr_cgc_mix_fwd / _bwd, csrc/cgc_mix.hip); inputs: the member lists, G gate-logit tensors [B, n_g], then E expert outputs
-    [B, H].  Capturable: nothing reads the device, every buffer is torch's."""
-
-    @staticmethod
-    def _fill(m, B, H, experts, sels):
-        m.B, m.H, m.n_experts, m.n_gates = B, H, len(experts), len(sels)
-        for e, x in enumerate(experts):
-            m.expert[e], m.expert_stride[e] = _lib.ptr(x), x.stride(0)
-        for g, sel in enumerate(sels):
-            m.n_sel[g] = len(sel)
-            for j, e in enumerate(sel):
-                m.sel[g][j] = e
-
-    @staticmethod
-    def forward(ctx, sels, *tensors):
-        G = len(sels)
+    def forward(ctx, sels, G, *tensors):
         logits = [t.contiguous() for t in tensors[:G]]
         experts = [_rows16(t) for t in tensors[G:]]
         B, H = experts[0].shape
         dev = experts[0].device
-        m = _lib.TzrCgcMix()
-        _CgcMixFn._fill(m, B, H, experts, sels)
+        m, stem, widths = _GateMixFn._begin(sels, G, experts)
         outs = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(G)]
-        probs = [torch.empty(B, len(sel), dtype=torch.float32, device=dev) for sel in sels]
+        probs = [torch.empty(B, n, dtype=torch.float32, device=dev) for n in widths]
         for g in range(G):
             m.logits[g], m.logits_stride[g] = _lib.ptr(logits[g]), logits[g].stride(0)
             m.probs[g] = _lib.ptr(probs[g])
             m.out[g], m.out_stride[g] = _lib.ptr(outs[g]), outs[g].stride(0)
-        _lib.check(_lib.lib().tzr_cgc_mix_fwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_cgc_mix_fwd")
+        _lib.check(getattr(_lib.lib(), stem + "_fwd")(_lib.C.byref(m), _lib.stream_ptr(dev)), stem + "_fwd")
         ctx.save_for_backward(*probs, *experts)
-        ctx.sels = sels
+        ctx.sels, ctx.n_gates = sels, G
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gouts):
-        sels = ctx.sels
-        G = len(sels)
+        G = ctx.n_gates
         probs, experts = ctx.saved_tensors[:G], ctx.saved_tensors[G:]
         B, H = experts[0].shape
         dev = experts[0].device
         gs = [torch.zeros(B, H, dtype=torch.float32, device=dev) if g is None else _rows16(g.float()) for g in gouts]
-        m = _lib.TzrCgcMix()
-        _CgcMixFn._fill(m, B, H, experts, sels)
+        m, stem, widths = _GateMixFn._begin(ctx.sels, G, experts)
         dx = [torch.empty(B, H, dtype=torch.float32, device=dev) for _ in experts]
-        dl = [torch.empty(B, len(sel), dtype=torch.float32, device=dev) for sel in sels]
+        dl = [torch.empty(B, n, dtype=torch.float32, device=dev) for n in widths]
         for e in range(len(experts)):
             m.d_expert[e], m.d_expert_stride[e] = _lib.ptr(dx[e]), dx[e].stride(0)
         for g in range(G):
             m.probs[g] = _lib.ptr(probs[g])
             m.grad_out[g], m.grad_out_stride[g] = _lib.ptr(gs[g]), gs[g].stride(0)
             m.d_logits[g], m.d_logits_stride[g] = _lib.ptr(dl[g]), dl[g].stride(0)
-        _lib.check(_lib.lib().tzr_cgc_mix_bwd(_lib.C.byref(m), _lib.stream_ptr(dev)), "tzr_cgc_mix_bwd")
-        return (None, *dl, *dx)
+        _lib.check(getattr(_lib.lib(), stem + "_bwd")(_lib.C.byref(m), _lib.stream_ptr(dev)), stem + "_bwd")
+        return (None, None, *dl, *dx)
+
+
+def _gate_mix_shapes_ok(logits, experts, widths, max_experts, max_gates) -> bool:
+    """the shape rules tzr_moe_mix_* and tzr_cgc_mix_* share: fp32 experts [B, H] (B > 0, H % 4 == 0, <= 4096, at most
+    `max_experts`), at most `max_gates` gates, gate g with fp32 logits [B, widths[g]]"""
+    if not (0 < len(experts) <= max_experts and 0 < len(logits) <= max_gates and len(widths) == len(logits)):
+        return False
+    x = experts[0]
+    return bool(x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 4096
+                and all(t.dtype == torch.float32 and t.shape == x.shape for t in experts)
+                and all(t.dtype == torch.float32 and n > 0 and t.shape == (x.shape[0], n) for t, n in zip(logits, widths)))
+
+
+def moe_mix_ok(logits, experts) -> bool:
+    """what tzr_moe_mix_* takes (the device and the backend are the caller's to look at)"""
+    return _gate_mix_shapes_ok(logits, experts, [len(experts)] * len(logits), _lib.MOE_MAX_EXPERTS, _lib.MOE_MAX_TASKS)
+
+
+def moe_mix(logits, experts):
+    """[softmax(logits_t) . experts for t] -- the mixing step of MMoE (tzrec/modules/mmoe.py:63-76) -- one launch for all tasks."""
+    return list(_GateMixFn.apply(None, len(logits), *logits, *experts))
 
 
 def cgc_mix_ok(logits, experts, sels) -> bool:
-    """what tzr_cgc_mix_* takes: fp32 experts [B, H] (H % 4 == 0, <= 4096, at most 16), at most 5 gates, gate g with logits
-    [B, len(sels[g])] over distinct experts sels[g], everything on the device of the loaded library"""
-    if not (0 < len(experts) <= _lib.CGC_MAX_EXPERTS and 0 < len(logits) <= _lib.CGC_MAX_GATES and len(sels) == len(logits)):
+    """what tzr_cgc_mix_* takes: the shared shape rules at its limits (at most 16 experts, 5 gates), gate g over distinct
+    experts sels[g], everything on the device of the loaded library"""
+    if not _gate_mix_shapes_ok(logits, experts, [len(sel) for sel in sels], _lib.CGC_MAX_EXPERTS, _lib.CGC_MAX_GATES):
         return False
-    x = experts[0]
-    if not (x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 4096):
+    dev = experts[0].device
+    if not all(t.device == dev for t in (*experts, *logits)) or (dev.type == "cpu") != (_lib.backend() == "emu"):
         return False
-    if not all(t.dtype == torch.float32 and t.shape == x.shape and t.device == x.device for t in experts):
-        return False
-    if (x.device.type == "cpu") != (_lib.backend() == "emu"):
-        return False
-    for lg, sel in zip(logits, sels):
-        if not (lg.dtype == torch.float32 and lg.device == x.device and lg.shape == (x.shape[0], len(sel)) and len(sel) > 0):
-            return False
-        if len(set(sel)) != len(sel) or not all(0 <= int(e) < len(experts) for e in sel):
-            return False
-    return True
+    return all(len(set(sel)) == len(sel) and all(0 <= int(e) < len(experts) for e in sel) for sel in sels)
 
 
 def cgc_mix(logits, experts, sels):
     """[softmax(logits_g) . [experts[e] for e in sels[g]] for g] -- the gate-and-mix step of one CGC level of PLE
     (tzrec/modules/extraction_net.py:98-139) -- one launch for all gates; an expert of several gates is read once."""
     sels = tuple(tuple(int(e) for e in sel) for sel in sels)
-    return list(_CgcMixFn.apply(sels, *logits, *experts))
+    return list(_GateMixFn.apply(sels, len(sels), *logits, *experts))
 
 
 class _GateScaleFn(torch.autograd.Function):

@@ -2,7 +2,7 @@
 value (tzrec/modules/extraction_net.py:20-139): `expert_num_per_task` expert MLPs per task over that task's input, `share_num`
 shared ones over the shared input; task gate t = Linear + softmax over [its own experts | the shared ones] of its input, the
 shared gate (absent on the last level) over [all task experts in task order | the shared ones] of the shared input.  The
-gate-and-mix step of the whole level is one launch per direction (dense.cgc_mix, csrc/cgc_mix.hip)."""
+gate-and-mix step of the whole level is one launch per direction (dense.cgc_mix, csrc/gate_mix.hip)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple

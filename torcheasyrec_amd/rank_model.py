@@ -262,7 +262,7 @@ class MMoE(nn.Module):
         if FUSED_MOE_MIX and input.dim() == 2 and (input.is_cuda or _on_emulator()):
             from .dense import moe_mix, moe_mix_ok
 
-            if moe_mix_ok(logits, outs):  # softmax + mixing of every task in one launch per direction, nothing stacked (csrc/moe_ops.hip)
+            if moe_mix_ok(logits, outs):  # softmax + mixing of every task in one launch per direction, nothing stacked (csrc/gate_mix.hip)
                 return moe_mix(logits, outs)
         experts = torch.stack(outs, dim=1)  # [B, E, H]: the reference's literal form
         return [torch.matmul(torch.softmax(lg, dim=1).unsqueeze(1), experts).squeeze(1) for lg in logits]
