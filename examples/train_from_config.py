@@ -14,6 +14,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/ple_mini.config          (ple: every gate of a CGC level mixed in one launch; per-tower metrics)
     python examples/train_from_config.py tests/golden/pepnet_mini.config       (pepnet: EPNet / PPNet gates in one launch per level; a tower per task and domain)
     python examples/train_from_config.py tests/golden/dbmtl_mini.config        (dbmtl: every Bayesian relation tower in one launch, no concat tensor)
+    python examples/train_from_config.py tests/golden/dssm_mini.config         (dssm: a match model; sampled softmax without its score matrix, recall@k)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""
@@ -33,10 +34,20 @@ from torcheasyrec_amd.rank_model import build_rank_model  # noqa: E402
 from torcheasyrec_amd.sparse import KeyedJaggedTensor, KeyedTensor  # noqa: E402
 
 
+NEG_DATA_GROUP = "__NEG__"  # tzrec/datasets/utils.py:29
+
+
 def synthetic_batches(spec, n_rows, batch_size, seed=0):
     rng = np.random.default_rng(seed)
-    sparse = [f for f in spec.features if f.is_sparse]
-    dense = [f for f in spec.features if not f.is_sparse]
+    # data_config.negative_sampler (a match model): the item-side features it names in `attr_fields` travel in a data group of
+    # their own, "__NEG__", with batch + num_sample rows -- row i the positive of sample i, the rest negatives for the whole
+    # batch -- all drawn uniformly here.  This stands in for the reference's graph sampler (tzrec/datasets/sampler.py), which
+    # draws the negatives by item weight from its `input_path` table.
+    sampler = getattr(spec, "negative_sampler", None)
+    item_side = set(sampler["attr_fields"]) if sampler else set()
+    neg = [f for f in spec.features if f.name in item_side]
+    sparse = [f for f in spec.features if f.is_sparse and f.name not in item_side]
+    dense = [f for f in spec.features if not f.is_sparse and f.name not in item_side]
     for s in range(0, n_rows, batch_size):
         b = min(batch_size, n_rows - s)
         # one id per sample, except the sub-features of a `sequence_feature` block: a history of 0 .. sequence_length ids, the
@@ -52,7 +63,18 @@ def synthetic_batches(spec, n_rows, batch_size, seed=0):
         labels = {name: torch.from_numpy((rng.random(b) < 0.25).astype(np.int64)) for name in spec.label_fields}
         # data_config.sample_weight_fields: one float column each (the losses read them, torcheasyrec_amd/losses.py)
         weights = {name: torch.from_numpy((0.5 + rng.random(b)).astype(np.float32)) for name in spec.sample_weight_fields}
-        yield Batch({BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt}, labels, weights)
+        dense_groups, sparse_groups = {BASE_DATA_GROUP: kt}, {BASE_DATA_GROUP: kjt}
+        if sampler:
+            rows = b + int(sampler["num_sample"])
+            nsp, nde = [f for f in neg if f.is_sparse], [f for f in neg if not f.is_sparse]
+            if nsp:
+                nids = np.concatenate([rng.integers(0, f.num_embeddings, size=rows) for f in nsp]).astype(np.int64)
+                sparse_groups[NEG_DATA_GROUP] = KeyedJaggedTensor([f.name for f in nsp], torch.from_numpy(nids),
+                                                                  torch.ones(len(nsp) * rows, dtype=torch.int32), uniform_length=1)
+            if nde:
+                dense_groups[NEG_DATA_GROUP] = KeyedTensor([f.name for f in nde], [f.value_dim for f in nde],
+                                                           torch.from_numpy(rng.random((rows, sum(f.value_dim for f in nde)), dtype=np.float32)))
+        yield Batch(dense_groups, sparse_groups, labels, weights)
 
 
 def main(path):
@@ -65,7 +87,9 @@ def main(path):
     opt = build_dense_optimizer(named_dense_parameters(model), spec.dense_optimizer)
     # the `learning_rate` oneof of the two optimizer blocks and of every part (tzrec/main.py:877-882); stepped per step
     # unless by_epoch (main.py:542-544)
-    schedulers = [create_scheduler(model.fused_optimizer, spec.sparse_optimizer_block)] + create_dense_schedulers(opt, spec.dense_optimizer)
+    # (a match model has an embedding group, and so a fused sparse optimizer, per tower: `fused_optimizers`)
+    fused = model.fused_optimizers if hasattr(model, "fused_optimizers") else [model.fused_optimizer]
+    schedulers = [create_scheduler(fo, spec.sparse_optimizer_block) for fo in fused] + create_dense_schedulers(opt, spec.dense_optimizer)
     # train_config.grad_clipping / gradient_accumulation_steps around the dense optimizer (tzrec/main.py:848-876)
     from torcheasyrec_amd.optimizer import build_train_optimizer
 
@@ -95,7 +119,11 @@ def main(path):
     if dumper is not None:
         print("delta embedding dump:", dumper.final_dump(step))
         dumper.close()
-    print("tables:", {n: tuple(w.shape) for n, w in model.embedding_group.ebc.table_weights().items()})
+    if hasattr(model, "embedding_group"):
+        print("tables:", {n: tuple(w.shape) for n, w in model.embedding_group.ebc.table_weights().items()})
+    else:  # a match model: each tower's own
+        print("tables:", {f"{t}.{n}": tuple(w.shape) for t in ("user_tower", "item_tower")
+                          for n, w in getattr(model, t).embedding_group.ebc.table_weights().items()})
     # model_config.metrics (and every task tower's) on a held-out run of batches: the evaluate half of the reference's
     # train_and_evaluate (tzrec/main.py).  EVAL_GRAPH=1: forward and metric updates replayed from one hipGraph
     if spec.metrics:

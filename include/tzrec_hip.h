@@ -705,6 +705,63 @@ int tzr_relation_chain_fwd(const TzrRelationChain* h_rc, void* stream);
 size_t tzr_relation_chain_bwd_workspace(const TzrRelationChain* h_rc);
 int tzr_relation_chain_bwd(const TzrRelationChain* h_rc, void* stream);
 
+/* The similarity head of the match models (tzrec/models/match_model.py:50-64, 303-336, dssm.py:81-83, 147-155): normalize,
+ * similarity, temperature, softmax cross entropy and the rank of the positive, without the [B, C] score matrix in memory.
+ * u [B, D] and v [M, D] are the towers' outputs, fp32, any row stride that is a multiple of 4 floats.
+ *   cosine == 1:  u^_i = u_i / max(|u_i|, 1e-12), v^ likewise (F.normalize); cosine == 0: u^ = u, v^ = v
+ *   TZR_MATCH_SAMPLED,  M = B + N, N >= 0:  row i has C = 1 + N scores, s_i0 = <u^_i, v^_i> / T, s_ij = <u^_i, v^_{B+j-1}> / T;
+ *                                           the label column is 0
+ *   TZR_MATCH_IN_BATCH, M = B:              s_ij = <u^_i, v^_j> / T, C = B; the label column is i
+ *   l_i = logsumexp_j s_ij - s_i,label;  loss = sum(w l) / sum(w), 0 when sum(w) == 0 (w [B], nullable: mean(l));
+ *   rank_i = the number of columns j != label with s_ij > s_i,label.
+ * forward (one launch and a finishing one): writes loss [1], lse [B] = rmax + lsum, rmax [B] (the row's largest score) and lsum
+ *   [B] (log of the sum of exp(s - rmax); kept apart for the backward: their sum rounds at the size of the scores, 1 / T), pos
+ *   [B] (s_i,label), rank [B] int32, scale [1] (the reciprocal of the loss's denominator), with cosine ru [B] and rv [M] (the
+ *   inverse norms, DOUBLE: see csrc/match_softmax.hip), and, when `sim` is not 0, the scores sim [B, C] with row stride
+ *   sim_stride >= C.  `ws`: tzr_match_softmax_workspace bytes.
+ * backward (two launches; one when SAMPLED has N == 0): reads grad_loss [1] FROM DEVICE MEMORY, u, v, w, rmax, lsum, pos,
+ *   scale, ru, rv; writes du [B, D] and dv [M, D], through the normalisation when cosine is set.  w is a constant.
+ * Deterministic, no atomics, two runs are bit-equal.  TZR_ERR_UNSUPPORTED: D % 4 != 0, D < 4, D > TZR_MATCH_SOFTMAX_MAX_D, B < 1,
+ * M < B, M != B in IN_BATCH mode, an unknown mode, a `cosine` other than 0 or 1, a row stride that is no multiple of 4 or below
+ * the width, a sim_stride below C.  TZR_ERR_INVALID: a null or misaligned pointer (u / v / du / dv 16 bytes, ru / rv 8, the
+ * others 4; w and sim may be 0, ru and rv without cosine).  TZR_ERR_WORKSPACE: `ws` null, not 256-byte aligned or below the query
+ * less its 256 bytes of slack.  A refused call launches nothing. */
+#define TZR_MATCH_SOFTMAX_MAX_D 256
+#define TZR_MATCH_SAMPLED 0
+#define TZR_MATCH_IN_BATCH 1
+typedef struct TzrMatchSoftmax {
+  int64_t B, M;
+  int32_t D, mode, cosine, reserved;
+  float inv_temperature;
+  int32_t reserved2;
+  uint64_t u;          /* const float* [B, D] */
+  int64_t u_stride;
+  uint64_t v;          /* const float* [M, D] */
+  int64_t v_stride;
+  uint64_t w;          /* const float* [B], nullable */
+  uint64_t loss;       /* float* [1]            (forward writes) */
+  uint64_t lse;        /* float* [B]            (forward writes) */
+  uint64_t rmax;       /* float* [B]            (forward writes, backward reads) */
+  uint64_t lsum;       /* float* [B]            (forward writes, backward reads) */
+  uint64_t pos;        /* float* [B]            (forward writes, backward reads) */
+  uint64_t rank;       /* int32_t* [B]          (forward writes) */
+  uint64_t scale;      /* float* [1]            (forward writes, backward reads) */
+  uint64_t ru;         /* double* [B], cosine   (forward writes, backward reads) */
+  uint64_t rv;         /* double* [M], cosine   (forward writes, backward reads) */
+  uint64_t sim;        /* float* [B, C], nullable (forward writes) */
+  int64_t sim_stride;
+  uint64_t grad_loss;  /* const float* [1]      (backward) */
+  uint64_t du;         /* float* [B, D]         (backward) */
+  int64_t du_stride;
+  uint64_t dv;         /* float* [M, D]         (backward) */
+  int64_t dv_stride;
+  uint64_t ws;         /* workspace             (forward) */
+  uint64_t ws_bytes;
+} TzrMatchSoftmax;
+size_t tzr_match_softmax_workspace(const TzrMatchSoftmax* h_ms);
+int tzr_match_softmax_fwd(const TzrMatchSoftmax* h_ms, void* stream);
+int tzr_match_softmax_bwd(const TzrMatchSoftmax* h_ms, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

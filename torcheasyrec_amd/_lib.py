@@ -131,6 +131,25 @@ class TzrRelationChain(C.Structure):
 
 assert C.sizeof(TzrRelationChain) == 2176
 
+# tzr_match_softmax_* (include/tzrec_hip.h: TZR_MATCH_*)
+MATCH_SOFTMAX_MAX_D = 256
+MATCH_SAMPLED, MATCH_IN_BATCH = 0, 1
+
+
+class TzrMatchSoftmax(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("M", C.c_int64), ("D", C.c_int32), ("mode", C.c_int32), ("cosine", C.c_int32), ("reserved", C.c_int32),
+        ("inv_temperature", C.c_float), ("reserved2", C.c_int32),
+        ("u", C.c_uint64), ("u_stride", C.c_int64), ("v", C.c_uint64), ("v_stride", C.c_int64), ("w", C.c_uint64),
+        ("loss", C.c_uint64), ("lse", C.c_uint64), ("rmax", C.c_uint64), ("lsum", C.c_uint64), ("pos", C.c_uint64), ("rank", C.c_uint64), ("scale", C.c_uint64),
+        ("ru", C.c_uint64), ("rv", C.c_uint64), ("sim", C.c_uint64), ("sim_stride", C.c_int64),
+        ("grad_loss", C.c_uint64), ("du", C.c_uint64), ("du_stride", C.c_int64), ("dv", C.c_uint64), ("dv_stride", C.c_int64),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrMatchSoftmax) == 224
+
 
 class TzrSparseOptim(C.Structure):
     _fields_ = [
@@ -361,6 +380,9 @@ _SIGNATURES = {
     "tzr_relation_chain_fwd": (_i32, [_vp, _vp]),
     "tzr_relation_chain_bwd_workspace": (_sz, [_vp]),
     "tzr_relation_chain_bwd": (_i32, [_vp, _vp]),
+    "tzr_match_softmax_workspace": (_sz, [_vp]),
+    "tzr_match_softmax_fwd": (_i32, [_vp, _vp]),
+    "tzr_match_softmax_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

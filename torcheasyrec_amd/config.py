@@ -268,9 +268,17 @@ class TowerSpec:
         return bool(self.sample_weight_name) or self.weight != 1.0 or bool(self.task_space_indicator_label)
 
 
-def _loss_specs(blocks, tower: Optional[str], num_class: int, sparse_names) -> List[LossSpec]:
+# the model_config oneof's match (retrieval) members (protos/model.proto:71-76): their softmax_cross_entropy runs over the
+# similarity scores of one positive and its negatives, not over `num_class` logits (tzrec/models/match_model.py:281-336)
+MATCH_MODELS = ("dssm", "dssm_v2", "dat", "hstu_match", "mind")
+# data_config's `sampler` oneof (protos/data.proto:160-166)
+SAMPLER_KINDS = ("negative_sampler", "negative_sampler_v2", "hard_negative_sampler", "hard_negative_sampler_v2", "tdm_sampler")
+
+
+def _loss_specs(blocks, tower: Optional[str], num_class: int, sparse_names, match: bool = False) -> List[LossSpec]:
     """The entries of `losses` blocks, refused or validated here, when the spec is built; no block: one plain BCE (what every
-    model computed before the block was read)."""
+    model computed before the block was read).  `match`: the model block is a match model, whose softmax_cross_entropy has
+    `num_class: 1`."""
     where = f"task tower {tower}" if tower else "model_config"
     out = []
     for m in blocks:
@@ -285,7 +293,7 @@ def _loss_specs(blocks, tower: Optional[str], num_class: int, sparse_names) -> L
         kind, f = ls.kind, ls.fields
         if kind in ("binary_cross_entropy", "binary_focal_loss") and num_class != 1:
             raise ValueError(f"{where}: num_class must be 1 when loss type is {kind} (got {num_class})")
-        if kind == "softmax_cross_entropy" and num_class <= 1:
+        if kind == "softmax_cross_entropy" and num_class <= 1 and not match:
             raise ValueError(f"{where}: num_class must be greater than 1 when loss type is {kind} (got {num_class})")
         if kind == "jrc_loss":
             if num_class != 2:
@@ -330,6 +338,10 @@ class PipelineSpec:
     losses: List[LossSpec] = field(default_factory=list)
     task_towers: List[TowerSpec] = field(default_factory=list)
     sample_weight_fields: List[str] = field(default_factory=list)  # data_config.sample_weight_fields
+    # data_config.negative_sampler (protos/sampler.proto:5-23) as written, num_sample an int and attr_fields a list; None: none
+    negative_sampler: Optional[dict] = None
+    sampler_kinds: List[str] = field(default_factory=list)  # the members of data_config's `sampler` oneof that are written
+    model_config_keys: List[str] = field(default_factory=list)  # every field written in model_config
 
     def tower(self, name: Optional[str]) -> Optional[TowerSpec]:
         return next((t for t in self.task_towers if t.tower_name == name), None)
@@ -557,10 +569,16 @@ def load_pipeline_spec(text: str) -> PipelineSpec:
     for t in (spec.model.many("task_towers") if spec.model else []):
         spec.metrics += _metric_specs(t.many("metrics"), str(t.one("tower_name")), str(t.one("label_name")))
     spec.sample_weight_fields = [str(x) for x in dc.many("sample_weight_fields")]
+    spec.sampler_kinds = [k for k in SAMPLER_KINDS if dc.has(k)]
+    spec.model_config_keys = [str(k) for k in mc]
+    if dc.has("negative_sampler"):
+        ns = dc.one("negative_sampler")
+        spec.negative_sampler = {**{k: v[-1] for k, v in ns.items()}, "num_sample": int(ns.one("num_sample", 0)),
+                                 "attr_fields": [str(x) for x in ns.many("attr_fields")]}
     sparse_names = {f.name for f in spec.features if f.is_sparse}
     towers = spec.model.many("task_towers") if spec.model else []
     if mc.has("losses") or not towers:  # (a multi-task model reads its towers' blocks only, multi_task_rank.py:80-95)
-        spec.losses = _loss_specs(mc.many("losses"), None, spec.num_class, sparse_names)
+        spec.losses = _loss_specs(mc.many("losses"), None, spec.num_class, sparse_names, match=spec.model_name in MATCH_MODELS)
     for t in towers:
         ts = TowerSpec(tower_name=str(t.one("tower_name")), label_name=str(t.one("label_name")), num_class=int(t.one("num_class", 1)),
                        weight=float(t.one("weight", 1.0)), sample_weight_name=t.one("sample_weight_name"),

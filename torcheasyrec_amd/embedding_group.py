@@ -126,8 +126,11 @@ class EmbeddingGroup(nn.Module):
         batch_size: int = 1024,
         exchange: str = "exact",
         use_planner: bool = False,
+        data_group: str = BASE_DATA_GROUP,
     ) -> None:
-        """`exchange`: "exact" | "capacity" ids exchange of the sharded pooled collections (sharding.py).
+        """`data_group`: the batch's data group this collection reads (a match model's item tower under a negative sampler reads
+        "__NEG__", whose tensors hold more rows than the labels: tzrec/datasets/utils.py:29).
+        `exchange`: "exact" | "capacity" ids exchange of the sharded pooled collections (sharding.py).
         `process_group`: shard the tables over its ranks (the seam DistributedModelParallel fills in
         the reference, tzrec/main.py:783-804): pooled tables go to a ShardedEmbeddingBagCollection
         (placement from `plan`, e.g. planner.plan_tables, or the size heuristic), sequence tables to
@@ -137,6 +140,7 @@ class EmbeddingGroup(nn.Module):
         `plan` take MixedShardedEmbeddingBagCollection (one exchange lane per dim)."""
         super().__init__()
         self._pg, self._plan_in, self._dp_max_rows = process_group, plan, dp_max_rows
+        self._data_group = data_group
         name_to_feature = {f.name: f for f in features}
         configs: "OrderedDict[str, EmbeddingBagConfig]" = OrderedDict()
         zch_blocks: Dict[str, object] = {}
@@ -495,8 +499,8 @@ class EmbeddingGroup(nn.Module):
         return None
 
     def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
-        sparse = batch.sparse_features.get(BASE_DATA_GROUP)
-        dense = batch.dense_features.get(BASE_DATA_GROUP)
+        sparse = batch.sparse_features.get(self._data_group)
+        dense = batch.dense_features.get(self._data_group)
         if self.mc is not None:
             self.mc.train(self.training)
             sparse = self.mc.remap_step(sparse)
@@ -528,8 +532,8 @@ class EmbeddingGroup(nn.Module):
                 parts.append(pooled[g][:, run[0]:run[1]])
             out[g] = torch.cat(parts, dim=1)
         if self._seq_info:
-            out.update(self._forward_sequence_groups(batch.sparse_features.get(BASE_DATA_GROUP), dense_cols,
-                                                     batch.sequence_mulval_lengths.get(BASE_DATA_GROUP),
+            out.update(self._forward_sequence_groups(batch.sparse_features.get(self._data_group), dense_cols,
+                                                     batch.sequence_mulval_lengths.get(self._data_group),
                                                      batch.sequence_dense_features))
         for g, encs in self._group_name_to_seq_encoders.items():
             out[g] = torch.cat([out[g]] + [enc(out) for enc in encs], dim=1)

@@ -20,7 +20,7 @@ from . import _lib
 from .config import MetricSpec, PipelineSpec
 from .embedding_group import BASE_DATA_GROUP, Batch, _batch_tensors, zch_wrapper_of
 
-BUILT_KINDS = ("auc", "grouped_auc", "normalized_entropy")
+BUILT_KINDS = ("auc", "grouped_auc", "normalized_entropy", "recall_at_k")
 
 
 def _world(pg) -> int:
@@ -216,6 +216,37 @@ class GroupedAUC:
         return out[0][keep], out[1][keep], out[2][keep]
 
 
+class RecallAtK:
+    """`recall_at_k { top_k }` of a match model (tzrec/metrics/recall_at_k.py): the share of the samples whose positive is among
+    the k highest scores of its row.  `update(rank)` takes the rank of the positive -- the number of other columns with a
+    strictly higher score, what the similarity head counts while it walks the scores -- and adds sum_i [rank_i < k] and the number
+    of rows to two int64 device counters: no host round trip, capturable.
+
+    Without ties this equals the reference's `argsort(descending)[:, :k]` / `gather` of the one-hot label (recall_at_k.py:44-49).
+    With ties the reference's result depends on the order its sort leaves equal scores in; here a tie never counts against the
+    positive."""
+
+    def __init__(self, top_k: int = 5, device=None, process_group=None) -> None:
+        self.top_k, self._pg = int(top_k), process_group
+        if self.top_k < 1:
+            raise ValueError(f"recall_at_k: top_k must be >= 1 (got {top_k})")
+        self._state = torch.zeros(2, dtype=torch.int64, device=device)  # {hits, rows}
+
+    def update(self, rank: torch.Tensor) -> None:
+        rank = rank.detach().reshape(-1)
+        self._state[0] += (rank < self.top_k).sum()
+        self._state[1] += rank.numel()
+
+    def reset(self) -> None:
+        self._state.zero_()
+
+    def compute(self) -> torch.Tensor:
+        s = self._state.clone()
+        if _world(self._pg) > 1:
+            _all_reduce_sum(s, self._pg)
+        return (s[0].to(torch.float64) / s[1].to(torch.float64)).to(torch.float32)
+
+
 def first_id_per_sample(kjt, key: str) -> torch.Tensor:
     """`kjt[key].to_padded_dense(1)[:, 0]` (rank_model.py:418-420): the first id of every sample, 0 for an empty bag --
     from the device tensors alone (`kjt[key]` asks the host for the key's extent), so it can be captured."""
@@ -243,7 +274,15 @@ class Evaluator:
         self.device = torch.device(device) if device is not None else None
         self.metrics: Dict[str, object] = {}
         self._specs: Dict[str, MetricSpec] = {}
+        self._recalls: List[str] = []  # the match models' metrics: fed predictions["rank"], no label
         for ms in spec.metrics:
+            if ms.kind == "recall_at_k":  # keyed recall@<k> (match_model.py:345-356)
+                name = f"recall@{int(ms.fields.get('top_k', 5))}" + ms.suffix
+                if name in self.metrics:
+                    raise ValueError(f"metric {name!r} is configured twice")
+                self.metrics[name] = RecallAtK(int(ms.fields.get("top_k", 5)), device=device, process_group=self._pg)
+                self._recalls.append(name)
+                continue
             if ms.kind == "auc":
                 m = BinnedAUC(int(ms.fields.get("thresholds", 200)), device=device, process_group=self._pg)
             elif ms.kind == "normalized_entropy":
@@ -269,6 +308,8 @@ class Evaluator:
     def update(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> None:
         if self._select is not None:
             predictions = self._select(predictions, batch)
+        for name in self._recalls:
+            self.metrics[name].update(predictions["rank"])
         for suffix, names in self._towers.items():
             probs = predictions[self._probs_key[suffix]]
             by_kind = {self._specs[n].kind: n for n in names}
