@@ -762,6 +762,85 @@ size_t tzr_match_softmax_workspace(const TzrMatchSoftmax* h_ms);
 int tzr_match_softmax_fwd(const TzrMatchSoftmax* h_ms, void* stream);
 int tzr_match_softmax_bwd(const TzrMatchSoftmax* h_ms, void* stream);
 
+/* The behaviour-to-interest capsule layer of MIND (tzrec/modules/capsule.py:125-231), restated on the jagged rows: pad /
+ * truncate to max_seq_len, low capsules U = X W, num_iters rounds of dynamic routing, squash, capsule mask -- one launch
+ * forward, two backward, nothing of shape [B, S, H] in memory.
+ *   x [N, L] fp32 jagged rows (unit column stride, row stride a multiple of 4 floats, 16-byte aligned rows), offsets [B + 1]
+ *   int64 (non-decreasing, offsets[B] <= N), w [L, H] contiguous (`bilinear_matrix`), logits0 [N, K] or 0 for zeros.
+ *   Sample b: len_b = offsets[b + 1] - offsets[b], its first s_b = min(len_b, S) rows take part;
+ *   k_b = K with const_caps_num, else max(1, #{ j < K : 2^j < len_b }) (= arange(K) < clamp(log2(len_b), 1, K), from the
+ *   UNTRUNCATED length); a sample without rows has high = 0 and one valid capsule.
+ *   logits = logits0 * stddev; every iteration: c = softmax over the k_b valid capsules of logits * scale (a masked capsule's
+ *   weight is exactly 0); except in the last, logits = c + <high_k, u_n / max(|u_n|, 1e-12)> with high = c^T U (the reference
+ *   adds the agreement to the softmax WEIGHTS); the last one: pre = c^T U, high_k = pre_k (r^squash_pow / e) with
+ *   e = max(|pre_k|, 1e-7), r = e^2 / (1 + e^2).
+ * forward writes high [B K, H] (row b K + k, row stride high_stride; rows k >= k_b are zeros), mask [B, K] (bytes 0 / 1), c
+ *   [N, K] (the final routing weights; rows behind S are zeros) and pre [B, K, H] (contiguous; for the backward).
+ * backward: the routing weights are constants for autograd (capsule.py:146, 154-157), so with Z = c^T X per sample and dpre
+ *   the gradient in front of the squash (through max(., 1e-7) as torch.max passes it): dx_n = sum_k c[n, k] (dpre W^T)[k, :]
+ *   (rows behind S: zeros), dw = sum_b Z_b^T dpre_b.  A per-sample launch of min(B, TZR_CAPSULE_BWD_MAX_GRID) workgroups (workgroup
+ *   g takes the samples g, g + grid, ... in that order) leaves dw as one partial [L x H] row per workgroup in `ws`
+ *   (tzr_capsule_workspace bytes); a finishing launch adds the rows in the interleaved order (csrc/parts_sum.h).  logits0 gets
+ *   no gradient.  No atomics; every sum's order is a function of the shapes and the offsets alone: two runs are bit-equal.
+ * Limits (TZR_ERR_UNSUPPORTED beyond): L, H multiples of 4 in [4, TZR_CAPSULE_MAX_DIM]; 1 <= K <= TZR_CAPSULE_MAX_K; 1 <=
+ *   num_iters <= TZR_CAPSULE_MAX_ITERS; 1 <= S <= TZR_CAPSULE_MAX_S and ceil16(S) * H <= TZR_CAPSULE_MAX_SH (the low capsules of one
+ *   sample in LDS: S <= 128 at H <= 64, S <= 64 at H <= 128); scale > 0; B, N < 2^31; a row stride that is no multiple of 4 or below the
+ *   width.  TZR_ERR_INVALID: a null or misaligned pointer (x / high / grad_high / dx 16 bytes, offsets 8, w 16, the others 4; x and dx
+ *   may be 0 when N == 0, logits0 may be 0), B < 0, N < 0.  TZR_ERR_WORKSPACE: `ws` null, not 256-byte aligned or below the
+ *   query less its 256 bytes of slack.  B == 0: TZR_OK without a launch.  A refused call launches nothing.
+ * A new struct and entry points, no change to existing ones: the ABI version stays 15. */
+#define TZR_CAPSULE_MAX_DIM 128
+#define TZR_CAPSULE_MAX_K 8
+#define TZR_CAPSULE_MAX_ITERS 8
+#define TZR_CAPSULE_MAX_S 128
+#define TZR_CAPSULE_MAX_SH 8192
+#define TZR_CAPSULE_BWD_MAX_GRID 512
+typedef struct TzrCapsule {
+  int64_t B, N;
+  int32_t L, H, K, S, num_iters, const_caps_num;
+  float scale, stddev, squash_pow; /* routing_logits_scale, routing_logits_stddev, squash_pow */
+  int32_t reserved;
+  uint64_t x;           /* const float* [N, L] */
+  int64_t x_stride;
+  uint64_t offsets;     /* const int64_t* [B + 1] */
+  uint64_t w;           /* const float* [L, H] */
+  uint64_t logits0;     /* const float* [N, K], nullable */
+  uint64_t high;        /* float* [B K, H]        (forward writes) */
+  int64_t high_stride;
+  uint64_t mask;        /* uint8_t* [B, K]        (forward writes) */
+  uint64_t c;           /* float* [N, K]          (forward writes, backward reads) */
+  uint64_t pre;         /* float* [B, K, H]       (forward writes, backward reads) */
+  uint64_t grad_high;   /* const float* [B K, H]  (backward) */
+  int64_t grad_high_stride;
+  uint64_t dx;          /* float* [N, L]          (backward) */
+  int64_t dx_stride;
+  uint64_t dw;          /* float* [L, H]          (backward) */
+  uint64_t ws;          /* workspace              (backward) */
+  uint64_t ws_bytes;
+} TzrCapsule;
+size_t tzr_capsule_workspace(const TzrCapsule* h_cap);
+int tzr_capsule_fwd(const TzrCapsule* h_cap, void* stream);
+int tzr_capsule_bwd(const TzrCapsule* h_cap, void* stream);
+
+/* MIND's label-aware attention (tzrec/models/mind.py:303-333): the positive item of a sample attends over its interests.
+ * i [B K, D] (row b K + k = interest k of sample b), v [B, D] (the first B rows of the item embeddings), fp32, row strides that are
+ * multiples of 4 floats, 16-byte aligned rows; mask [B, K] bytes (the capsule mask).
+ *   forward:   a_k = <i_bk, v_b>; w = softmax over the valid capsules of simi_pow a_k (a masked capsule's weight is exactly 0);
+ *              out[b] = sum_k w_k i_bk; d_w [B, K] is kept for the backward.
+ *   backward:  t_k = <g_b, i_bk>; da_k = simi_pow w_k (t_k - sum_j w_j t_j); d_di[b K + k] = w_k g_b + da_k v_b (zero rows for masked
+ *              capsules); d_dv[b] = sum_k da_k i_bk.
+ * One launch each way, one wave per sample, fixed summation order, no atomics: bit-reproducible.  TZR_ERR_UNSUPPORTED: D % 4
+ * != 0, D < 4, D > TZR_LABEL_ATTN_MAX_D, K < 1, K > TZR_LABEL_ATTN_MAX_K, simi_pow <= 0, B >= 2^31, a row stride that is no
+ * multiple of 4 or below D.  TZR_ERR_INVALID: a null or misaligned pointer (rows 16 bytes, d_w 4), B < 0.  B == 0 is TZR_OK
+ * without a launch.  Entry points only, no struct changes: the ABI version stays 15. */
+#define TZR_LABEL_ATTN_MAX_D 256
+#define TZR_LABEL_ATTN_MAX_K 8
+int tzr_label_attn_fwd(const float* d_i, int64_t i_stride, const float* d_v, int64_t v_stride, const uint8_t* d_mask, int64_t B, int K, int D,
+                       float simi_pow, float* d_out, int64_t out_stride, float* d_w, void* stream);
+int tzr_label_attn_bwd(const float* d_grad_out, int64_t grad_out_stride, const float* d_i, int64_t i_stride, const float* d_v, int64_t v_stride,
+                       const float* d_w, const uint8_t* d_mask, int64_t B, int K, int D, float simi_pow, float* d_di, int64_t di_stride,
+                       float* d_dv, int64_t dv_stride, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

@@ -150,6 +150,25 @@ class TzrMatchSoftmax(C.Structure):
 
 assert C.sizeof(TzrMatchSoftmax) == 224
 
+# limits of tzr_capsule_* (include/tzrec_hip.h: TZR_CAPSULE_*)
+CAPSULE_MAX_DIM, CAPSULE_MAX_K, CAPSULE_MAX_ITERS, CAPSULE_MAX_S, CAPSULE_MAX_SH, CAPSULE_BWD_MAX_GRID = 128, 8, 8, 128, 8192, 512
+
+
+class TzrCapsule(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("N", C.c_int64),
+        ("L", C.c_int32), ("H", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("num_iters", C.c_int32), ("const_caps_num", C.c_int32),
+        ("scale", C.c_float), ("stddev", C.c_float), ("squash_pow", C.c_float), ("reserved", C.c_int32),
+        ("x", C.c_uint64), ("x_stride", C.c_int64), ("offsets", C.c_uint64), ("w", C.c_uint64), ("logits0", C.c_uint64),
+        ("high", C.c_uint64), ("high_stride", C.c_int64), ("mask", C.c_uint64), ("c", C.c_uint64), ("pre", C.c_uint64),
+        ("grad_high", C.c_uint64), ("grad_high_stride", C.c_int64), ("dx", C.c_uint64), ("dx_stride", C.c_int64), ("dw", C.c_uint64),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrCapsule) == 192
+LABEL_ATTN_MAX_D, LABEL_ATTN_MAX_K = 256, 8  # TZR_LABEL_ATTN_MAX_*
+
 
 class TzrSparseOptim(C.Structure):
     _fields_ = [
@@ -383,6 +402,11 @@ _SIGNATURES = {
     "tzr_match_softmax_workspace": (_sz, [_vp]),
     "tzr_match_softmax_fwd": (_i32, [_vp, _vp]),
     "tzr_match_softmax_bwd": (_i32, [_vp, _vp]),
+    "tzr_capsule_workspace": (_sz, [_vp]),
+    "tzr_capsule_fwd": (_i32, [_vp, _vp]),
+    "tzr_capsule_bwd": (_i32, [_vp, _vp]),
+    "tzr_label_attn_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, C.c_float, _vp, _i64, _vp, _vp]),
+    "tzr_label_attn_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp, _i64, _vp, _i64, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

@@ -1,9 +1,11 @@
-"""The match (retrieval) models: the fused similarity head and DSSM built from its config.
+"""The match (retrieval) models: the fused similarity head, MIND's label-aware attention, and DSSM and MIND built from their configs.
 
 `match_softmax` is the head of tzrec/models/match_model.py:50-64, 303-336 and dssm.py:81-83, 147-155 -- normalize,
 similarity, temperature, softmax cross entropy -- plus the rank of the positive that recall@k needs, in one autograd Function over
 tzr_match_softmax_fwd / _bwd (csrc/match_softmax.hip): the [B, 1 + N] (or [B, B]) score matrix is never in memory unless the
 caller asks for it.  `FUSED_MATCH_SOFTMAX = False`, or a shape outside `match_softmax_ok`, runs the reference's literal form.
+`label_attention` (tzrec/models/mind.py:303-333, tzr_label_attn_fwd / _bwd, csrc/label_attention.hip) is switched the same way by
+`FUSED_LABEL_ATTENTION` and `label_attention_ok`; MIND's capsule layer is capsule.py's.
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from .capsule import CapsuleConfig, CapsuleLayer
 from .embedding_group import BASE_DATA_GROUP, Batch, EmbeddingGroup
 
 SAMPLED, IN_BATCH = _lib.MATCH_SAMPLED, _lib.MATCH_IN_BATCH
@@ -164,19 +167,106 @@ def match_softmax(user: torch.Tensor, item: torch.Tensor, mode: int, cosine: boo
     return _literal(user, item, mode, bool(cosine), float(temperature), weights, want_sim)
 
 
+FUSED_LABEL_ATTENTION = True  # profiles/capsule: with the capsule layer, against the literal forms
+
+
+def label_attention_literal(interests: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, simi_pow: float) -> torch.Tensor:
+    """tzrec/models/mind.py:303-333, word for word"""
+    pos_item_emb = item[:interests.size(0)]
+    interest_weight = torch.einsum("bkd, bd->bk", interests, pos_item_emb)
+    threshold = (mask.to(interests.dtype) * 2 - 1) * float("inf")
+    interest_weight = torch.minimum(interest_weight, threshold)
+    interest_weight = interest_weight.unsqueeze(-1) * simi_pow
+    interest_weight = torch.nn.functional.softmax(interest_weight, dim=1)
+    return torch.sum(torch.multiply(interest_weight, interests), dim=1)
+
+
+def _interests_ok(x: torch.Tensor) -> bool:
+    """[B, K, D] rows of one [B K, D] operand with a row stride"""
+    return bool(x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(1) % 4 == 0 and x.stride(1) >= x.shape[2]
+                and x.stride(0) == x.shape[1] * x.stride(1) and x.data_ptr() % 16 == 0)
+
+
+def label_attention_ok(interests: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, simi_pow: float) -> bool:
+    """what tzr_label_attn_* takes: fp32 interests [B, K, D] whose B K rows have one stride (a multiple of 4 floats, 16-byte
+    aligned; a column slice of a [B K, .] buffer is fine), item [M >= B, D] rows likewise, mask [B, K] bool contiguous; D % 4 == 0,
+    4 <= D <= 256, 1 <= K <= 8, B >= 1, simi_pow > 0; everything on the device of the loaded library"""
+    if interests.dim() != 3 or item.dim() != 2 or mask.dim() != 2:
+        return False
+    B, K, D = interests.shape
+    if (interests.device.type == "cpu") != (_lib.backend() == "emu") or item.device != interests.device or mask.device != interests.device:
+        return False
+    if not (D % 4 == 0 and 4 <= D <= _lib.LABEL_ATTN_MAX_D and 1 <= K <= _lib.LABEL_ATTN_MAX_K and B >= 1 and simi_pow > 0):
+        return False
+    return bool(_interests_ok(interests) and item.shape[0] >= B and _rows_ok(item, D) and mask.shape == (B, K) and mask.dtype == torch.bool
+                and mask.is_contiguous())
+
+
+class _LabelAttentionFn(torch.autograd.Function):
+    """Inputs: interests [B, K, D], item [M, D], mask [B, K] bool.  Outputs: user_emb [B, D] and the weights w [B, K] (saved for
+    the backward, no gradient).  The item gradient is zero behind its first B rows."""
+
+    @staticmethod
+    def forward(ctx, interests, item, mask, simi_pow):
+        B, K, D = interests.shape
+        dev = interests.device
+        out = torch.empty(B, D, dtype=torch.float32, device=dev)
+        w = torch.empty(B, K, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().tzr_label_attn_fwd(_lib.ptr(interests), interests.stride(1), _lib.ptr(item), item.stride(0), _lib.ptr(mask), B, K, D,
+                                                 float(simi_pow), _lib.ptr(out), D, _lib.ptr(w), _lib.stream_ptr(dev)), "tzr_label_attn_fwd")
+        ctx.save_for_backward(interests, item, mask, w)
+        ctx.simi_pow = float(simi_pow)
+        ctx.mark_non_differentiable(w)
+        ctx.set_materialize_grads(False)  # (no zero-filled gradient for w: a launch a pass)
+        return out, w
+
+    @staticmethod
+    def backward(ctx, gout, _gw):
+        if gout is None:
+            return None, None, None, None
+        interests, item, mask, w = ctx.saved_tensors
+        B, K, D = interests.shape
+        dev = interests.device
+        g = gout.to(torch.float32)
+        if not _rows_ok(g, D):
+            g = g.contiguous()
+        di = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+        dv = torch.zeros(item.shape, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().tzr_label_attn_bwd(_lib.ptr(g), g.stride(0), _lib.ptr(interests), interests.stride(1), _lib.ptr(item), item.stride(0),
+                                                 _lib.ptr(w), _lib.ptr(mask), B, K, D, ctx.simi_pow, _lib.ptr(di), D, _lib.ptr(dv), D,
+                                                 _lib.stream_ptr(dev)), "tzr_label_attn_bwd")
+        return di, dv, None, None
+
+
+def label_attention(interests: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, simi_pow: float, want_weights: bool = False):
+    """MIND's label-aware attention (mind.py:303-333): user_emb_b = sum_k w_k I_bk with w = softmax over the valid capsules of
+    simi_pow <I_bk, v_b>, v = the first B rows of `item` [M, D].  One launch each way, unless FUSED_LABEL_ATTENTION is off or
+    `label_attention_ok` refuses the shape: then the literal form runs.  want_weights: -> (user_emb, w [B, K])."""
+    if FUSED_LABEL_ATTENTION and label_attention_ok(interests, item, mask, simi_pow):
+        out, w = _LabelAttentionFn.apply(interests, item, mask, float(simi_pow))
+    else:
+        out = label_attention_literal(interests, item, mask, float(simi_pow))
+        w = None
+        if want_weights:
+            a = torch.einsum("bkd, bd->bk", interests, item[:interests.size(0)]).detach()
+            w = torch.softmax(torch.minimum(a, (mask.to(a.dtype) * 2 - 1) * float("inf")) * float(simi_pow), dim=1)
+    return (out, w) if want_weights else out
+
+
 NEG_DATA_GROUP = "__NEG__"  # tzrec/datasets/utils.py:29: the item-side features the negative sampler delivers, B + N rows
 
 
 class MatchTower(nn.Module):
-    """Base match tower (tzrec/models/match_model.py:110-199): one feature group, named by the tower block's `input`, behind an
-    EmbeddingGroup of its own over that group's features."""
+    """Base match tower (tzrec/models/match_model.py:110-199): one feature group, named by the tower block's `input` (MIND's user
+    tower: that one and its history group), behind an EmbeddingGroup of its own over those groups' features."""
 
     def __init__(self, tower_config, output_dim: int, similarity: str, feature_group, features, device=None, sparse_optimizer=None,
                  batch_size: int = 1024, data_group: str = BASE_DATA_GROUP) -> None:
         super().__init__()
         self._group_name = str(tower_config.one("input"))
         self._output_dim, self._similarity = int(output_dim), similarity
-        self.embedding_group = EmbeddingGroup(features, [feature_group], device=device, sparse_optimizer=sparse_optimizer,
+        groups = list(feature_group) if isinstance(feature_group, (list, tuple)) else [feature_group]
+        self.embedding_group = EmbeddingGroup(features, groups, device=device, sparse_optimizer=sparse_optimizer,
                                               batch_size=batch_size, data_group=data_group)
 
     def build_input(self, batch: Batch) -> Dict[str, torch.Tensor]:
@@ -218,60 +308,53 @@ class DSSMTower(MatchTower):
         return self.embed(self.build_input(batch)[self._group_name])
 
 
-class ConfigDSSM(nn.Module):
-    """`dssm { user_tower {} item_tower {} output_dim similarity temperature in_batch_negative }` (tzrec/models/dssm.py:86-155,
-    match_model.py:246-336): two DSSMTowers, each with the EmbeddingGroup of its own feature group, and the similarity head.
+class ConfigMatchModel(nn.Module):
+    """What the config-built match models share (tzrec/models/match_model.py:246-336): the refusals, the two towers' feature
+    groups and features, the similarity head and the plumbing the pipelines read.  A subclass names its block (`_NAME`), the
+    block's and the towers' fields, the default similarity, and builds `user_tower` / `item_tower` in `_build_towers`;
+    `_embeddings(batch)` hands the head its user [B, D] and item [M, D] rows, `_head_cosine` says whether the head still
+    normalizes them."""
 
-    With `data_config.negative_sampler` the item tower reads the batch's "__NEG__" data group: B + num_sample rows, row i the
-    positive of user row i, the rest negatives shared by the batch; with `in_batch_negative` it reads the base group's B rows and
-    every other row of the batch is a negative.  Without either the positive is the only column (loss 0), as in the reference.
-
-    `loss_and_predictions(batch)` -- what the train pipelines call -- runs the fused head: {"softmax_cross_entropy": loss} and
-    {"rank": rank} (plus "similarity" when `want_similarity` is set), no score matrix otherwise.  `forward(batch)` keeps the
-    literal contract, {"similarity": [B, C]} (plus "rank"), for `loss(predictions, batch)` and evaluation.
-
-    Refused when built, by name: every sampler but `negative_sampler`; `variational_dropout`; `train_metrics`; any loss but one
-    `softmax_cross_entropy`; any metric but `recall_at_k` (both the reference's own assertions, match_model.py:284-291, 345-348);
-    `in_batch_negative` with a sampler; a table that both towers' groups would share; a zero-collision-hash feature; sharded
-    towers (`process_group`); a field the `dssm` block or a tower block does not have."""
-
-    _FIELDS = ("user_tower", "item_tower", "output_dim", "similarity", "temperature", "in_batch_negative")
-    _TOWER_FIELDS = ("input", "mlp")
+    _NAME = ""
+    _FIELDS: tuple = ()
+    _TOWER_FIELDS: Dict[str, tuple] = {}
+    _TOWER_GROUPS: Dict[str, tuple] = {"user_tower": ("input",), "item_tower": ("input",)}  # the tower fields that name a feature group
+    _DEFAULT_SIMILARITY = "INNER_PRODUCT"
 
     def __init__(self, spec, device=None, sparse_optimizer=None) -> None:
         super().__init__()
         from .rank_model import RankModel
 
-        m = spec.model
+        name, m = self._NAME, spec.model
         if RankModel._build_pg is not None:
-            raise NotImplementedError("dssm: `process_group` (sharded towers) is not built")
+            raise NotImplementedError(f"{name}: `process_group` (sharded towers) is not built")
         other = sorted(k for k in m if k not in self._FIELDS)
         if other:
-            raise ValueError(f"dssm: dssm has no field {other[0]!r} (fields: {', '.join(self._FIELDS)})")
+            raise ValueError(f"{name}: {name} has no field {other[0]!r} (fields: {', '.join(self._FIELDS)})")
         for k in spec.sampler_kinds:
             if k != "negative_sampler":
-                raise NotImplementedError(f"dssm: data_config `{k}` is not built (built: negative_sampler)")
+                raise NotImplementedError(f"{name}: data_config `{k}` is not built (built: negative_sampler)")
         for k in ("variational_dropout", "train_metrics"):
             if k in spec.model_config_keys:
-                raise NotImplementedError(f"dssm: model_config `{k}` is not built")
+                raise NotImplementedError(f"{name}: model_config `{k}` is not built")
         if len(spec.losses) != 1 or spec.losses[0].kind != "softmax_cross_entropy":
-            raise ValueError(f"dssm: a match model takes exactly one loss, softmax_cross_entropy (got {[l.kind for l in spec.losses]})")
+            raise ValueError(f"{name}: a match model takes exactly one loss, softmax_cross_entropy (got {[l.kind for l in spec.losses]})")
         if float(spec.losses[0].fields.get("label_smoothing", 0.0)) != 0.0:
-            raise NotImplementedError("dssm: softmax_cross_entropy `label_smoothing` is not built for match models")
+            raise NotImplementedError(f"{name}: softmax_cross_entropy `label_smoothing` is not built for match models")
         for ms in spec.metrics:
             if ms.kind != "recall_at_k":
-                raise ValueError(f"dssm: a match model's metrics are recall_at_k only (got {ms.kind!r})")
+                raise ValueError(f"{name}: a match model's metrics are recall_at_k only (got {ms.kind!r})")
         self._in_batch = bool(m.one("in_batch_negative", False))
         self._sampler = spec.negative_sampler
         if self._in_batch and self._sampler is not None:
-            raise ValueError("dssm: `in_batch_negative: true` together with a negative_sampler is not built (the reference adds "
+            raise ValueError(f"{name}: `in_batch_negative: true` together with a negative_sampler is not built (the reference adds "
                              "the in-batch columns to the sampled ones)")
         for k in ("user_tower", "item_tower", "output_dim"):
             if not m.has(k):
-                raise ValueError(f"dssm: needs `{k}`")
-        similarity = str(m.one("similarity", "INNER_PRODUCT")).upper()
+                raise ValueError(f"{name}: needs `{k}`")
+        similarity = str(m.one("similarity", self._DEFAULT_SIMILARITY)).upper()
         if similarity not in ("INNER_PRODUCT", "COSINE"):
-            raise ValueError(f"dssm: similarity {similarity!r} (INNER_PRODUCT, COSINE)")
+            raise ValueError(f"{name}: similarity {similarity!r} (INNER_PRODUCT, COSINE)")
         self._cosine, self._temperature = similarity == "COSINE", float(m.one("temperature", 1.0))
         self._mode = IN_BATCH if self._in_batch else SAMPLED
         self._spec, self._pg = spec, None
@@ -282,33 +365,39 @@ class ConfigDSSM(nn.Module):
         towers, tables = {}, {}
         for which in ("user_tower", "item_tower"):
             t = m.one(which)
-            other = sorted(k for k in t if k not in self._TOWER_FIELDS)
+            other = sorted(k for k in t if k not in self._TOWER_FIELDS[which])
             if other:
-                raise ValueError(f"dssm: {which} has no field {other[0]!r} (fields: {', '.join(self._TOWER_FIELDS)})")
-            gname = str(t.one("input"))
-            if gname not in groups:
-                raise ValueError(f"dssm: {which}.input {gname!r} is not a feature group of the config")
-            g = groups[gname]
-            names = list(g.feature_names) + [n for sg in g.sequence_groups for n in sg.feature_names]
-            feats = [by_name[n] for n in dict.fromkeys(names) if n in by_name]
+                raise ValueError(f"{name}: {which} has no field {other[0]!r} (fields: {', '.join(self._TOWER_FIELDS[which])})")
+            gs, feats = [], []
+            for field in self._TOWER_GROUPS[which]:
+                if not t.has(field):
+                    raise ValueError(f"{name}: {which} needs `{field}`")
+                gname = str(t.one(field))
+                if gname not in groups:
+                    raise ValueError(f"{name}: {which}.{field} {gname!r} is not a feature group of the config")
+                g = groups[gname]
+                gs.append(g)
+                feats += list(g.feature_names) + [n for sg in g.sequence_groups for n in sg.feature_names]
+            feats = [by_name[n] for n in dict.fromkeys(feats) if n in by_name]
             for f in feats:
                 if f.zch is not None:
-                    raise NotImplementedError(f"dssm: {which}: feature {f.name!r} has a zero-collision hash (`zch`): not built in a match tower")
+                    raise NotImplementedError(f"{name}: {which}: feature {f.name!r} has a zero-collision hash (`zch`): not built in a match tower")
             tables[which] = {f.embedding_name or f"{f.name}_emb" for f in feats if f.is_sparse}
-            towers[which] = (t, g, feats)
+            towers[which] = (t, gs, feats)
         shared = sorted(tables["user_tower"] & tables["item_tower"])
         if shared:
-            raise NotImplementedError(f"dssm: table {shared[0]!r} appears in both towers' groups: each tower owns its tables")
-        out_dim = int(m.one("output_dim"))
+            raise NotImplementedError(f"{name}: table {shared[0]!r} appears in both towers' groups: each tower owns its tables")
         so = sparse_optimizer if sparse_optimizer is not None else spec.sparse_optimizer
-        bs = spec.batch_size or 1024
-        t, g, feats = towers["user_tower"]
-        self.user_tower = DSSMTower(t, out_dim, similarity, g, feats, device, so, bs)
-        t, g, feats = towers["item_tower"]
-        self.item_tower = DSSMTower(t, out_dim, similarity, g, feats, device, so, bs,
-                                    data_group=NEG_DATA_GROUP if self._sampler is not None else BASE_DATA_GROUP)
-        if self.user_tower.embedding_dim() != self.item_tower.embedding_dim():
-            raise ValueError(f"dssm: the towers end {self.user_tower.embedding_dim()} and {self.item_tower.embedding_dim()} wide")
+        self._build_towers(towers, int(m.one("output_dim")), similarity, device, so, spec.batch_size or 1024,
+                           NEG_DATA_GROUP if self._sampler is not None else BASE_DATA_GROUP)
+
+    def _build_towers(self, towers, out_dim: int, similarity: str, device, sparse_optimizer, batch_size: int, item_data_group: str) -> None:
+        raise NotImplementedError
+
+    @property
+    def _head_cosine(self) -> bool:
+        """whether the similarity head normalizes the embeddings it is handed"""
+        return self._cosine
 
     # ---- what the pipelines and the example read
     def dense_parameters(self):
@@ -337,9 +426,9 @@ class ConfigDSSM(nn.Module):
         autograd, out of the fused forward under no_grad (evaluation)"""
         u, v = self._embeddings(batch)
         if not torch.is_grad_enabled():
-            _, rank, sim = match_softmax(u, v, self._mode, self._cosine, self._temperature, None, want_sim=True)
+            _, rank, sim = match_softmax(u, v, self._mode, self._head_cosine, self._temperature, None, want_sim=True)
             return {"similarity": sim, "rank": rank}
-        sim = match_scores(u, v, self._mode, self._cosine, self._temperature)
+        sim = match_scores(u, v, self._mode, self._head_cosine, self._temperature)
         return {"similarity": sim, "rank": scores_loss_rank(sim.detach(), self._mode)[1]}
 
     def loss(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
@@ -347,7 +436,7 @@ class ConfigDSSM(nn.Module):
 
     def head(self, u: torch.Tensor, v: torch.Tensor, weights: Optional[torch.Tensor] = None):
         """the towers' embeddings -> ({"softmax_cross_entropy": loss}, {"rank": rank[, "similarity": sim]}) on the fused head"""
-        loss, rank, sim = match_softmax(u, v, self._mode, self._cosine, self._temperature, weights, want_sim=self.want_similarity)
+        loss, rank, sim = match_softmax(u, v, self._mode, self._head_cosine, self._temperature, weights, want_sim=self.want_similarity)
         predictions = {"rank": rank}
         if sim is not None:
             predictions["similarity"] = sim
@@ -356,3 +445,203 @@ class ConfigDSSM(nn.Module):
     def loss_and_predictions(self, batch: Batch):
         u, v = self._embeddings(batch)
         return self.head(u, v, self._weights(batch))
+
+
+class ConfigDSSM(ConfigMatchModel):
+    """`dssm { user_tower {} item_tower {} output_dim similarity temperature in_batch_negative }` (tzrec/models/dssm.py:86-155,
+    match_model.py:246-336): two DSSMTowers, each with the EmbeddingGroup of its own feature group, and the similarity head.
+
+    With `data_config.negative_sampler` the item tower reads the batch's "__NEG__" data group: B + num_sample rows, row i the
+    positive of user row i, the rest negatives shared by the batch; with `in_batch_negative` it reads the base group's B rows and
+    every other row of the batch is a negative.  Without either the positive is the only column (loss 0), as in the reference.
+
+    `loss_and_predictions(batch)` -- what the train pipelines call -- runs the fused head: {"softmax_cross_entropy": loss} and
+    {"rank": rank} (plus "similarity" when `want_similarity` is set), no score matrix otherwise.  `forward(batch)` keeps the
+    literal contract, {"similarity": [B, C]} (plus "rank"), for `loss(predictions, batch)` and evaluation.
+
+    Refused when built, by name: every sampler but `negative_sampler`; `variational_dropout`; `train_metrics`; any loss but one
+    `softmax_cross_entropy`; any metric but `recall_at_k` (both the reference's own assertions, match_model.py:284-291, 345-348);
+    `in_batch_negative` with a sampler; a table that both towers' groups would share; a zero-collision-hash feature; sharded
+    towers (`process_group`); a field the `dssm` block or a tower block does not have."""
+
+    _NAME = "dssm"
+    _FIELDS = ("user_tower", "item_tower", "output_dim", "similarity", "temperature", "in_batch_negative")
+    _TOWER_FIELDS = {"user_tower": ("input", "mlp"), "item_tower": ("input", "mlp")}
+
+    def _build_towers(self, towers, out_dim, similarity, device, sparse_optimizer, batch_size, item_data_group) -> None:
+        t, gs, feats = towers["user_tower"]
+        self.user_tower = DSSMTower(t, out_dim, similarity, gs[0], feats, device, sparse_optimizer, batch_size)
+        t, gs, feats = towers["item_tower"]
+        self.item_tower = DSSMTower(t, out_dim, similarity, gs[0], feats, device, sparse_optimizer, batch_size, data_group=item_data_group)
+        if self.user_tower.embedding_dim() != self.item_tower.embedding_dim():
+            raise ValueError(f"dssm: the towers end {self.user_tower.embedding_dim()} and {self.item_tower.embedding_dim()} wide")
+
+
+_CAPSULE_FIELDS = ("max_k", "max_seq_len", "high_dim", "num_iters", "routing_logits_scale", "routing_logits_stddev", "squash_pow",
+                   "const_caps_num", "routing_init_method")
+
+
+def capsule_config_from_msg(msg) -> CapsuleConfig:
+    """a `capsule_config { }` block (protos/module.proto: B2ICapsule) with the reference's defaults"""
+    other = sorted(k for k in msg if k not in _CAPSULE_FIELDS)
+    if other:
+        raise ValueError(f"mind: capsule_config has no field {other[0]!r} (fields: {', '.join(_CAPSULE_FIELDS)})")
+    for k in ("max_seq_len", "high_dim"):
+        if not msg.has(k):
+            raise ValueError(f"mind: capsule_config needs `{k}`")
+    init = str(msg.one("routing_init_method", "normal"))
+    if init not in ("normal", "zeros"):
+        raise ValueError(f"mind: capsule_config.routing_init_method {init!r}: init_method should be 'normal' or 'zeros'")
+    return CapsuleConfig(max_k=int(msg.one("max_k", 5)), max_seq_len=int(msg.one("max_seq_len")), high_dim=int(msg.one("high_dim")),
+                         num_iters=int(msg.one("num_iters", 3)), routing_logits_scale=float(msg.one("routing_logits_scale", 20.0)),
+                         routing_logits_stddev=float(msg.one("routing_logits_stddev", 1.0)), squash_pow=float(msg.one("squash_pow", 1.0)),
+                         const_caps_num=bool(msg.one("const_caps_num", False)), routing_init_method=init)
+
+
+class MINDUserTower(MatchTower):
+    """MIND's user tower (tzrec/models/mind.py:30-194) with the reference's parameter names: `user_mlp` (all but the last of
+    user_mlp.hidden_units) and `user_mlp_out` over the user group; `_hist_seq_mlp` / `_hist_seq_mlp_out` (no bias) over the
+    history; `_capsule_layer`; `_concat_mlp` over [user feature | interest] per interest; `output` = Linear(., output_dim) without
+    bias.  -> (interests [B, max_k, D], capsule mask [B, max_k]), the interests normalized under COSINE.
+
+    The history group is read as ROWS (`<g>.sequence_jagged` / `<g>.sequence_offsets` of the embedding group) whenever its features
+    are the sub-features of one `sequence_feature` block with a `sequence_length`: `_hist_seq_mlp` runs on the [N, D] rows -- exact,
+    it has no bias and the capsule layer masks its input -- and the capsule layer on the rows (capsule.capsule_routing).  Any other
+    history group is read padded and its valid positions are gathered into rows (a device read-back: not capturable).
+    `_concat_mlp` runs on the [B max_k, .] rows.  `user_seq_combine` is accepted and has no effect, as in the reference, which
+    never reads it."""
+
+    def __init__(self, tower_config, output_dim: int, similarity: str, user_group, hist_group, features, device=None, sparse_optimizer=None,
+                 batch_size: int = 1024) -> None:
+        super().__init__(tower_config, output_dim, similarity, [user_group, hist_group], features, device, sparse_optimizer, batch_size)
+        self._hist_group_name = hist_group.group_name
+        eg = self.embedding_group
+        info = eg._seq_info[self._hist_group_name]
+        if info["max_len"] and len({f.name.split("__")[0] for f in info["sequence"]}) == 1 \
+                and not any(getattr(f, "value_dim", 1) not in (0, 1) for f in info["sequence"]):
+            eg.jagged_sequence_groups.add(self._hist_group_name)
+        self._build_dense(eg.group_total_dim(self._group_name), eg.group_total_dim(self._hist_group_name + ".sequence"), tower_config, device)
+
+    def _build_dense(self, d_user: int, d_hist: int, tower_config, device=None) -> None:
+        from .dlrm import MLP
+        from .rank_model import mlp_kwargs
+
+        user = mlp_kwargs(tower_config.one("user_mlp"))
+        if len(user["hidden_units"]) < 2:
+            raise ValueError("mind: user_tower.user_mlp needs at least two hidden_units (the reference itself fails with fewer, mind.py:83-85)")
+        first = lambda d: d[0] if d else None  # noqa: E731  (the reference hands the MLP dropout_ratio[0])
+        self.user_mlp = MLP(d_user, user["hidden_units"][:-1], activation=user["activation"], use_bn=user["use_bn"],
+                            dropout_ratio=first(user["dropout_ratio"]))
+        self.user_mlp_out = nn.Linear(self.user_mlp.output_dim(), user["hidden_units"][-1])
+        self._hist_seq_mlp = self._hist_seq_mlp_out = None
+        hist = mlp_kwargs(tower_config.one("hist_seq_mlp")) if tower_config.has("hist_seq_mlp") else None
+        for which, kw in (("hist_seq_mlp", hist), ("concat_mlp", mlp_kwargs(tower_config.one("concat_mlp")))):
+            if kw is not None and kw["use_bn"]:
+                raise NotImplementedError(f"mind: user_tower.{which} `use_bn` is not built (batch statistics over padded positions "
+                                          "cannot be restated on rows)")
+        if hist is not None and len(hist["hidden_units"]) > 1:
+            self._hist_seq_mlp = MLP(d_hist, hist["hidden_units"][:-1], bias=False, activation=hist["activation"], dropout_ratio=first(hist["dropout_ratio"]))
+            self._hist_seq_mlp_out = nn.Linear(self._hist_seq_mlp.output_dim(), hist["hidden_units"][-1], bias=False)
+            d_hist = hist["hidden_units"][-1]
+        elif hist is not None and len(hist["hidden_units"]) > 0:
+            self._hist_seq_mlp = nn.Linear(d_hist, hist["hidden_units"][-1], bias=False)
+            d_hist = hist["hidden_units"][-1]
+        cfg = capsule_config_from_msg(tower_config.one("capsule_config"))
+        self._capsule_layer = CapsuleLayer(cfg, d_hist)
+        self._concat_mlp = MLP(user["hidden_units"][-1] + cfg.high_dim, **mlp_kwargs(tower_config.one("concat_mlp")))
+        if self._output_dim > 0:
+            self.output = nn.Linear(self._concat_mlp.output_dim(), self._output_dim, bias=False)
+        if device is not None:
+            for name, mod in self.named_children():
+                if name != "embedding_group":
+                    mod.to(device)
+
+    def embedding_dim(self) -> int:
+        return self._output_dim if self._output_dim > 0 else self._concat_mlp.output_dim()
+
+    def history_rows(self, feats: Dict[str, torch.Tensor]):
+        """-> (rows [N, D], offsets [B + 1]) of the history group"""
+        g = self._hist_group_name
+        if g in self.embedding_group.jagged_sequence_groups:
+            return feats[f"{g}.sequence_jagged"], feats[f"{g}.sequence_offsets"]
+        seq, lens = feats[f"{g}.sequence"], feats[f"{g}.sequence_length"].clamp(max=feats[f"{g}.sequence"].shape[1])
+        keep = torch.arange(seq.shape[1], device=seq.device)[None, :] < lens[:, None]
+        return seq[keep], torch.cat([lens.new_zeros(1), lens.cumsum(0)])
+
+    def interests(self, user_x: torch.Tensor, rows: torch.Tensor, offsets: torch.Tensor, logits0: Optional[torch.Tensor] = None):
+        """the user group's features [B, .] and the history rows -> (interests [B, K, D], mask [B, K]) (mind.py:158-194); logits0
+        [N, K]: the capsule layer's initial routing logits instead of its own draw"""
+        user_feature = self.user_mlp_out(self.user_mlp(user_x))
+        if self._hist_seq_mlp is not None:
+            rows = self._hist_seq_mlp(rows)
+            if self._hist_seq_mlp_out is not None:
+                rows = self._hist_seq_mlp_out(rows)
+        high, mask = self._capsule_layer(rows, offsets, logits0)
+        B, K, _ = high.shape
+        maskf = mask.unsqueeze(-1).to(high.dtype)
+        x = torch.cat([user_feature.unsqueeze(1).expand(B, K, user_feature.shape[1]), high], dim=-1) * maskf
+        x = self._concat_mlp(x.reshape(B * K, -1)).reshape(B, K, -1) * maskf
+        if self._output_dim > 0:
+            x = self.output(x)
+        if self._similarity == "COSINE":
+            x = F.normalize(x, p=2.0, dim=-1)
+        return x, mask
+
+    def forward(self, batch: Batch):
+        feats = self.build_input(batch)
+        rows, offsets = self.history_rows(feats)
+        return self.interests(feats[self._group_name], rows, offsets)
+
+
+class MINDItemTower(DSSMTower):
+    """MIND's item tower (mind.py:197-252): DSSM's, plus its own normalisation under COSINE"""
+
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        out = super().embed(x)
+        return F.normalize(out, p=2.0, dim=1) if self._similarity == "COSINE" else out
+
+
+class ConfigMIND(ConfigMatchModel):
+    """`mind { user_tower {} item_tower {} simi_pow similarity in_batch_negative temperature output_dim }` (tzrec/models/mind.py,
+    match_model.py:246-336): a MINDUserTower over the groups `input` and `history_input`, a MINDItemTower, the label-aware
+    attention of the positive item over the user's interests (`label_attention`) and DSSM's similarity head.  The towers
+    normalize under COSINE (the default here), so the head runs without its own normalisation; the attended user embedding is
+    deliberately not re-normalized: the reference has that line commented out (mind.py:356-357).
+
+    Data groups, `loss_and_predictions`, `forward`, `loss`, `head`: as ConfigDSSM.  Refused when built, by name: everything
+    ConfigDSSM refuses (hard-negative samplers among it); `user_mlp` with fewer than two `hidden_units`; `use_bn` in `hist_seq_mlp`
+    or `concat_mlp`; a field the `mind` block, a tower or `capsule_config` does not have; a `routing_init_method` other than
+    normal / zeros; a `history_input` that is not a SEQUENCE group.  The inference form that returns the interests instead of one
+    user embedding (mind.py:191-192) is not built: no method of this class returns them."""
+
+    _NAME = "mind"
+    _FIELDS = ("user_tower", "item_tower", "simi_pow", "similarity", "in_batch_negative", "temperature", "output_dim")
+    _TOWER_FIELDS = {"user_tower": ("input", "history_input", "user_mlp", "hist_seq_mlp", "user_seq_combine", "capsule_config", "concat_mlp"),
+                     "item_tower": ("input", "mlp")}
+    _TOWER_GROUPS = {"user_tower": ("input", "history_input"), "item_tower": ("input",)}
+    _DEFAULT_SIMILARITY = "COSINE"
+
+    def _build_towers(self, towers, out_dim, similarity, device, sparse_optimizer, batch_size, item_data_group) -> None:
+        t, gs, feats = towers["user_tower"]
+        for k in ("user_mlp", "capsule_config", "concat_mlp"):
+            if not t.has(k):
+                raise ValueError(f"mind: user_tower needs `{k}`")
+        if gs[1].group_type != "SEQUENCE":
+            raise ValueError(f"mind: user_tower.history_input {gs[1].group_name!r} is a {gs[1].group_type} group: the history is a SEQUENCE group")
+        if gs[0].group_type == "SEQUENCE":
+            raise ValueError(f"mind: user_tower.input {gs[0].group_name!r} is a SEQUENCE group")
+        self._simi_pow = float(self._spec.model.one("simi_pow", 10.0))
+        self.user_tower = MINDUserTower(t, out_dim, similarity, gs[0], gs[1], feats, device, sparse_optimizer, batch_size)
+        t, gs, feats = towers["item_tower"]
+        self.item_tower = MINDItemTower(t, out_dim, similarity, gs[0], feats, device, sparse_optimizer, batch_size, data_group=item_data_group)
+        if self.user_tower.embedding_dim() != self.item_tower.embedding_dim():
+            raise ValueError(f"mind: the towers end {self.user_tower.embedding_dim()} and {self.item_tower.embedding_dim()} wide")
+
+    @property
+    def _head_cosine(self) -> bool:
+        return False  # (the towers have normalized)
+
+    def _embeddings(self, batch: Batch):
+        interests, mask = self.user_tower(batch)
+        v = self.item_tower(batch)
+        return label_attention(interests, v, mask, self._simi_pow), v
