@@ -841,6 +841,56 @@ int tzr_label_attn_bwd(const float* d_grad_out, int64_t grad_out_stride, const f
                        const float* d_w, const uint8_t* d_mask, int64_t B, int K, int D, float simi_pow, float* d_di, int64_t di_stride,
                        float* d_dv, int64_t dv_stride, void* stream);
 
+/* DAT's Adaptive-Mimic loss (tzrec/models/dat.py:212-259), the user side and the item side in one launch.  ua [B, D] / ia [M, D]:
+ * the towers' augment rows; ue [B, D] / ie [M, D]: the towers' embeddings BEFORE any normalisation, constants here (no gradient);
+ * M >= B, only the first B rows of ia / ie take part.  fp32, unit column stride, row strides that are multiples of 4 floats and no
+ * narrower than D, 16-byte aligned rows (column slices of wider buffers are fine); w [B] fp32 sample weights or 0.
+ *   Side u: a = ua[b], t = ie[b], c = c_u; side i: a = ia[b], t = ue[b], c = c_i.
+ *   n = max(|a|, 1e-12), y = a / n; tau = t / max(|t|, 1e-12) when `cosine`, else t; l_b = sum_d (y_d - tau_d)^2;
+ *   loss_s = c sum_b l_b (a sum, not a mean), with w: c sum_b(l_b w_b) / sum_b(w_b), exactly 0 when the weights add to 0.
+ * forward writes loss [2] (loss_u, loss_i), rows [6, B] contiguous (l_u, l_i, 1/n of side u, of side i -- NEGATED where |a| < 1e-12,
+ *   the backward's clamp branch --, 1/max(|t|, 1e-12) of side u, of side i: 1 without `cosine`) and scale [1] (1 / sum(w), 0 when that sum
+ *   is 0, 1 without w).  One wave per sample, four samples per workgroup, one partial row (sum l_u w, sum l_i w, sum w) per
+ *   workgroup in `ws` (tzr_amm_loss_workspace bytes); a finishing launch adds the rows in the interleaved order (csrc/parts_sum.h).
+ * backward reads the upstream gradients g_u, g_i from device memory (grad_u / grad_i, one float each; 0 = no gradient for that
+ *   side) and `rows`, `scale` as the forward left them: k_b = g c (with w: g c w_b scale); dy = 2 k_b (y - tau);
+ *   da = (dy - y <y, dy>) / n where |a| >= 1e-12, dy / 1e-12 below (torch's clamp_min branch); writes dua [B, D] and dia [M, D], rows
+ *   b >= B of dia as exact zeros.  One launch.  Nothing flows to ue / ie.
+ * No atomics, every sum's order a function of B alone: two runs are bit-equal.  TZR_ERR_UNSUPPORTED: D % 4 != 0, D < 4, D >
+ * TZR_AMM_MAX_D, M < B, B or M >= 2^31, `cosine` not 0 / 1, a row stride that is no multiple of 4 or below D.  TZR_ERR_INVALID: a
+ * null or misaligned pointer (rows 16 bytes, the others 4; w, grad_u, grad_i may be 0), B < 0.  TZR_ERR_WORKSPACE (forward): `ws`
+ * null, not 256-byte aligned or below the query less its 256 bytes of slack.  B == 0 is TZR_OK without a launch.  A refused call
+ * launches nothing.  A new struct and entry points, no change to existing ones: the ABI version stays 15. */
+#define TZR_AMM_MAX_D 256
+typedef struct TzrAmmLoss {
+  int64_t B, M;
+  int32_t D, cosine;
+  float c_u, c_i;      /* amm_u_weight, amm_i_weight */
+  uint64_t ua;         /* const float* [B, D] */
+  int64_t ua_stride;
+  uint64_t ia;         /* const float* [M, D] */
+  int64_t ia_stride;
+  uint64_t ue;         /* const float* [B, D] */
+  int64_t ue_stride;
+  uint64_t ie;         /* const float* [M, D] */
+  int64_t ie_stride;
+  uint64_t w;          /* const float* [B], nullable */
+  uint64_t loss;       /* float* [2]            (forward writes) */
+  uint64_t rows;       /* float* [6, B]         (forward writes, backward reads) */
+  uint64_t scale;      /* float* [1]            (forward writes, backward reads) */
+  uint64_t grad_u;     /* const float* [1], nullable (backward) */
+  uint64_t grad_i;     /* const float* [1], nullable (backward) */
+  uint64_t dua;        /* float* [B, D]         (backward) */
+  int64_t dua_stride;
+  uint64_t dia;        /* float* [M, D]         (backward) */
+  int64_t dia_stride;
+  uint64_t ws;         /* workspace             (forward) */
+  uint64_t ws_bytes;
+} TzrAmmLoss;
+size_t tzr_amm_loss_workspace(const TzrAmmLoss* h_amm);
+int tzr_amm_loss_fwd(const TzrAmmLoss* h_amm, void* stream);
+int tzr_amm_loss_bwd(const TzrAmmLoss* h_amm, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

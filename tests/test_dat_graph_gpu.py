@@ -1,0 +1,100 @@
+"""tests/golden/dat_mini.config and its in-batch variant (tests/dat_variants.py) through GraphTrainPipeline at B = 64, N = 12:
+three eager steps followed by four steps captured into / replayed from hipGraphs leave bit for bit what seven eager steps of an
+identically seeded twin leave -- the Adaptive-Mimic launches capture (the argument struct is read when the launch is recorded, the
+two upstream gradients from device memory; outputs, saved rows and the workspace are torch's buffers), the id lookups that feed a
+group and an augment group take both gradients in the fused sparse backward, and every sum has a fixed order.  And the
+evaluation of the config's recall@k, eager and replayed from a graph."""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+
+LOSS_KEYS = ["amm_loss_i", "amm_loss_u", "softmax_cross_entropy"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["sampled", "in_batch"])
+def test_dat_replays_from_a_graph(variant):
+    import dat_variants as dv
+    from torcheasyrec_amd import _lib, match
+    from torcheasyrec_amd.config import load_pipeline_spec
+    from torcheasyrec_amd.dense import FusedDenseAdam
+    from torcheasyrec_amd.embedding_group import GraphTrainPipeline
+    from torcheasyrec_amd.match import ConfigDAT
+    from torcheasyrec_amd.rank_model import build_rank_model
+
+    _lib.use_native()
+    dev = torch.device("cuda", 0)
+    spec = load_pipeline_spec(dv.variant(variant))
+    B, n_steps = 64, 7
+    host = [b.pin_memory() for b in dv.batches(spec, B, n_steps, seed=9)]
+    L = _lib.lib()
+    orig, n_calls = L.tzr_amm_loss_fwd, [0]
+
+    def counted(*a):
+        n_calls[0] += 1
+        return orig(*a)
+
+    res = []
+    work = torch.cuda.Stream(dev)
+    L.tzr_amm_loss_fwd = counted
+    try:
+        with torch.cuda.stream(work):
+            for graphs in (False, True):
+                torch.manual_seed(3)
+                model = build_rank_model(spec, device=dev)
+                assert type(model) is ConfigDAT
+                opt = FusedDenseAdam(list(model.dense_parameters()), lr=spec.dense_lr)
+                pipe = GraphTrainPipeline(model, opt, dev, model.loss, warmup=10 ** 9)  # (the twin never captures)
+                it, losses = iter(host), []
+                for step in range(n_steps):
+                    if graphs and step == 3:
+                        pipe._warmup = 0  # three eager steps lie behind: steps 3 and 4 capture their slot and replay, 5 and 6 replay
+                    l, p, _ = pipe.progress(it)
+                    assert sorted(l) == LOSS_KEYS and sorted(p) == ["rank"]
+                    losses.append(torch.stack([l[k].detach() for k in LOSS_KEYS]).clone())
+                torch.cuda.synchronize()
+                assert (pipe._graphs[0] is not None and pipe._graphs[1] is not None) == graphs  # captured without raising
+                res.append((torch.stack(losses).cpu(),
+                            {f"{t}/{n}": w.detach().cpu().clone() for t in ("user_tower", "item_tower")
+                             for n, w in getattr(model, t).embedding_group.ebc.table_weights().items()},
+                            {n: p.detach().cpu().clone() for n, p in model.named_parameters() if ".embedding_group." not in n}))
+    finally:
+        L.tzr_amm_loss_fwd = orig
+    # the fused loss is what ran: one forward call per eager or captured step (7 eager steps, then 3 eager + 2 captured; replays
+    # call nothing)
+    assert match.FUSED_AMM_LOSS and n_calls[0] == 12
+    (la, ta, pa), (lb, tb, pb) = res
+    print("losses eager", la.tolist(), "eager then replayed", lb.tolist())
+    assert bool(torch.isfinite(la).all()) and torch.equal(la, lb) and not torch.equal(la[0], la[-1]) and bool((la[:, :2] > 0).all())
+    assert len(ta) == 4 and len(pa) == 12
+    for n in ta:
+        assert torch.equal(ta[n], tb[n]), n
+    for n in pa:
+        assert torch.equal(pa[n], pb[n]), n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["sampled", "in_batch"])
+def test_dat_evaluates_recall_eager_and_from_a_graph(variant):
+    import dat_variants as dv
+    from torcheasyrec_amd import _lib
+    from torcheasyrec_amd.config import load_pipeline_spec
+    from torcheasyrec_amd.metrics import Evaluator, evaluate
+    from torcheasyrec_amd.rank_model import build_rank_model
+
+    _lib.use_native()
+    dev = torch.device("cuda", 0)
+    spec = load_pipeline_spec(dv.variant(variant))
+    torch.manual_seed(4)
+    model = build_rank_model(spec, device=dev)
+    out = {}
+    for graph in (False, True):
+        host = [b.pin_memory() for b in dv.batches(spec, 64, 4, seed=10)]
+        out[graph] = {k: float(v) for k, v in evaluate(model, host, Evaluator(model, spec, dev), graph=graph).items()}
+        assert sorted(out[graph]) == ["recall@1", "recall@5"]
+        assert 0.0 <= out[graph]["recall@1"] <= out[graph]["recall@5"] <= 1.0
+    assert out[False] == out[True]  # (the same batches, the same counts)

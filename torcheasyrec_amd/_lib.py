@@ -168,6 +168,21 @@ class TzrCapsule(C.Structure):
 
 assert C.sizeof(TzrCapsule) == 192
 LABEL_ATTN_MAX_D, LABEL_ATTN_MAX_K = 256, 8  # TZR_LABEL_ATTN_MAX_*
+AMM_MAX_D = 256  # TZR_AMM_MAX_D
+
+
+class TzrAmmLoss(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("M", C.c_int64), ("D", C.c_int32), ("cosine", C.c_int32), ("c_u", C.c_float), ("c_i", C.c_float),
+        ("ua", C.c_uint64), ("ua_stride", C.c_int64), ("ia", C.c_uint64), ("ia_stride", C.c_int64),
+        ("ue", C.c_uint64), ("ue_stride", C.c_int64), ("ie", C.c_uint64), ("ie_stride", C.c_int64), ("w", C.c_uint64),
+        ("loss", C.c_uint64), ("rows", C.c_uint64), ("scale", C.c_uint64), ("grad_u", C.c_uint64), ("grad_i", C.c_uint64),
+        ("dua", C.c_uint64), ("dua_stride", C.c_int64), ("dia", C.c_uint64), ("dia_stride", C.c_int64),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrAmmLoss) == 192
 
 
 class TzrSparseOptim(C.Structure):
@@ -407,6 +422,9 @@ _SIGNATURES = {
     "tzr_capsule_bwd": (_i32, [_vp, _vp]),
     "tzr_label_attn_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, C.c_float, _vp, _i64, _vp, _vp]),
     "tzr_label_attn_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp, _i64, _vp, _i64, _vp]),
+    "tzr_amm_loss_workspace": (_sz, [_vp]),
+    "tzr_amm_loss_fwd": (_i32, [_vp, _vp]),
+    "tzr_amm_loss_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

@@ -1,11 +1,13 @@
-"""The match (retrieval) models: the fused similarity head, MIND's label-aware attention, and DSSM and MIND built from their configs.
+"""The match (retrieval) models: the fused similarity head, MIND's label-aware attention, DAT's Adaptive-Mimic loss, and DSSM, MIND and
+DAT built from their configs.
 
 `match_softmax` is the head of tzrec/models/match_model.py:50-64, 303-336 and dssm.py:81-83, 147-155 -- normalize,
 similarity, temperature, softmax cross entropy -- plus the rank of the positive that recall@k needs, in one autograd Function over
 tzr_match_softmax_fwd / _bwd (csrc/match_softmax.hip): the [B, 1 + N] (or [B, B]) score matrix is never in memory unless the
 caller asks for it.  `FUSED_MATCH_SOFTMAX = False`, or a shape outside `match_softmax_ok`, runs the reference's literal form.
 `label_attention` (tzrec/models/mind.py:303-333, tzr_label_attn_fwd / _bwd, csrc/label_attention.hip) is switched the same way by
-`FUSED_LABEL_ATTENTION` and `label_attention_ok`; MIND's capsule layer is capsule.py's.
+`FUSED_LABEL_ATTENTION` and `label_attention_ok`; MIND's capsule layer is capsule.py's.  `amm_loss` (tzrec/models/dat.py:212-259,
+tzr_amm_loss_fwd / _bwd, csrc/amm_loss.hip) likewise by `FUSED_AMM_LOSS` and `amm_loss_ok`.
 """
 from __future__ import annotations
 
@@ -253,6 +255,129 @@ def label_attention(interests: torch.Tensor, item: torch.Tensor, mask: torch.Ten
     return (out, w) if want_weights else out
 
 
+FUSED_AMM_LOSS = True  # profiles/amm_loss: the fused form against the literal one, without and with sample weights
+
+
+def _div_no_nan(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    return torch.where(den != 0, num / torch.where(den != 0, den, torch.ones_like(den)), torch.zeros_like(num))
+
+
+def amm_terms(user_augment: torch.Tensor, item_augment: torch.Tensor, user_tower_emb: torch.Tensor, item_tower_emb: torch.Tensor,
+              c_u: float, c_i: float, weights: Optional[torch.Tensor] = None):
+    """tzrec/models/dat.py:225-255, word for word, on the embeddings as the reference's towers deliver them (detached, normalized
+    under COSINE) -> (amm_loss_u, amm_loss_i)"""
+    batch_size = user_augment.size(0)
+    dim = 1 if weights is not None else (0, 1)
+    amm_loss_u = c_u * torch.sum(torch.square(F.normalize(user_augment, p=2.0, dim=1) - item_tower_emb[:batch_size]), dim=dim)
+    amm_loss_i = c_i * torch.sum(torch.square(F.normalize(item_augment[:batch_size], p=2.0, dim=1) - user_tower_emb), dim=dim)
+    if weights is not None:
+        amm_loss_u = _div_no_nan(torch.mean(amm_loss_u * weights), torch.mean(weights))
+        amm_loss_i = _div_no_nan(torch.mean(amm_loss_i * weights), torch.mean(weights))
+    return amm_loss_u, amm_loss_i
+
+
+def amm_loss_literal(user_aug, item_aug, user_emb, item_emb, cosine: bool, c_u: float, c_i: float, weights=None):
+    """the towers' raw embeddings detached and, under COSINE, normalized as the reference's towers do before they return
+    (dat.py:100-101, 206-207); then `amm_terms`"""
+    user_emb, item_emb = user_emb.detach(), item_emb.detach()
+    if cosine:
+        user_emb, item_emb = F.normalize(user_emb, p=2.0, dim=1), F.normalize(item_emb, p=2.0, dim=1)
+    return amm_terms(user_aug, item_aug, user_emb, item_emb, c_u, c_i, weights)
+
+
+def amm_loss_ok(user_aug: torch.Tensor, item_aug: torch.Tensor, user_emb: torch.Tensor, item_emb: torch.Tensor,
+                weights: Optional[torch.Tensor] = None) -> bool:
+    """what tzr_amm_loss_* takes: fp32 user_aug / user_emb [B, D] and item_aug / item_emb [M >= B, D] with unit column stride, row
+    strides that are multiples of 4 floats and 16-byte aligned rows (column slices of wider buffers are fine); D % 4 == 0, 4 <= D
+    <= 256; B >= 1; weights fp32 [B] contiguous; everything on the device of the loaded library"""
+    if any(t.dim() != 2 for t in (user_aug, item_aug, user_emb, item_emb)):
+        return False
+    B, D = user_aug.shape
+    M = item_aug.shape[0]
+    dev = user_aug.device
+    if (dev.type == "cpu") != (_lib.backend() == "emu") or any(t.device != dev for t in (item_aug, user_emb, item_emb)):
+        return False
+    if not (D % 4 == 0 and 4 <= D <= _lib.AMM_MAX_D and B >= 1 and M >= B and user_emb.shape[0] == B and item_emb.shape[0] == M):
+        return False
+    if not all(_rows_ok(t, D) for t in (user_aug, item_aug, user_emb, item_emb)):
+        return False
+    if weights is not None and not (weights.shape == (B,) and weights.dtype == torch.float32 and weights.is_contiguous()
+                                    and weights.device == dev):
+        return False
+    return True
+
+
+class _AmmLossFn(torch.autograd.Function):
+    """Inputs: user_aug [B, D], item_aug [M, D] (the gradients go here), user_emb [B, D], item_emb [M, D], weights [B] or None
+    (constants).  Outputs: loss_u, loss_i (scalars).  Saved for the backward: the inputs and 6 B + 1 floats.  Capturable: the
+    upstream gradients are read from device memory, every buffer is torch's.  Asked for a double backward, the backward
+    differentiates the literal form instead."""
+
+    @staticmethod
+    def _fill(m, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i, rows, scale):
+        m.B, m.M, m.D, m.cosine, m.c_u, m.c_i = user_aug.shape[0], item_aug.shape[0], user_aug.shape[1], int(cosine), c_u, c_i
+        m.ua, m.ua_stride, m.ia, m.ia_stride = _lib.ptr(user_aug), user_aug.stride(0), _lib.ptr(item_aug), item_aug.stride(0)
+        m.ue, m.ue_stride, m.ie, m.ie_stride = _lib.ptr(user_emb), user_emb.stride(0), _lib.ptr(item_emb), item_emb.stride(0)
+        m.w = _lib.ptr(weights) if weights is not None else 0
+        m.rows, m.scale = _lib.ptr(rows), _lib.ptr(scale)
+
+    @staticmethod
+    def forward(ctx, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i):
+        B, dev = user_aug.shape[0], user_aug.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        loss, rows, scale = torch.empty(2, **f32), torch.empty(6, B, **f32), torch.empty(1, **f32)
+        m = _lib.TzrAmmLoss()
+        _AmmLossFn._fill(m, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i, rows, scale)
+        m.loss = _lib.ptr(loss)
+        L = _lib.lib()
+        ws = _lib.workspace(L.tzr_amm_loss_workspace(C.byref(m)), dev)
+        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
+        _lib.check(L.tzr_amm_loss_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_amm_loss_fwd")
+        ctx.save_for_backward(user_aug, item_aug, user_emb, item_emb, weights, rows, scale)
+        ctx.cfg = (cosine, c_u, c_i)
+        ctx.set_materialize_grads(False)  # (no zero-filled gradient for a side nobody reads: a launch)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_u, g_i):
+        user_aug, item_aug, user_emb, item_emb, weights, rows, scale = ctx.saved_tensors
+        cosine, c_u, c_i = ctx.cfg
+        none = (None,) * 6
+        if g_u is None and g_i is None:
+            return (None, None) + none
+        if torch.is_grad_enabled():  # (create_graph: a double backward is coming)
+            lu, li = amm_loss_literal(user_aug, item_aug, user_emb, item_emb, cosine, c_u, c_i, weights)
+            total = sum(l * g for l, g in ((lu, g_u), (li, g_i)) if g is not None)
+            wanted = [t for t, need in zip((user_aug, item_aug), ctx.needs_input_grad) if need]
+            grads = iter(torch.autograd.grad(total, wanted, create_graph=True))
+            return tuple(next(grads) if need else None for need in ctx.needs_input_grad[:2]) + none
+        dev = user_aug.device
+        g_u, g_i = (None if g is None else g.to(torch.float32) for g in (g_u, g_i))
+        dua = torch.empty(user_aug.shape, dtype=torch.float32, device=dev)
+        dia = torch.empty(item_aug.shape, dtype=torch.float32, device=dev)
+        m = _lib.TzrAmmLoss()
+        _AmmLossFn._fill(m, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i, rows, scale)
+        m.grad_u, m.grad_i = (_lib.ptr(g_u) if g_u is not None else 0), (_lib.ptr(g_i) if g_i is not None else 0)
+        m.dua, m.dua_stride, m.dia, m.dia_stride = _lib.ptr(dua), dua.stride(0), _lib.ptr(dia), dia.stride(0)
+        _lib.check(_lib.lib().tzr_amm_loss_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_amm_loss_bwd")
+        return (dua, dia) + none
+
+
+def amm_loss(user_aug: torch.Tensor, item_aug: torch.Tensor, user_emb: torch.Tensor, item_emb: torch.Tensor, cosine: bool,
+             c_u: float, c_i: float, weights: Optional[torch.Tensor] = None):
+    """DAT's Adaptive-Mimic loss -> (loss_u, loss_i).  user_aug [B, D] / item_aug [M >= B, D]: the towers' augment rows; user_emb
+    [B, D] / item_emb [M, D]: the towers' embeddings before any normalisation, treated as detached.  loss_u = c_u sum_b |normalize(
+    user_aug_b) - tau(item_emb_b)|^2 and loss_i likewise with the sides swapped, tau = normalize under `cosine`; with `weights` [B]:
+    c mean(l w) / mean(w), 0 where mean(w) is 0.  Gradients go to the two augment tensors only.  One launch and a finishing one
+    forward, one backward, unless FUSED_AMM_LOSS is off or `amm_loss_ok` refuses the operands: then the literal form runs."""
+    if weights is not None:
+        weights = weights.detach()
+    user_emb, item_emb = user_emb.detach(), item_emb.detach()
+    if FUSED_AMM_LOSS and amm_loss_ok(user_aug, item_aug, user_emb, item_emb, weights):
+        return _AmmLossFn.apply(user_aug, item_aug, user_emb, item_emb, weights, bool(cosine), float(c_u), float(c_i))
+    return amm_loss_literal(user_aug, item_aug, user_emb, item_emb, bool(cosine), float(c_u), float(c_i), weights)
+
+
 NEG_DATA_GROUP = "__NEG__"  # tzrec/datasets/utils.py:29: the item-side features the negative sampler delivers, B + N rows
 
 
@@ -475,6 +600,105 @@ class ConfigDSSM(ConfigMatchModel):
         self.item_tower = DSSMTower(t, out_dim, similarity, gs[0], feats, device, sparse_optimizer, batch_size, data_group=item_data_group)
         if self.user_tower.embedding_dim() != self.item_tower.embedding_dim():
             raise ValueError(f"dssm: the towers end {self.user_tower.embedding_dim()} and {self.item_tower.embedding_dim()} wide")
+
+
+class DATTower(DSSMTower):
+    """DAT user / item tower (tzrec/models/dat.py:39-106): one EmbeddingGroup over the `input` group and the `augment_input`
+    group; `mlp` over cat([input group, augment group], 1), then `output`.  -> (embedding, augment rows): the embedding BEFORE the
+    COSINE normalisation, as DSSMTower's, the augment group's rows as the embedding group delivers them."""
+
+    def __init__(self, tower_config, output_dim: int, similarity: str, feature_groups, features, device=None, sparse_optimizer=None,
+                 batch_size: int = 1024, data_group: str = BASE_DATA_GROUP) -> None:
+        MatchTower.__init__(self, tower_config, output_dim, similarity, list(feature_groups), features, device, sparse_optimizer,
+                            batch_size, data_group)
+        self._augment_group_name = str(tower_config.one("augment_input"))
+        eg = self.embedding_group
+        self._build_dense(eg.group_total_dim(self._group_name) + eg.group_total_dim(self._augment_group_name), tower_config, device)
+
+    def augment_dim(self) -> int:
+        return self.embedding_group.group_total_dim(self._augment_group_name)
+
+    def forward(self, batch: Batch):
+        feats = self.build_input(batch)
+        augment = feats[self._augment_group_name]
+        return self.embed(torch.cat([feats[self._group_name], augment], dim=1)), augment
+
+
+class ConfigDAT(ConfigMatchModel):
+    """`dat { user_tower {} item_tower {} output_dim similarity temperature in_batch_negative amm_i_weight amm_u_weight }`
+    (tzrec/models/dat.py, protos/models/match_model.proto: DAT, protos/tower.proto: DATTower): two DATTowers, each reading a second
+    "augment" feature group next to its own, DSSM's similarity head, and in training the Adaptive-Mimic loss that pulls each
+    tower's normalized augment rows towards the other tower's detached embedding of the same sample (`amm_loss`).  A feature may
+    sit in a tower's group and in its augment group (the docs' user_id / item_id): one lookup, copied into both, gradient from both.
+
+    `loss_and_predictions(batch)`: {"softmax_cross_entropy"} from the fused head plus, in training mode, {"amm_loss_u",
+    "amm_loss_i"}; under `eval()` the first alone, as the reference's towers return no augment vector then.  `forward(batch)`
+    keeps the literal contract: under autograd in training mode "similarity", "rank", "user_augment", "item_augment" and the
+    detached "user_tower_emb" / "item_tower_emb" (normalized under COSINE), from which `loss(predictions, batch)` computes the
+    literal terms; under no_grad or `eval()` "similarity" and "rank" alone.  With a negative sampler the item tower reads
+    "__NEG__" (B + N rows) and the AMM terms use its first B rows.
+
+    Refused when built, by name: everything ConfigDSSM refuses; a missing `amm_i_weight` / `amm_u_weight` (`required` in the
+    proto); a tower without `augment_input`; an augment group that is not a DEEP group of the config; an augment group whose total
+    dim differs from the towers' embedding dim (the reference would fail at the subtraction, or silently broadcast a 1-wide
+    group); towers ending in different widths."""
+
+    _NAME = "dat"
+    _FIELDS = ("user_tower", "item_tower", "output_dim", "similarity", "temperature", "in_batch_negative", "amm_i_weight", "amm_u_weight")
+    _TOWER_FIELDS = {"user_tower": ("input", "augment_input", "mlp"), "item_tower": ("input", "augment_input", "mlp")}
+    _TOWER_GROUPS = {"user_tower": ("input", "augment_input"), "item_tower": ("input", "augment_input")}
+
+    def _build_towers(self, towers, out_dim, similarity, device, sparse_optimizer, batch_size, item_data_group) -> None:
+        m = self._spec.model
+        for k in ("amm_i_weight", "amm_u_weight"):
+            if not m.has(k):
+                raise ValueError(f"dat: needs `{k}` (required in the proto)")
+        self._amm_u, self._amm_i = float(m.one("amm_u_weight")), float(m.one("amm_i_weight"))
+        for which in ("user_tower", "item_tower"):
+            for field, g in zip(self._TOWER_GROUPS[which], towers[which][1]):
+                if g.group_type != "DEEP":
+                    raise ValueError(f"dat: {which}.{field} {g.group_name!r} is a {g.group_type} group: the towers read DEEP groups")
+        t, gs, feats = towers["user_tower"]
+        self.user_tower = DATTower(t, out_dim, similarity, gs, feats, device, sparse_optimizer, batch_size)
+        t, gs, feats = towers["item_tower"]
+        self.item_tower = DATTower(t, out_dim, similarity, gs, feats, device, sparse_optimizer, batch_size, data_group=item_data_group)
+        if self.user_tower.embedding_dim() != self.item_tower.embedding_dim():
+            raise ValueError(f"dat: the towers end {self.user_tower.embedding_dim()} and {self.item_tower.embedding_dim()} wide")
+        for which, tower in (("user_tower", self.user_tower), ("item_tower", self.item_tower)):
+            if tower.augment_dim() != tower.embedding_dim():
+                raise ValueError(f"dat: {which}.augment_input {tower._augment_group_name!r} is {tower.augment_dim()} wide, the towers' "
+                                 f"embedding {tower.embedding_dim()}: the Adaptive-Mimic loss subtracts one from the other")
+
+    def _embeddings(self, batch: Batch):
+        return self.user_tower(batch)[0], self.item_tower(batch)[0]
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        if not (self.training and torch.is_grad_enabled()):
+            return super().forward(batch)
+        (u, user_augment), (v, item_augment) = self.user_tower(batch), self.item_tower(batch)
+        sim = match_scores(u, v, self._mode, self._head_cosine, self._temperature)
+        ue, ve = u.detach(), v.detach()
+        if self._cosine:
+            ue, ve = F.normalize(ue, p=2.0, dim=1), F.normalize(ve, p=2.0, dim=1)
+        return {"similarity": sim, "rank": scores_loss_rank(sim.detach(), self._mode)[1], "user_augment": user_augment,
+                "item_augment": item_augment, "user_tower_emb": ue, "item_tower_emb": ve}
+
+    def loss(self, predictions: Dict[str, torch.Tensor], batch: Batch) -> Dict[str, torch.Tensor]:
+        losses = super().loss(predictions, batch)
+        if "user_augment" in predictions:
+            losses["amm_loss_u"], losses["amm_loss_i"] = amm_terms(predictions["user_augment"], predictions["item_augment"],
+                                                                   predictions["user_tower_emb"], predictions["item_tower_emb"],
+                                                                   self._amm_u, self._amm_i, self._weights(batch))
+        return losses
+
+    def loss_and_predictions(self, batch: Batch):
+        if not self.training:
+            return super().loss_and_predictions(batch)
+        (u, user_augment), (v, item_augment) = self.user_tower(batch), self.item_tower(batch)
+        weights = self._weights(batch)
+        losses, predictions = self.head(u, v, weights)
+        losses["amm_loss_u"], losses["amm_loss_i"] = amm_loss(user_augment, item_augment, u, v, self._cosine, self._amm_u, self._amm_i, weights)
+        return losses, predictions
 
 
 _CAPSULE_FIELDS = ("max_k", "max_seq_len", "high_dim", "num_iters", "routing_logits_scale", "routing_logits_stddev", "squash_pow",

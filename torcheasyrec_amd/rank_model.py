@@ -883,10 +883,11 @@ _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": Config
            "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
 
 
-from .match import ConfigDSSM, ConfigMIND  # noqa: E402  (the match models; match.py reads this module's helpers when a tower is built)
+from .match import ConfigDAT, ConfigDSSM, ConfigMIND  # noqa: E402  (the match models; match.py reads this module's helpers when a tower is built)
 
 _MODELS["dssm"] = ConfigDSSM
 _MODELS["mind"] = ConfigMIND
+_MODELS["dat"] = ConfigDAT
 
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
