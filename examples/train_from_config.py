@@ -17,6 +17,7 @@ held-out batches (state on the device, torcheasyrec_amd/metrics.py).
     python examples/train_from_config.py tests/golden/dssm_mini.config         (dssm: a match model; sampled softmax without its score matrix, recall@k)
     python examples/train_from_config.py tests/golden/mind_mini.config         (mind: a click history routed into interests in one launch, label-aware attention)
     python examples/train_from_config.py tests/golden/dat_mini.config          (dat: augment groups beside the towers' own, the Adaptive-Mimic loss of both sides in one launch)
+    python examples/train_from_config.py tests/golden/rocket_mini.config       (rocket_launching: a booster and a light net, every distillation term of a step in one launch; auc_light)
 
 What a tzrec user keeps: the pipeline config, feature / group / model semantics, `pipeline.progress`.
 What changes underneath: the embedding path runs on libtzrec_hip.so."""

@@ -891,6 +891,60 @@ size_t tzr_amm_loss_workspace(const TzrAmmLoss* h_amm);
 int tzr_amm_loss_fwd(const TzrAmmLoss* h_amm, void* stream);
 int tzr_amm_loss_bwd(const TzrAmmLoss* h_amm, void* stream);
 
+/* Rocket Launching's distillation terms (tzrec/models/rocket_launching.py:125-204): the similarity term of every pair of equally
+ * wide hidden layers and the hint loss on the logits, in one launch.  P <= TZR_DISTILL_MAX_PAIRS pairs; pair p is light[p] and
+ * booster[p], both [B, W[p]] fp32 with unit column stride, their own row strides (multiples of 4 floats, no narrower than W[p]) and
+ * 16-byte aligned rows (column slices of wider buffers are fine); W[p] % 4 == 0, 4 <= W[p] <= TZR_DISTILL_MAX_W, the widths of one
+ * call may differ.  logits_light / logits_booster [B, C] contiguous fp32, 1 <= C <= 64; w [B] fp32 sample weights or 0.  Every
+ * booster operand is a constant: no gradient.
+ *   lw_b = w_b / mean(w), 0 when mean(w) is 0 (div_no_nan); 1 without w.
+ *   cosine:   sim_p = -0.1 mean_b(lw_b <l / max(|l|, 1e-12), t / max(|t|, 1e-12)>), l = light[p][b], t = booster[p][b];
+ *   distance: sim_p = sqrt(sum_b lw_b |t - l|^2) (the root of a sum, not a mean);
+ *   hint = sum_b lw_b sum_c (logits_light[b, c] - logits_booster[b, c])^2 / (B C).
+ * forward writes loss [P + 1] (sim_0 .. sim_{P-1}, hint) and scale [1 + TZR_DISTILL_MAX_PAIRS] (scale[0] = B / sum(w), 0 when
+ *   that sum is 0, 1 without w; scale[1 + p] = 1 / sim_p under distance, 0 where sim_p is 0 and under cosine).  One wave per
+ *   sample walks the pairs, four samples per workgroup, one partial row of P + 2 sums per workgroup in `ws`
+ *   (tzr_distill_loss_workspace bytes); a finishing launch adds the rows in the interleaved order (csrc/parts_sum.h).  Nothing is
+ *   saved per sample: the backward recomputes the norms from the rows it reads anyway.
+ * backward reads the upstream gradients from device memory (grad_sim[p], grad_hint: one float each; 0 = nobody asked for that
+ *   term) and `scale` as the forward left it, and writes dlight[p] [B, W[p]] (0 = skip the pair; with grad_sim[p] == 0 the rows are
+ *   written as zeros) and dlogits_light [B, C] contiguous (0 = skip; with grad_hint == 0 zeros).  cosine: dy = k t / max(|t|, 1e-12),
+ *   k = g_p (-0.1 / B) lw_b; dl = (dy - y <y, dy>) / |l| where |l| >= 1e-12, dy / 1e-12 below (torch's clamp_min branch).
+ *   distance: dl = g_p lw_b (l - t) / sim_p, and ZERO rows where sim_p is exactly 0 (the literal form gives NaN there: 0 * inf).
+ *   hint: g_h lw_b 2 (ll - lb) / (B C).  One launch.
+ * No atomics, every sum's order a function of the shapes alone: two runs are bit-equal.  TZR_ERR_UNSUPPORTED: P outside 0 ..
+ * TZR_DISTILL_MAX_PAIRS, C outside 1 .. 64, B >= 2^31, `cosine` not 0 / 1, a W[p] that is no multiple of 4, below 4 or above
+ * TZR_DISTILL_MAX_W, a row stride that is no multiple of 4 or below W[p].  TZR_ERR_INVALID: a null or misaligned pointer (rows 16
+ * bytes, the others 4; w, grad_*, dlight[p], dlogits_light may be 0), B < 0.  TZR_ERR_WORKSPACE (forward): `ws` null, not 256-byte
+ * aligned or below the query less its 256 bytes of slack.  Limits are checked first, then pointers.  B == 0 is TZR_OK without a
+ * launch.  A refused call launches nothing.  A new struct and entry points, no change to existing ones: the ABI version stays 15. */
+#define TZR_DISTILL_MAX_PAIRS 8
+#define TZR_DISTILL_MAX_W 1024
+typedef struct TzrDistillLoss {
+  int64_t B;
+  int32_t P, C, cosine, pad_;
+  int32_t W[TZR_DISTILL_MAX_PAIRS];
+  uint64_t light[TZR_DISTILL_MAX_PAIRS];          /* const float* [B, W[p]] */
+  int64_t light_stride[TZR_DISTILL_MAX_PAIRS];
+  uint64_t booster[TZR_DISTILL_MAX_PAIRS];        /* const float* [B, W[p]] */
+  int64_t booster_stride[TZR_DISTILL_MAX_PAIRS];
+  uint64_t logits_light;                          /* const float* [B, C] */
+  uint64_t logits_booster;                        /* const float* [B, C] */
+  uint64_t w;                                     /* const float* [B], nullable */
+  uint64_t loss;                                  /* float* [P + 1]                          (forward writes) */
+  uint64_t scale;                                 /* float* [1 + TZR_DISTILL_MAX_PAIRS]      (forward writes, backward reads) */
+  uint64_t grad_sim[TZR_DISTILL_MAX_PAIRS];       /* const float* [1] each, nullable         (backward) */
+  uint64_t grad_hint;                             /* const float* [1], nullable              (backward) */
+  uint64_t dlight[TZR_DISTILL_MAX_PAIRS];         /* float* [B, W[p]], nullable              (backward) */
+  int64_t dlight_stride[TZR_DISTILL_MAX_PAIRS];
+  uint64_t dlogits_light;                         /* float* [B, C], nullable                 (backward) */
+  uint64_t ws;                                    /* workspace                               (forward) */
+  uint64_t ws_bytes;
+} TzrDistillLoss;
+size_t tzr_distill_loss_workspace(const TzrDistillLoss* h_dst);
+int tzr_distill_loss_fwd(const TzrDistillLoss* h_dst, void* stream);
+int tzr_distill_loss_bwd(const TzrDistillLoss* h_dst, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

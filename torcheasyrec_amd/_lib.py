@@ -183,6 +183,23 @@ class TzrAmmLoss(C.Structure):
 
 
 assert C.sizeof(TzrAmmLoss) == 192
+DISTILL_MAX_PAIRS, DISTILL_MAX_W, DISTILL_MAX_C = 8, 1024, 64  # TZR_DISTILL_MAX_*; C: the logits' width
+
+
+class TzrDistillLoss(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("P", C.c_int32), ("C", C.c_int32), ("cosine", C.c_int32), ("pad_", C.c_int32),
+        ("W", C.c_int32 * DISTILL_MAX_PAIRS),
+        ("light", C.c_uint64 * DISTILL_MAX_PAIRS), ("light_stride", C.c_int64 * DISTILL_MAX_PAIRS),
+        ("booster", C.c_uint64 * DISTILL_MAX_PAIRS), ("booster_stride", C.c_int64 * DISTILL_MAX_PAIRS),
+        ("logits_light", C.c_uint64), ("logits_booster", C.c_uint64), ("w", C.c_uint64), ("loss", C.c_uint64), ("scale", C.c_uint64),
+        ("grad_sim", C.c_uint64 * DISTILL_MAX_PAIRS), ("grad_hint", C.c_uint64),
+        ("dlight", C.c_uint64 * DISTILL_MAX_PAIRS), ("dlight_stride", C.c_int64 * DISTILL_MAX_PAIRS), ("dlogits_light", C.c_uint64),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrDistillLoss) == 576
 
 
 class TzrSparseOptim(C.Structure):
@@ -425,6 +442,9 @@ _SIGNATURES = {
     "tzr_amm_loss_workspace": (_sz, [_vp]),
     "tzr_amm_loss_fwd": (_i32, [_vp, _vp]),
     "tzr_amm_loss_bwd": (_i32, [_vp, _vp]),
+    "tzr_distill_loss_workspace": (_sz, [_vp]),
+    "tzr_distill_loss_fwd": (_i32, [_vp, _vp]),
+    "tzr_distill_loss_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

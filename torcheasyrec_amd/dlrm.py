@@ -142,12 +142,16 @@ def _activation(name: Optional[str]) -> Optional[nn.Module]:
 class MLP(nn.Module):
     """Stack of Perceptrons (tzrec/modules/mlp.py:21-177): per layer Linear -> [BatchNorm1d | LayerNorm]
     -> activation -> [Dropout]; with `use_bn` the Linear has no bias (mlp.py:60).  The reference
-    defaults (bias, ReLU, no norm, no dropout) are the DLRM / DeepFM case and take the fused path."""
+    defaults (bias, ReLU, no norm, no dropout) are the DLRM / DeepFM case and take the fused path.
+    `return_hidden_layer_feature` (mlp.py:166-177): forward returns {"hidden_layer<i>": layer i's output, "hidden_layer_end":
+    the last one's} -- the layers one at a time (the fused Linear+ReLU call per layer where the MLP is plain), never the
+    two-layer one-launch `mlp2`, which keeps no hidden output."""
 
     def __init__(self, in_features: int, hidden_units: Sequence[int], bias: bool = True, activation: Optional[str] = "nn.ReLU",
-                 use_bn: bool = False, dropout_ratio=None, use_ln: bool = False) -> None:
+                 use_bn: bool = False, dropout_ratio=None, use_ln: bool = False, return_hidden_layer_feature: bool = False) -> None:
         super().__init__()
         self.hidden_units = list(hidden_units)
+        self.return_hidden_layer_feature = bool(return_hidden_layer_feature)
         if use_bn and use_ln:
             raise ValueError("Could not use_bn and use_ln at the same time in Perceptron.")
         if dropout_ratio is None or (isinstance(dropout_ratio, (list, tuple)) and len(dropout_ratio) == 0):
@@ -162,6 +166,7 @@ class MLP(nn.Module):
             drops = [float(dropout_ratio)] * len(self.hidden_units)
         self._plain = bias and activation == "nn.ReLU" and not use_bn and not use_ln and not any(d > 0 for d in drops)
         layers: List[nn.Module] = []
+        ends: List[int] = []
         d = in_features
         for h, dr in zip(self.hidden_units, drops):
             layers.append(nn.Linear(d, h, bias=False if use_bn else bias))
@@ -175,7 +180,9 @@ class MLP(nn.Module):
             if dr > 0.0:
                 layers.append(nn.Dropout(dr))
             d = h
+            ends.append(len(layers))
         self.mlp = nn.Sequential(*layers)
+        self._layer_ends = ends  # layer i is self.mlp[_layer_ends[i - 1]:_layer_ends[i]]
 
     def output_dim(self) -> int:
         return self.hidden_units[-1]
@@ -183,7 +190,25 @@ class MLP(nn.Module):
     def linears(self) -> List[nn.Linear]:
         return [m for m in self.mlp if isinstance(m, nn.Linear)]
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _hidden_features(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        fused = self._plain and _FUSED_RELU and x.is_cuda and x.dim() == 2
+        out: Dict[str, torch.Tensor] = {}
+        start = 0
+        for i, end in enumerate(self._layer_ends):
+            if fused:
+                x = _LinearReluFn.apply(x, self.mlp[start].weight, self.mlp[start].bias)
+            else:
+                for m in self.mlp[start:end]:
+                    x = m(x)
+            out[f"hidden_layer{i}"] = x
+            start = end
+        if self._layer_ends:
+            out["hidden_layer_end"] = x
+        return out
+
+    def forward(self, x: torch.Tensor):
+        if self.return_hidden_layer_feature:
+            return self._hidden_features(x)
         if self._plain and _FUSED_MLP2 and x.dim() == 2 and (x.is_cuda or _on_emulator()):
             from .dense import mlp2, mlp2_fits
 

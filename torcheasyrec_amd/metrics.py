@@ -275,7 +275,11 @@ class Evaluator:
         self.metrics: Dict[str, object] = {}
         self._specs: Dict[str, MetricSpec] = {}
         self._recalls: List[str] = []  # the match models' metrics: fed predictions["rank"], no label
-        for ms in spec.metrics:
+        # which predictions a model-level metric reads: "" unless the model says otherwise (`metric_suffixes()`; rocket_launching
+        # in evaluation: "_light", keyed auc_light as the reference's update_metric does); a task tower's metric reads its tower's
+        model_suffixes = list(model.metric_suffixes()) if hasattr(model, "metric_suffixes") else [""]
+        self._suffix: Dict[str, str] = {}
+        for ms, extra in [(ms, extra) for ms in spec.metrics for extra in ([""] if ms.tower else model_suffixes)]:
             if ms.kind == "recall_at_k":  # keyed recall@<k> (match_model.py:345-356)
                 name = f"recall@{int(ms.fields.get('top_k', 5))}" + ms.suffix
                 if name in self.metrics:
@@ -291,13 +295,14 @@ class Evaluator:
                 m = GroupedAUC(grouped_auc_capacity, device=device, process_group=self._pg)
             else:
                 raise NotImplementedError(f"metric {ms.kind!r} is not built (built: {', '.join(BUILT_KINDS)})")
-            if ms.name in self.metrics:
-                raise ValueError(f"metric {ms.name!r} is configured twice")
-            self.metrics[ms.name], self._specs[ms.name] = m, ms
+            name = ms.name + extra
+            if name in self.metrics:
+                raise ValueError(f"metric {name!r} is configured twice")
+            self.metrics[name], self._specs[name], self._suffix[name] = m, ms, ms.suffix + extra
         # per tower: the `auc` and the `normalized_entropy` share a launch
         self._towers: Dict[str, List[str]] = {}
-        for name, ms in self._specs.items():
-            self._towers.setdefault(ms.suffix, []).append(name)
+        for name in self._specs:
+            self._towers.setdefault(self._suffix[name], []).append(name)
         # a two-class softmax output: `auc` / `grouped_auc` read the positive class's column (rank_model.py:392-416)
         self._probs_key: Dict[str, str] = {}
         for suffix in self._towers:

@@ -889,6 +889,8 @@ _MODELS["dssm"] = ConfigDSSM
 _MODELS["mind"] = ConfigMIND
 _MODELS["dat"] = ConfigDAT
 
+from . import rocket  # noqa: E402,F401  (rocket.py builds on RankModel and puts _MODELS["rocket_launching"] there itself: either may be imported first)
+
 
 def build_rank_model(spec: PipelineSpec, device=None, sparse_optimizer=None, process_group=None,
                      plan: Optional[Dict[str, dict]] = None, use_planner: bool = False, exchange: str = "exact") -> RankModel:
