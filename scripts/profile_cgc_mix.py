@@ -39,7 +39,7 @@ def bytes_moved(H, T, P, S):
 
 def mix_pass(dev, H, T, P, S):
     """the level's own code path with the experts and gate logits given: ExtractionNet.forward's mixing step"""
-    from torcheasyrec_amd.dense import cgc_mix, cgc_mix_ok
+    from torcheasyrec_amd.gate_ops import cgc_mix, cgc_mix_ok
 
     torch.manual_seed(0)
     shared = list(range(T * P, T * P + S))

@@ -41,7 +41,7 @@ def bytes_moved(H, N):
 
 def step_pass(dev, H, N):
     """PPNet.forward's step behind the GEMMs of one level, the GEMM outputs given"""
-    from torcheasyrec_amd.dense import gate_scale, gate_scale_ok
+    from torcheasyrec_amd.gate_ops import gate_scale, gate_scale_ok
 
     torch.manual_seed(0)
     zs = [torch.randn(B, H, device=dev).requires_grad_(True) for _ in range(N)]

@@ -33,7 +33,7 @@ SHAPES = {"taobao": ([64, 64], [[], [0]], [[], [64]]),
 
 
 def chain_pass(dev, hx, deps, hidden):
-    from torcheasyrec_amd.dense import relation_chain, relation_chain_ok
+    from torcheasyrec_amd.gate_ops import relation_chain, relation_chain_ok
 
     torch.manual_seed(0)
     xs = [torch.randn(B, w, device=dev).requires_grad_(True) for w in hx]

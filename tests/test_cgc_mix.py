@@ -1,4 +1,4 @@
-"""dense.cgc_mix (tzr_cgc_mix_fwd / _bwd, csrc/gate_mix.hip): softmax + mixing of EVERY gate of one CGC level of PLE in one launch
+"""gate_ops.cgc_mix (tzr_cgc_mix_fwd / _bwd, csrc/gate_mix.hip): softmax + mixing of EVERY gate of one CGC level of PLE in one launch
 per direction, each gate over its own subset of the experts, against the reference's stack / softmax / batched-matmul form
 (tzrec/modules/extraction_net.py:98-109) evaluated in float64 on the CPU.  Tolerances: those of
 tests/test_dense_glue.py::test_moe_mix_matches_the_stacked_form -- outputs and expert gradients rtol 1e-5, atol 1e-6; logit
@@ -45,7 +45,7 @@ def draw(B, H, n_experts, sels, dev, seed, strided=False):
 
 
 def run(logits, experts, sels, gouts):
-    from torcheasyrec_amd.dense import cgc_mix, cgc_mix_ok
+    from torcheasyrec_amd.gate_ops import cgc_mix, cgc_mix_ok
 
     assert cgc_mix_ok(logits, experts, sels)
     outs = cgc_mix(logits, experts, sels)
@@ -108,7 +108,7 @@ def test_cgc_mix_takes_any_membership(dev):
 
 
 def test_cgc_mix_ok_refuses_what_the_kernel_does_not_take(dev):
-    from torcheasyrec_amd.dense import cgc_mix_ok
+    from torcheasyrec_amd.gate_ops import cgc_mix_ok
 
     def case(B=6, H=8, n_experts=3, n_gates=2, dtype=torch.float32):
         sels = [list(range(n_experts))] * n_gates

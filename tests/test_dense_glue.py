@@ -224,7 +224,7 @@ def test_skinny_linear_matches_torch(dev, B, K, n):
 def test_moe_mix_matches_the_stacked_form(dev, B, H, E, T):
     """softmax + mixing of all tasks of an MMoE in one launch per direction (tzr_moe_mix_fwd / _bwd) against the reference's
     literal form: stack, softmax, batched matmul (tzrec/modules/mmoe.py:63-76) and its autograd"""
-    from torcheasyrec_amd.dense import moe_mix, moe_mix_ok
+    from torcheasyrec_amd.gate_ops import moe_mix, moe_mix_ok
 
     g = torch.Generator().manual_seed(B + H + E + T)
     xs = [torch.randn(B, H, generator=g) for _ in range(E)]

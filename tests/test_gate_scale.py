@@ -1,4 +1,4 @@
-"""dense.gate_scale (tzr_gate_scale_fwd / _bwd, csrc/gate_scale.hip): out_n = act(z_n + bz_n) * gamma * sigmoid(g_n + bg_n) for
+"""gate_ops.gate_scale (tzr_gate_scale_fwd / _bwd, csrc/gate_scale.hip): out_n = act(z_n + bz_n) * gamma * sigmoid(g_n + bg_n) for
 every slot of one PPNet level (or EPNet's one gate) in one launch per direction, against the literal expression evaluated in
 float64 on the CPU.  Tolerances: out, dz, dg are elementwise kinds of tests/test_cgc_mix.py -- rtol 1e-5, atol 1e-6; the bias
 gradients (sums over the batch) 4 x the distance of torch's own fp32 literal form to the float64 result on the same inputs,
@@ -59,7 +59,7 @@ def draw(B, H, N, relu, dev, seed, strided=False, with_bz=True):
 
 
 def run(zs, bzs, gs, bgs, gouts, relu):
-    from torcheasyrec_amd.dense import gate_scale, gate_scale_ok
+    from torcheasyrec_amd.gate_ops import gate_scale, gate_scale_ok
 
     assert gate_scale_ok(zs, gs, bzs, bgs)
     outs = gate_scale(zs, bzs, gs, bgs, GAMMA, relu)
@@ -123,7 +123,7 @@ def test_gate_scale_matches_the_literal_form(dev, B, H, N, relu, strided):
 
 
 def test_gate_scale_ok_refuses_what_the_kernel_does_not_take(dev):
-    from torcheasyrec_amd.dense import gate_scale_ok
+    from torcheasyrec_amd.gate_ops import gate_scale_ok
 
     def case(B=6, H=8, N=2, dtype=torch.float32):
         new = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731

@@ -141,7 +141,7 @@ def test_jagged_kernels_edge_cases(dev, name, kind):
 def test_rows_taken_as_a_column_slice_of_a_wider_tensor(dev, kind):
     """non-contiguous strides reach the kernels as they are (row stride 40 floats, first column 4 floats in): same bits as
     the contiguous copy"""
-    from torcheasyrec_amd.sequence import _rows
+    from torcheasyrec_amd._lib import rows16 as _rows
 
     D, lengths, max_len = 32, [9, 0, 70, 3], 80
     g = torch.Generator().manual_seed(9)
@@ -160,6 +160,31 @@ def test_rows_taken_as_a_column_slice_of_a_wider_tensor(dev, kind):
     for a, b in zip(*res):
         assert torch.equal(a, b)
     assert float(res[0][0].abs().sum()) > 0
+
+
+@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("kind", ["attn", "mean"])
+def test_one_row_slices_of_a_wider_tensor(dev, kind, N):
+    """B = 1, N = 1: rows, query and output gradient are one-row slices [1:2, :8] of [4, 10] tensors -- row stride 10 floats, first
+    float 8 bytes past a 16-byte boundary, and "contiguous" to torch whatever their strides, so .contiguous() hands them on as they
+    are and the library refuses them (TZR_ERR_UNSUPPORTED: the row stride).  The encoders copy such rows (`_lib.rows16` clones).
+    N = 2: the one-row query and output gradient beside two rows -- over one score the softmax is 1 whatever the query holds; over
+    two, the copy of the query is what the outputs and gradients show."""
+    D, lengths, max_len = 8, [N], 4
+    g = torch.Generator().manual_seed(11)
+    rows, query, gy = (torch.randn(4, D + 2, generator=g).to(dev)[1:1 + n, :D] for n in (N, 1, 1))
+    assert query.contiguous().data_ptr() == query.data_ptr() and gy.data_ptr() % 16 == 8
+    assert N > 1 or rows.contiguous().data_ptr() == rows.data_ptr() and rows.data_ptr() % 16 == 8 and rows.stride(0) == D + 2
+    r, q = rows.detach().requires_grad_(True), query.detach().requires_grad_(True)
+    y = jagged_dot_attention(r, q, _offsets(lengths).to(dev), max_len) if kind == "attn" else jagged_pool(r, _offsets(lengths).to(dev), max_len, kind)
+    y.backward(gy)
+    rd, qd = rows.detach().cpu().double().requires_grad_(True), query.detach().cpu().double().requires_grad_(True)
+    want = ref.simple_attention(qd, rd, lengths, N) if kind == "attn" else ref.pooling(rd, lengths, N, kind)
+    want.backward(gy.cpu().double())
+    torch.testing.assert_close(y.detach().cpu(), want.detach().float(), rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(r.grad.cpu(), rd.grad.float(), rtol=1e-5, atol=1e-5)
+    if kind == "attn":
+        torch.testing.assert_close(q.grad.cpu(), qd.grad.float(), rtol=1e-5, atol=1e-5)
 
 
 def test_max_len_bound_of_the_attention_kernels(dev):

@@ -1,7 +1,7 @@
 """personalized_net.EPNet / PPNet against vectors recorded from the reference's own modules
 (tests/golden/make_reference_pepnet_vectors.py running tzrec/modules/personalized_net.py): loaded with the reference's parameters
 under the reference's state-dict keys they reproduce the reference's outputs, input gradients and parameter gradients, with the
-gate-and-scale step fused (dense.gate_scale: one tzr_gate_scale_fwd per PPNet level, one per EPNet) and in the literal form.
+gate-and-scale step fused (gate_ops.gate_scale: one tzr_gate_scale_fwd per PPNet level, one per EPNet) and in the literal form.
 Bound per kind: 4 x the reference's own fp32-vs-float64 distance stored with the vectors, floor 2^-20 (tests/test_ple_module.py's)."""
 import os
 

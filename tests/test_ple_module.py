@@ -1,7 +1,7 @@
 """ple.ExtractionNet (one CGC level of PLE) against vectors recorded from the reference's own module
 (tests/golden/make_reference_ple_vectors.py running tzrec/modules/extraction_net.py): loaded with the reference's parameters
 under the reference's state-dict keys it reproduces the reference's outputs, input gradients and parameter gradients, with the
-gate-and-mix step fused (dense.cgc_mix, one tzr_cgc_mix_fwd per level) and in the literal form.  Bound per kind: 4 x the
+gate-and-mix step fused (gate_ops.cgc_mix, one tzr_cgc_mix_fwd per level) and in the literal form.  Bound per kind: 4 x the
 reference's own fp32-vs-float64 distance stored with the vectors (the factor tests/test_cross_v2.py and tests/test_wukong_module.py
 hold their modules to against the same yardstick), floor 2^-20 as there."""
 import os

@@ -1,4 +1,4 @@
-"""dense.relation_chain (tzr_relation_chain_fwd / _bwd, csrc/relation_chain.hip): every Bayesian relation tower of a DBMTL
+"""gate_ops.relation_chain (tzr_relation_chain_fwd / _bwd, csrc/relation_chain.hip): every Bayesian relation tower of a DBMTL
 model in one launch forward and two backward, against the literal cat / Linear / ReLU form evaluated in float64 on the CPU
 (tests/relation_chain_ref.py).  Per kind (h, dx, dW, db): max |got - fp64| / max(1, |fp64|) at or below 4 x the distance of
 torch's own fp32 literal form to the float64 result on the same inputs, floor 2^-20.  The inputs are settled: no float64
@@ -25,7 +25,7 @@ def to_dev(xs, layers, gouts, dev, strided=False):
 
 
 def run(xs, deps, layers, gouts):
-    from torcheasyrec_amd.dense import relation_chain, relation_chain_ok
+    from torcheasyrec_amd.gate_ops import relation_chain, relation_chain_ok
 
     assert relation_chain_ok(xs, deps, layers)
     rs, hs = relation_chain(xs, deps, layers, hidden=True)
@@ -117,7 +117,7 @@ def test_inputs_as_column_slices_of_wider_buffers(dev):
 
 
 def test_forward_under_no_grad(dev):
-    from torcheasyrec_amd.dense import relation_chain
+    from torcheasyrec_amd.gate_ops import relation_chain
 
     hx, deps, widths = GRAPHS["l0_consumed"]
     xs, layers, gouts = ref.draw(9, hx, deps, widths, seed=8)
@@ -131,7 +131,7 @@ def test_forward_under_no_grad(dev):
 
 
 def test_relation_chain_ok_refuses_what_the_kernel_does_not_take(dev):
-    from torcheasyrec_amd.dense import relation_chain_ok
+    from torcheasyrec_amd.gate_ops import relation_chain_ok
 
     def case(B=6, hx=(8, 8), widths=((8,), (8,)), deps=((), (0,)), dtype=torch.float32):
         new = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731

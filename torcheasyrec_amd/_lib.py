@@ -567,6 +567,85 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def opt_ptr(t: Optional[torch.Tensor]) -> int:
+    """the address for a struct field: 0 for an operand that is not there"""
+    return 0 if t is None else ptr(t)
+
+
+# ---- operands of the fused ops: the rules their *_ok predicates and autograd Functions share ------------------------------
+def takes(x) -> bool:
+    """`x` (a tensor or a device) is on the device of the loaded library: HIP memory for the gfx950 build, host memory for the
+    emulator.  Loads the library when none is loaded yet."""
+    if _lib is None:
+        lib()
+    return (getattr(x, "device", x).type == "cpu") == (_backend == "emu")
+
+
+def emulated(load: bool = False) -> bool:
+    """the emulator is the loaded library.  Loads none unless `load`: the modules' routing guards (`x.is_cuda or emulated()`) leave
+    a CPU tensor to the literal form in a process that has loaded nothing, and send every HIP tensor on to the op's own predicate."""
+    if load and _lib is None:
+        lib()
+    return _lib is not None and _backend == "emu"
+
+
+def rows_f4(t: torch.Tensor) -> bool:
+    """the rows of `t` can be read as float4 pieces: 2-D fp32, unit column stride, row stride a multiple of 4 floats, 16-byte
+    aligned data.  (The tall-input linears read the leading K columns of such rows; their library entry checks K itself.)"""
+    return t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+def rows_ok(t: torch.Tensor, D: Optional[int] = None) -> bool:
+    """what `tzr_rows_operand` (csrc/tzr_common.h) takes as a [B, H] float4 row operand: `rows_f4` with the rows a whole width
+    apart, D columns when `D` is given.  A column slice of a wider buffer passes; the number of rows is the caller's to look at."""
+    if t.dim() != 2 or t.dtype != torch.float32:
+        return False
+    stride, one = t.stride()  # (one look at the strides: these predicates run on every eager forward)
+    return one == 1 and stride % 4 == 0 and stride >= t.shape[1] and t.data_ptr() % 16 == 0 and (D is None or t.shape[1] == D)
+
+
+def rows3_ok(t: torch.Tensor) -> bool:
+    """fp32 [B, K, D] whose B K rows lie one row stride apart: a `rows_ok` operand [B K, D] (a column slice of a [B K, .] buffer is)"""
+    s0, s1, s2 = t.stride()
+    return t.dtype == torch.float32 and s2 == 1 and s1 % 4 == 0 and s1 >= t.shape[2] and s0 == t.shape[1] * s1 and t.data_ptr() % 16 == 0
+
+
+def rows16(t: torch.Tensor) -> torch.Tensor:
+    """`t` when `rows_ok` takes it (a gradient slice of a torch.cat does not), else a copy it takes: a clone, .contiguous() keeps
+    the odd strides of a 1-row tensor"""
+    return t if rows_ok(t) else t.clone(memory_format=torch.contiguous_format)
+
+
+def scalar_row_stride(t: torch.Tensor) -> int:
+    """floats between the rows of a [B, D] tensor with unit column stride (the stride of a single row says nothing)"""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def scalar_rows(t: torch.Tensor) -> torch.Tensor:
+    """`t` when its rows are whole and apart (a column slice of a wider tensor is), else a copy (an expanded gradient): the rule
+    of the kernels that read rows float by float (cross networks, CIN, LayerNorm-and-mask, WuKong) -- no alignment, not `rows_ok`"""
+    return t if t.stride(1) == 1 and scalar_row_stride(t) >= t.shape[1] else t.contiguous()
+
+
+def packed_ok(t: torch.Tensor, shape: tuple, dev: torch.device, aligned: bool = False) -> bool:
+    """a contiguous fp32 tensor of `shape` on `dev` (sample weights [B], a bias [H], a weight matrix); `aligned`: at a 16-byte address"""
+    return bool(t.shape == shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                and (not aligned or t.data_ptr() % 16 == 0))
+
+
+def launch(name: str, m: C.Structure, dev: torch.device) -> None:
+    """entry point `name`(&m, torch's current stream on `dev`), checked.  Looked up when called: tests wrap the entry points."""
+    check(getattr(lib(), name)(C.byref(m), stream_ptr(dev)), name)
+
+
+def launch_ws(stem: str, m: C.Structure, dev: torch.device, entry: str) -> torch.Tensor:
+    """`launch(entry, m, dev)` with the scratch `<stem>_workspace(&m)` asks for in m.ws / m.ws_bytes -> that scratch"""
+    ws = workspace(getattr(lib(), stem + "_workspace")(C.byref(m)), dev)
+    m.ws, m.ws_bytes = ptr(ws), ws.numel()
+    launch(entry, m, dev)
+    return ws
+
+
 def ptr_array(tensors):
     """a C array of the tensors' addresses (the `const float* const*` arguments)"""
     return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])

@@ -7,7 +7,6 @@ runs `capsule_literal`, the reference's padded form word for word.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -85,11 +84,6 @@ def capsule_literal(x: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor
     return high * capsule_mask.unsqueeze(-1).to(x.dtype), capsule_mask
 
 
-def _rows_ok(x: torch.Tensor, D: int) -> bool:
-    return bool(x.dim() == 2 and x.shape[1] == D and x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0
-                and x.stride(0) >= D and x.data_ptr() % 16 == 0)
-
-
 def capsule_ok(x: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, cfg: CapsuleConfig,
                logits0: Optional[torch.Tensor] = None) -> bool:
     """what tzr_capsule_* takes: fp32 x [N, L] with unit column stride, a row stride that is a multiple of 4 floats and 16-byte
@@ -99,24 +93,20 @@ def capsule_ok(x: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor, cfg
     if x.dim() != 2 or weight.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
         return False
     (N, L), H, K, S = x.shape, weight.shape[1], cfg.max_k, cfg.max_seq_len
-    if (x.device.type == "cpu") != (_lib.backend() == "emu") or weight.device != x.device or offsets.device != x.device:
+    if not _lib.takes(x) or weight.device != x.device or offsets.device != x.device:
         return False
     if not (L % 4 == 0 and 4 <= L <= _lib.CAPSULE_MAX_DIM and H % 4 == 0 and 4 <= H <= _lib.CAPSULE_MAX_DIM and weight.shape[0] == L):
         return False
     if not (1 <= K <= _lib.CAPSULE_MAX_K and 1 <= cfg.num_iters <= _lib.CAPSULE_MAX_ITERS and 1 <= S <= _lib.CAPSULE_MAX_S
             and (S + 15) // 16 * 16 * H <= _lib.CAPSULE_MAX_SH and cfg.routing_logits_scale > 0):
         return False
-    if not (weight.dtype == torch.float32 and weight.is_contiguous() and weight.data_ptr() % 16 == 0
-            and offsets.dtype == torch.int64 and offsets.is_contiguous()):
+    if not (_lib.packed_ok(weight, (L, H), x.device, aligned=True) and offsets.dtype == torch.int64 and offsets.is_contiguous()):
         return False
-    if N > 0 and not _rows_ok(x, L):
+    if N > 0 and not _lib.rows_ok(x, L):
         return False
     if x.dtype != torch.float32 or N >= 2 ** 31 or offsets.numel() - 1 >= 2 ** 31:
         return False
-    if logits0 is not None and not (logits0.shape == (N, K) and logits0.dtype == torch.float32 and logits0.is_contiguous()
-                                    and logits0.device == x.device):
-        return False
-    return True
+    return logits0 is None or _lib.packed_ok(logits0, (N, K), x.device)
 
 
 class _CapsuleFn(torch.autograd.Function):
@@ -134,7 +124,7 @@ class _CapsuleFn(torch.autograd.Function):
         else:
             m.x_stride = x.shape[1]
         m.offsets, m.w, m.pre = _lib.ptr(offsets), _lib.ptr(weight), _lib.ptr(pre)
-        m.logits0 = _lib.ptr(logits0) if logits0 is not None and x.shape[0] > 0 else 0
+        m.logits0 = _lib.opt_ptr(logits0) if x.shape[0] > 0 else 0
 
     @staticmethod
     def forward(ctx, x, offsets, weight, logits0, cfg):
@@ -146,7 +136,7 @@ class _CapsuleFn(torch.autograd.Function):
         m = _lib.TzrCapsule()
         _CapsuleFn._fill(m, x, offsets, weight, logits0, cfg, c, pre)
         m.high, m.high_stride, m.mask = _lib.ptr(high), H, _lib.ptr(mask)
-        _lib.check(_lib.lib().tzr_capsule_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_capsule_fwd")
+        _lib.launch("tzr_capsule_fwd", m, dev)
         ctx.save_for_backward(x, offsets, weight, c, pre)
         ctx.cfg = cfg
         ctx.mark_non_differentiable(mask, c)
@@ -159,10 +149,9 @@ class _CapsuleFn(torch.autograd.Function):
             return None, None, None, None, None
         x, offsets, weight, c, pre = ctx.saved_tensors
         cfg, dev = ctx.cfg, x.device
-        B, K, H = pre.shape
         g = ghigh.to(torch.float32)
-        if not (g.stride(2) == 1 and g.stride(1) % 4 == 0 and g.stride(1) >= H and g.stride(0) == K * g.stride(1) and g.data_ptr() % 16 == 0):
-            g = g.contiguous()
+        if not _lib.rows3_ok(g):
+            g = g.clone(memory_format=torch.contiguous_format)  # (.contiguous() keeps the odd strides of a 1-row tensor)
         dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
         dw = torch.empty(weight.shape, dtype=torch.float32, device=dev)
         m = _lib.TzrCapsule()
@@ -172,10 +161,7 @@ class _CapsuleFn(torch.autograd.Function):
             m.dx, m.dx_stride = _lib.ptr(dx), dx.stride(0)
         else:
             m.dx_stride = x.shape[1]
-        L = _lib.lib()
-        ws = _lib.workspace(L.tzr_capsule_workspace(C.byref(m)), dev)
-        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
-        _lib.check(L.tzr_capsule_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_capsule_bwd")
+        _lib.launch_ws("tzr_capsule", m, dev, "tzr_capsule_bwd")
         return dx, None, dw, None, None
 
 

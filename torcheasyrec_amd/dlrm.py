@@ -13,6 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 from torch import nn
 
+from . import _lib
 from .embedding import EmbeddingBagCollection, EmbeddingBagConfig, SparseOptimizerConfig
 from .interaction import FactorizationMachine, dot_interaction
 from .sparse import KeyedJaggedTensor
@@ -30,13 +31,6 @@ _FUSED_TOP_LOSS = os.environ.get("TZR_FUSED_TOP_LOSS", "1") == "1"  # A/B switch
 # persistent kernels' prologue (W1 into registers, 200 KB per workgroup) is not amortised
 _FUSED_IA_TOP = os.environ.get("TZR_FUSED_IA_TOP", "1") == "1"
 _FUSED_IA_TOP_MIN_B = int(os.environ.get("TZR_FUSED_IA_TOP_MIN_B", "0"))
-
-
-def _on_emulator() -> bool:
-    from . import _lib
-
-    return _lib._lib is not None and _lib.backend() == "emu"
-
 
 
 class _LinearReluFn(torch.autograd.Function):
@@ -118,7 +112,7 @@ class OutputLinear(nn.Linear):
     as nn.Linear)."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if _SKINNY_LINEAR and (x.is_cuda or _on_emulator()) and x.dim() == 2:
+        if _SKINNY_LINEAR and (x.is_cuda or _lib.emulated()) and x.dim() == 2:
             from .dense import skinny_linear_ok
 
             if skinny_linear_ok(x, self.weight):
@@ -209,7 +203,7 @@ class MLP(nn.Module):
     def forward(self, x: torch.Tensor):
         if self.return_hidden_layer_feature:
             return self._hidden_features(x)
-        if self._plain and _FUSED_MLP2 and x.dim() == 2 and (x.is_cuda or _on_emulator()):
+        if self._plain and _FUSED_MLP2 and x.dim() == 2 and (x.is_cuda or _lib.emulated()):
             from .dense import mlp2, mlp2_fits
 
             lin = self.linears()
@@ -228,9 +222,9 @@ class MLP(nn.Module):
 def head_loss(model, dense: torch.Tensor, sparse: torch.Tensor, labels: torch.Tensor, d: Optional[torch.Tensor] = None):
     """(mean BCE-with-logits loss, logits [B]) of a DLRM head (`dense_mlp`, `final_mlp`, `output_mlp`, `dim`,
     `arch_with_sparse` of `model`) on the dense features and the pooled sparse block; shared by DLRM and ShardedDLRM."""
-    fused = _FUSED_TOP_LOSS and model.final_mlp._plain and (sparse.is_cuda or _on_emulator())
+    fused = _FUSED_TOP_LOSS and model.final_mlp._plain and (sparse.is_cuda or _lib.emulated())
     if (d is None and fused and _FUSED_IA_TOP and _FUSED_MLP2 and model.arch_with_sparse and sparse.shape[0] >= _FUSED_IA_TOP_MIN_B
-            and getattr(model.dense_mlp, "_plain", False) and dense.dim() == 2 and (dense.is_cuda or _on_emulator())):
+            and getattr(model.dense_mlp, "_plain", False) and dense.dim() == 2 and (dense.is_cuda or _lib.emulated())):
         from .dense import head_phases_fit, head_phases_loss, top_loss_fits
 
         bot, lin = model.dense_mlp.linears(), model.final_mlp.linears()
@@ -305,7 +299,7 @@ class DLRM(nn.Module):
     def predict_from_embeddings(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
         d = self.dense_mlp(dense)
         if (not torch.is_grad_enabled() and _FUSED_IA_TOP and self.final_mlp._plain and self.arch_with_sparse
-                and (sparse.is_cuda or _on_emulator()) and sparse.shape[0] >= _FUSED_IA_TOP_MIN_B):
+                and (sparse.is_cuda or _lib.emulated()) and sparse.shape[0] >= _FUSED_IA_TOP_MIN_B):
             from .dense import interaction_first_layer, interaction_top_fits
 
             lin = self.final_mlp.linears()

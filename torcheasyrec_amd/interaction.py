@@ -132,28 +132,18 @@ FUSED_CROSS = True  # A/B switch: False = the reference's literal loop (a produc
 CROSS_MAX_DIM, CROSS_MAX_LAYERS = 1024, 8  # CN_MAXDIM, CN_MAXL of csrc/cross_net.hip
 
 
-def _row_stride(t: torch.Tensor) -> int:
-    """floats between the rows of a [B, D] tensor with unit column stride (the stride of a single row says nothing)"""
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """`t` when its rows are whole and apart (a column slice of a wider tensor is), else a copy (an expanded gradient)"""
-    return t if t.stride(1) == 1 and _row_stride(t) >= t.shape[1] else t.contiguous()
-
-
 class _CrossFn(torch.autograd.Function):
     """y = x_L of x_{l+1} = (x_l . w_l) x_0 + b_l + x_l: tzr_cross_fwd keeps the scalars x_l . w_l ([B, L]), tzr_cross_bwd
     returns the input gradient and the finished gradients of every w_l and b_l (rows of one [2, L, D] buffer)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, L: int, *params: torch.Tensor):
-        x = _rows(x)
+        x = _lib.scalar_rows(x)
         B, D = x.shape
         params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
         y = torch.empty(B, D, dtype=torch.float32, device=x.device)
         s = torch.empty(B, L, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().tzr_cross_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), L, B, D,
+        rc = _lib.lib().tzr_cross_fwd(_lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), L, B, D,
                                       _lib.ptr(y), D, _lib.ptr(s), _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cross_fwd")
         ctx.save_for_backward(x, s, *params)
@@ -164,14 +154,14 @@ class _CrossFn(torch.autograd.Function):
         x, s, *params = ctx.saved_tensors
         B, D = x.shape
         L = len(params) // 2
-        gy = _rows(gy)
+        gy = _lib.scalar_rows(gy)
         dx = torch.empty(B, D, dtype=torch.float32, device=x.device)
         dwb = torch.empty(2, L, D, dtype=torch.float32, device=x.device)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_cross_bwd_workspace(B, D, L), x.device)
-        rc = lib.tzr_cross_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(s), _lib.ptr_array(params[:L]),
-                               _lib.ptr_array(params[L:]), L, B, D, _lib.ptr(dx), D, _lib.ptr(dwb[0]), _lib.ptr(dwb[1]), _lib.ptr(ws),
-                               ws.numel(), _lib.stream_ptr(x.device))
+        rc = lib.tzr_cross_bwd(_lib.ptr(gy), _lib.scalar_row_stride(gy), _lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr(s),
+                               _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), L, B, D, _lib.ptr(dx), D,
+                               _lib.ptr(dwb[0]), _lib.ptr(dwb[1]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cross_bwd")
         return (dx, None, *[dwb[0, l].view(1, D) for l in range(L)], *[dwb[1, l] for l in range(L)])
 
@@ -200,11 +190,9 @@ class Cross(nn.Module):
             nn.init.zeros_(self.b[i])
 
     def _fused_ok(self, x: torch.Tensor) -> bool:
-        from .dlrm import _on_emulator
-
         return bool(FUSED_CROSS and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
                     and 1 <= self.cross_num <= CROSS_MAX_LAYERS and 1 <= x.shape[1] <= CROSS_MAX_DIM
-                    and self.w[0].weight.dtype == torch.float32 and (x.is_cuda or _on_emulator()))
+                    and self.w[0].weight.dtype == torch.float32 and (x.is_cuda or _lib.emulated()))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fused_ok(x):
@@ -226,14 +214,14 @@ class _CrossV2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, L: int, save: bool, *params: torch.Tensor):
-        x = _rows(x)
+        x = _lib.scalar_rows(x)
         B, D = x.shape
         params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
         R = params[0].shape[0]
         y = torch.empty(B, D, dtype=torch.float32, device=x.device)
         xs = torch.empty(L - 1, B, D, dtype=torch.float32, device=x.device) if save else None
         t = torch.empty(L, B, R, dtype=torch.float32, device=x.device) if save else None
-        rc = _lib.lib().tzr_cross_v2_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:2 * L]),
+        rc = _lib.lib().tzr_cross_v2_fwd(_lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:2 * L]),
                                          _lib.ptr_array(params[2 * L:]), L, B, D, R, _lib.ptr(y), D, _lib.ptr(xs), _lib.ptr(t),
                                          _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cross_v2_fwd")
@@ -247,7 +235,7 @@ class _CrossV2Fn(torch.autograd.Function):
         B, D = x.shape
         L = len(params) // 3
         R = params[0].shape[0]
-        gy = _rows(gy)
+        gy = _lib.scalar_rows(gy)
         dev = x.device
         dx = torch.empty(B, D, dtype=torch.float32, device=dev)
         du = torch.empty(L, R, D, dtype=torch.float32, device=dev)
@@ -255,7 +243,7 @@ class _CrossV2Fn(torch.autograd.Function):
         dc = torch.empty(L, D, dtype=torch.float32, device=dev)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_cross_v2_bwd_workspace(B, D, R, L), dev)
-        rc = lib.tzr_cross_v2_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr(xs), _lib.ptr(t),
+        rc = lib.tzr_cross_v2_bwd(_lib.ptr(gy), _lib.scalar_row_stride(gy), _lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr(xs), _lib.ptr(t),
                                   _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:2 * L]), _lib.ptr_array(params[2 * L:]), L, B, D, R,
                                   _lib.ptr(dx), D, _lib.ptr(du), _lib.ptr(dv), _lib.ptr(dc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_cross_v2_bwd")
@@ -279,12 +267,10 @@ class CrossV2(nn.Module):
         return self._input_dim
 
     def _fused_ok(self, x: torch.Tensor) -> bool:
-        from .dlrm import _on_emulator
-
         return bool(FUSED_CROSS_V2 and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
                     and 1 <= self.cross_num <= CROSS_V2_MAX_LAYERS and 1 <= x.shape[1] <= CROSS_V2_MAX_DIM
                     and x.shape[1] == self._input_dim and 1 <= self._low_rank <= CROSS_V2_MAX_RANK
-                    and self.u_kernels[0].weight.dtype == torch.float32 and (x.is_cuda or _on_emulator()))
+                    and self.u_kernels[0].weight.dtype == torch.float32 and (x.is_cuda or _lib.emulated()))
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         if self._fused_ok(input):
@@ -308,14 +294,14 @@ class _CINFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, F: int, D: int, layers, *params: torch.Tensor):
-        x = _rows(x)
+        x = _lib.scalar_rows(x)
         B, L = x.shape[0], len(layers)
         params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)
         y = torch.empty(B, sum(layers), dtype=torch.float32, device=x.device)
         save = any(ctx.needs_input_grad)
         xs = [torch.empty(B, o, D, dtype=torch.float32, device=x.device) for o in layers[:-1]] if save else []
         sizes = (C.c_int * L)(*layers)
-        rc = _lib.lib().tzr_cin_fwd(_lib.ptr(x), _row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), sizes, L, B, F, D,
+        rc = _lib.lib().tzr_cin_fwd(_lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr_array(params[:L]), _lib.ptr_array(params[L:]), sizes, L, B, F, D,
                                     _lib.ptr_array(xs) if xs else None, _lib.ptr(y), y.shape[1], _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cin_fwd")
         ctx.save_for_backward(x, *params[:L], *xs)
@@ -333,14 +319,14 @@ class _CINFn(torch.autograd.Function):
                                "run the forward again (or set interaction.FUSED_CIN = False) for a second backward")
         ctx.consumed = True
         B = x.shape[0]
-        gy = _rows(gy)
+        gy = _lib.scalar_rows(gy)
         hs = (F,) + layers[:-1]
         total = sum(o * h * F + o for o, h in zip(layers, hs))
         gx = torch.empty(B, F * D, dtype=torch.float32, device=x.device)
         dwc = torch.empty(total, dtype=torch.float32, device=x.device)
         lib, sizes = _lib.lib(), (C.c_int * L)(*layers)
         ws = _lib.workspace(lib.tzr_cin_bwd_workspace(B, F, D, sizes, L), x.device)
-        rc = lib.tzr_cin_bwd(_lib.ptr(gy), _row_stride(gy), _lib.ptr(x), _row_stride(x), _lib.ptr_array(ws_), sizes, L, B, F, D,
+        rc = lib.tzr_cin_bwd(_lib.ptr(gy), _lib.scalar_row_stride(gy), _lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr_array(ws_), sizes, L, B, F, D,
                              _lib.ptr_array(xs) if xs else None, _lib.ptr(gx), F * D, _lib.ptr(dwc), _lib.ptr(ws), ws.numel(),
                              _lib.stream_ptr(x.device))
         _lib.check(rc, "tzr_cin_bwd")
@@ -369,15 +355,13 @@ class CIN(nn.Module):
         return sum(self.cin_layer_size)
 
     def _fused_ok(self, x: torch.Tensor) -> bool:
-        from .dlrm import _on_emulator
-
         L = len(self.cin_layer_size)
         return bool(FUSED_CIN and x.dim() == 3 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
                     and x.shape[1] == self.feature_num and 1 <= L <= CIN_MAX_LAYERS
                     and 1 <= x.shape[1] <= CIN_MAX_FEATURES and 1 <= x.shape[2] <= CIN_MAX_DIM
                     and all(1 <= o <= CIN_MAX_LAYER_SIZE for o in self.cin_layer_size)
                     and all(m.weight.dtype == torch.float32 and m.bias is not None for m in self.cin_layers)
-                    and (x.is_cuda or _on_emulator()))
+                    and (x.is_cuda or _lib.emulated()))
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         if self._fused_ok(input):

@@ -16,15 +16,15 @@ import torch
 from torch import nn
 
 from . import _lib
-from .dlrm import MLP, _LinearReluFn, _on_emulator
-from .interaction import _row_stride, _rows, _traced
+from .dlrm import MLP, _LinearReluFn
+from .interaction import _traced
 
 FUSED_MASKNET = True  # A/B switch: False = the reference's literal loop (nn.LayerNorm, a multiply, nn.ReLU, a concat, op by op)
 LN_MASK_MAX_DIM, LN_MASK_MAX_OUT = 1024, 8  # LM_MAXDIM, LM_MAXOUT of csrc/ln_mask.hip
 
 
 def _strides(ts: Sequence[torch.Tensor]):
-    return (C.c_int64 * len(ts))(*[_row_stride(t) for t in ts])
+    return (C.c_int64 * len(ts))(*[_lib.scalar_row_stride(t) for t in ts])
 
 
 class _LnMaskFn(torch.autograd.Function):
@@ -37,10 +37,10 @@ class _LnMaskFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n_out: int, shared: bool, relu: bool, concat: bool, eps: float, *ts: torch.Tensor):
         n_x = 1 if shared else n_out
-        xs = [_rows(t) for t in ts[:n_x]]
+        xs = [_lib.scalar_rows(t) for t in ts[:n_x]]
         gammas = [t.contiguous() for t in ts[n_x:2 * n_x]]
         betas = [t.contiguous() for t in ts[2 * n_x:3 * n_x]]
-        ms = [_rows(t) for t in ts[3 * n_x:]]
+        ms = [_lib.scalar_rows(t) for t in ts[3 * n_x:]]
         assert len(ms) in (0, n_out)
         B, D = xs[0].shape
         dev = xs[0].device
@@ -65,10 +65,10 @@ class _LnMaskFn(torch.autograd.Function):
         B, D = xs[0].shape
         dev = xs[0].device
         if concat or n_out == 1:
-            g = _rows(gouts[0])
+            g = _lib.scalar_rows(gouts[0])
             gouts = [g[:, j * D:(j + 1) * D] for j in range(n_out)]
         else:
-            gouts = [_rows(g) for g in gouts]
+            gouts = [_lib.scalar_rows(g) for g in gouts]
         gx = [torch.empty(B, D, dtype=torch.float32, device=dev) for _ in range(n_x)]
         gm = [torch.empty(B, D, dtype=torch.float32, device=dev) for _ in range(n_out)] if masked else []
         dgb = torch.empty(2, n_x, D, dtype=torch.float32, device=dev)
@@ -87,7 +87,7 @@ def ln_mask_ok(x: torch.Tensor, n_out: int, *params: torch.Tensor) -> bool:
     """the row kernels take `x` [B, D] with these LayerNorm parameters for n_out outputs"""
     return bool(x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
                 and 1 <= x.shape[1] <= LN_MASK_MAX_DIM and 1 <= n_out <= LN_MASK_MAX_OUT
-                and all(p is not None and p.dtype == torch.float32 for p in params) and (x.is_cuda or _on_emulator()))
+                and all(p is not None and p.dtype == torch.float32 for p in params) and (x.is_cuda or _lib.emulated()))
 
 
 def _linear_relu(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:

@@ -11,7 +11,6 @@ tzr_amm_loss_fwd / _bwd, csrc/amm_loss.hip) likewise by `FUSED_AMM_LOSS` and `am
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
@@ -26,11 +25,6 @@ SAMPLED, IN_BATCH = _lib.MATCH_SAMPLED, _lib.MATCH_IN_BATCH
 FUSED_MATCH_SOFTMAX = True  # profiles/match_softmax: the fused head against the literal one at both modes' example shapes
 
 
-def _rows_ok(x: torch.Tensor, D: int) -> bool:
-    return bool(x.dim() == 2 and x.shape[1] == D and x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0
-                and x.stride(0) >= D and x.data_ptr() % 16 == 0)
-
-
 def match_softmax_ok(user: torch.Tensor, item: torch.Tensor, mode: int, weights: Optional[torch.Tensor] = None) -> bool:
     """what tzr_match_softmax_* takes: fp32 user [B, D] and item [M, D] with unit column stride, row strides that are multiples of
     4 floats and 16-byte aligned rows (column slices of wider buffers are fine); D % 4 == 0, 4 <= D <= 256; B >= 1; M >= B in
@@ -39,9 +33,9 @@ def match_softmax_ok(user: torch.Tensor, item: torch.Tensor, mode: int, weights:
     if user.dim() != 2 or item.dim() != 2:
         return False
     B, D = user.shape
-    if (user.device.type == "cpu") != (_lib.backend() == "emu") or item.device != user.device:
+    if not _lib.takes(user) or item.device != user.device:
         return False
-    if not (D % 4 == 0 and 4 <= D <= _lib.MATCH_SOFTMAX_MAX_D and B >= 1 and _rows_ok(user, D) and _rows_ok(item, D)):
+    if not (D % 4 == 0 and 4 <= D <= _lib.MATCH_SOFTMAX_MAX_D and B >= 1 and _lib.rows_ok(user, D) and _lib.rows_ok(item, D)):
         return False
     M = item.shape[0]
     if mode == SAMPLED:
@@ -52,10 +46,7 @@ def match_softmax_ok(user: torch.Tensor, item: torch.Tensor, mode: int, weights:
             return False
     else:
         return False
-    if weights is not None and not (weights.shape == (B,) and weights.dtype == torch.float32 and weights.is_contiguous()
-                                    and weights.device == user.device):
-        return False
-    return True
+    return weights is None or _lib.packed_ok(weights, (B,), user.device)
 
 
 def match_scores(user: torch.Tensor, item: torch.Tensor, mode: int, cosine: bool, temperature: float) -> torch.Tensor:
@@ -107,7 +98,7 @@ class _MatchSoftmaxFn(torch.autograd.Function):
         m.B, m.M, m.D, m.mode, m.cosine = user.shape[0], item.shape[0], user.shape[1], mode, int(cosine)
         m.inv_temperature = 1.0 / float(temperature)
         m.u, m.u_stride, m.v, m.v_stride = _lib.ptr(user), user.stride(0), _lib.ptr(item), item.stride(0)
-        m.w = _lib.ptr(weights) if weights is not None else 0
+        m.w = _lib.opt_ptr(weights)
         m.lse, m.rmax, m.lsum, m.pos, m.scale = _lib.ptr(lse), _lib.ptr(rmax), _lib.ptr(lsum), _lib.ptr(pos), _lib.ptr(scale)
         if cosine:
             m.ru, m.rv = _lib.ptr(ru), _lib.ptr(rv)
@@ -128,10 +119,7 @@ class _MatchSoftmaxFn(torch.autograd.Function):
         m.loss, m.rank = _lib.ptr(loss), _lib.ptr(rank)
         if want_sim:
             m.sim, m.sim_stride = _lib.ptr(sim), sim.stride(0)
-        L = _lib.lib()
-        ws = _lib.workspace(L.tzr_match_softmax_workspace(C.byref(m)), dev)
-        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
-        _lib.check(L.tzr_match_softmax_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_match_softmax_fwd")
+        _lib.launch_ws("tzr_match_softmax", m, dev, "tzr_match_softmax_fwd")
         ctx.save_for_backward(user, item, weights, rows, scale, ru, rv)
         ctx.cfg = (mode, cosine, temperature)
         ctx.mark_non_differentiable(rank, sim)
@@ -149,7 +137,7 @@ class _MatchSoftmaxFn(torch.autograd.Function):
         _MatchSoftmaxFn._fill(m, user, item, weights, mode, cosine, temperature, (lse, rmax, lsum, pos, scale, ru, rv))
         m.grad_loss = _lib.ptr(g)
         m.du, m.du_stride, m.dv, m.dv_stride = _lib.ptr(du), du.stride(0), _lib.ptr(dv), dv.stride(0)
-        _lib.check(_lib.lib().tzr_match_softmax_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_match_softmax_bwd")
+        _lib.launch("tzr_match_softmax_bwd", m, dev)
         return du, dv, None, None, None, None, None
 
 
@@ -183,12 +171,6 @@ def label_attention_literal(interests: torch.Tensor, item: torch.Tensor, mask: t
     return torch.sum(torch.multiply(interest_weight, interests), dim=1)
 
 
-def _interests_ok(x: torch.Tensor) -> bool:
-    """[B, K, D] rows of one [B K, D] operand with a row stride"""
-    return bool(x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(1) % 4 == 0 and x.stride(1) >= x.shape[2]
-                and x.stride(0) == x.shape[1] * x.stride(1) and x.data_ptr() % 16 == 0)
-
-
 def label_attention_ok(interests: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, simi_pow: float) -> bool:
     """what tzr_label_attn_* takes: fp32 interests [B, K, D] whose B K rows have one stride (a multiple of 4 floats, 16-byte
     aligned; a column slice of a [B K, .] buffer is fine), item [M >= B, D] rows likewise, mask [B, K] bool contiguous; D % 4 == 0,
@@ -196,11 +178,11 @@ def label_attention_ok(interests: torch.Tensor, item: torch.Tensor, mask: torch.
     if interests.dim() != 3 or item.dim() != 2 or mask.dim() != 2:
         return False
     B, K, D = interests.shape
-    if (interests.device.type == "cpu") != (_lib.backend() == "emu") or item.device != interests.device or mask.device != interests.device:
+    if not _lib.takes(interests) or item.device != interests.device or mask.device != interests.device:
         return False
     if not (D % 4 == 0 and 4 <= D <= _lib.LABEL_ATTN_MAX_D and 1 <= K <= _lib.LABEL_ATTN_MAX_K and B >= 1 and simi_pow > 0):
         return False
-    return bool(_interests_ok(interests) and item.shape[0] >= B and _rows_ok(item, D) and mask.shape == (B, K) and mask.dtype == torch.bool
+    return bool(_lib.rows3_ok(interests) and item.shape[0] >= B and _lib.rows_ok(item, D) and mask.shape == (B, K) and mask.dtype == torch.bool
                 and mask.is_contiguous())
 
 
@@ -229,9 +211,7 @@ class _LabelAttentionFn(torch.autograd.Function):
         interests, item, mask, w = ctx.saved_tensors
         B, K, D = interests.shape
         dev = interests.device
-        g = gout.to(torch.float32)
-        if not _rows_ok(g, D):
-            g = g.contiguous()
+        g = _lib.rows16(gout.to(torch.float32))
         di = torch.empty(B, K, D, dtype=torch.float32, device=dev)
         dv = torch.zeros(item.shape, dtype=torch.float32, device=dev)
         _lib.check(_lib.lib().tzr_label_attn_bwd(_lib.ptr(g), g.stride(0), _lib.ptr(interests), interests.stride(1), _lib.ptr(item), item.stride(0),
@@ -260,6 +240,15 @@ FUSED_AMM_LOSS = True  # profiles/amm_loss: the fused form against the literal o
 
 def _div_no_nan(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
     return torch.where(den != 0, num / torch.where(den != 0, den, torch.ones_like(den)), torch.zeros_like(num))
+
+
+def _literal_grads(losses, gouts, inputs, needs, allow_unused: bool = False) -> tuple:
+    """the backward of a fused loss that is asked for a double backward (create_graph): the gradients of sum(loss * gout) over the
+    literal form's `losses` to the `inputs` that `needs` marks, None for the others, themselves differentiable"""
+    total = sum(l * g for l, g in zip(losses, gouts) if g is not None)
+    wanted = [t for t, need in zip(inputs, needs) if need]
+    got = iter(torch.autograd.grad(total, wanted, create_graph=True, allow_unused=allow_unused))
+    return tuple(next(got) if need else None for need in needs)
 
 
 def amm_terms(user_augment: torch.Tensor, item_augment: torch.Tensor, user_tower_emb: torch.Tensor, item_tower_emb: torch.Tensor,
@@ -295,16 +284,13 @@ def amm_loss_ok(user_aug: torch.Tensor, item_aug: torch.Tensor, user_emb: torch.
     B, D = user_aug.shape
     M = item_aug.shape[0]
     dev = user_aug.device
-    if (dev.type == "cpu") != (_lib.backend() == "emu") or any(t.device != dev for t in (item_aug, user_emb, item_emb)):
+    if not _lib.takes(dev) or any(t.device != dev for t in (item_aug, user_emb, item_emb)):
         return False
     if not (D % 4 == 0 and 4 <= D <= _lib.AMM_MAX_D and B >= 1 and M >= B and user_emb.shape[0] == B and item_emb.shape[0] == M):
         return False
-    if not all(_rows_ok(t, D) for t in (user_aug, item_aug, user_emb, item_emb)):
+    if not all(_lib.rows_ok(t, D) for t in (user_aug, item_aug, user_emb, item_emb)):
         return False
-    if weights is not None and not (weights.shape == (B,) and weights.dtype == torch.float32 and weights.is_contiguous()
-                                    and weights.device == dev):
-        return False
-    return True
+    return weights is None or _lib.packed_ok(weights, (B,), dev)
 
 
 class _AmmLossFn(torch.autograd.Function):
@@ -318,7 +304,7 @@ class _AmmLossFn(torch.autograd.Function):
         m.B, m.M, m.D, m.cosine, m.c_u, m.c_i = user_aug.shape[0], item_aug.shape[0], user_aug.shape[1], int(cosine), c_u, c_i
         m.ua, m.ua_stride, m.ia, m.ia_stride = _lib.ptr(user_aug), user_aug.stride(0), _lib.ptr(item_aug), item_aug.stride(0)
         m.ue, m.ue_stride, m.ie, m.ie_stride = _lib.ptr(user_emb), user_emb.stride(0), _lib.ptr(item_emb), item_emb.stride(0)
-        m.w = _lib.ptr(weights) if weights is not None else 0
+        m.w = _lib.opt_ptr(weights)
         m.rows, m.scale = _lib.ptr(rows), _lib.ptr(scale)
 
     @staticmethod
@@ -329,10 +315,7 @@ class _AmmLossFn(torch.autograd.Function):
         m = _lib.TzrAmmLoss()
         _AmmLossFn._fill(m, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i, rows, scale)
         m.loss = _lib.ptr(loss)
-        L = _lib.lib()
-        ws = _lib.workspace(L.tzr_amm_loss_workspace(C.byref(m)), dev)
-        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
-        _lib.check(L.tzr_amm_loss_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_amm_loss_fwd")
+        _lib.launch_ws("tzr_amm_loss", m, dev, "tzr_amm_loss_fwd")
         ctx.save_for_backward(user_aug, item_aug, user_emb, item_emb, weights, rows, scale)
         ctx.cfg = (cosine, c_u, c_i)
         ctx.set_materialize_grads(False)  # (no zero-filled gradient for a side nobody reads: a launch)
@@ -346,20 +329,17 @@ class _AmmLossFn(torch.autograd.Function):
         if g_u is None and g_i is None:
             return (None, None) + none
         if torch.is_grad_enabled():  # (create_graph: a double backward is coming)
-            lu, li = amm_loss_literal(user_aug, item_aug, user_emb, item_emb, cosine, c_u, c_i, weights)
-            total = sum(l * g for l, g in ((lu, g_u), (li, g_i)) if g is not None)
-            wanted = [t for t, need in zip((user_aug, item_aug), ctx.needs_input_grad) if need]
-            grads = iter(torch.autograd.grad(total, wanted, create_graph=True))
-            return tuple(next(grads) if need else None for need in ctx.needs_input_grad[:2]) + none
+            losses = amm_loss_literal(user_aug, item_aug, user_emb, item_emb, cosine, c_u, c_i, weights)
+            return _literal_grads(losses, (g_u, g_i), (user_aug, item_aug), ctx.needs_input_grad[:2]) + none
         dev = user_aug.device
         g_u, g_i = (None if g is None else g.to(torch.float32) for g in (g_u, g_i))
         dua = torch.empty(user_aug.shape, dtype=torch.float32, device=dev)
         dia = torch.empty(item_aug.shape, dtype=torch.float32, device=dev)
         m = _lib.TzrAmmLoss()
         _AmmLossFn._fill(m, user_aug, item_aug, user_emb, item_emb, weights, cosine, c_u, c_i, rows, scale)
-        m.grad_u, m.grad_i = (_lib.ptr(g_u) if g_u is not None else 0), (_lib.ptr(g_i) if g_i is not None else 0)
+        m.grad_u, m.grad_i = _lib.opt_ptr(g_u), _lib.opt_ptr(g_i)
         m.dua, m.dua_stride, m.dia, m.dia_stride = _lib.ptr(dua), dua.stride(0), _lib.ptr(dia), dia.stride(0)
-        _lib.check(_lib.lib().tzr_amm_loss_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_amm_loss_bwd")
+        _lib.launch("tzr_amm_loss_bwd", m, dev)
         return (dua, dia) + none
 
 

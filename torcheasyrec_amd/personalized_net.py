@@ -3,7 +3,7 @@
 main embedding by a gate over [domain | main.detach()], `PPNet` runs per task a stack of Linear -> activation -> times a gate
 over [uia | main.detach()] -> dropout.  Everything behind the three GEMMs of a (task, layer) -- two bias adds, the ReLU, the
 sigmoid, the scale by gamma and the multiply, and in the backward the two bias gradients -- is one launch per PPNet level for
-all tasks, and one for EPNet (dense.gate_scale, csrc/gate_scale.hip)."""
+all tasks, and one for EPNet (gate_ops.gate_scale, csrc/gate_scale.hip)."""
 from __future__ import annotations
 
 from typing import List, Optional, Union
@@ -11,13 +11,14 @@ from typing import List, Optional, Union
 import torch
 from torch import nn
 
-from .dlrm import _activation, _on_emulator
+from . import _lib
+from .dlrm import _activation
 
 FUSED_GATE_SCALE = True  # A/B switch: False = the reference's literal form, op by op
 
 
 def _fusable(x: torch.Tensor) -> bool:
-    return bool(FUSED_GATE_SCALE and x.dim() == 2 and (x.is_cuda or _on_emulator()))
+    return bool(FUSED_GATE_SCALE and x.dim() == 2 and (x.is_cuda or _lib.emulated()))
 
 
 class GateNU(nn.Module):
@@ -31,7 +32,7 @@ class GateNU(nn.Module):
         return self._output_dim
 
     def pre_sigmoid(self, x: torch.Tensor) -> torch.Tensor:
-        """relu(Linear(x)) times the second layer's weight, WITHOUT its bias: the `g` of dense.gate_scale"""
+        """relu(Linear(x)) times the second layer's weight, WITHOUT its bias: the `g` of gate_ops.gate_scale"""
         first, second = self.dense_layers[0], self.dense_layers[2]
         return nn.functional.linear(torch.relu(first(x)), second.weight)
 
@@ -52,9 +53,9 @@ class EPNet(nn.Module):
     def forward(self, main_emb: torch.Tensor, domain_emb: torch.Tensor) -> torch.Tensor:
         gate_input = torch.cat([domain_emb, main_emb.detach()], dim=-1)
         if _fusable(main_emb) and main_emb.dtype == torch.float32 and main_emb.shape[0] > 0:
-            from .dense import _rows16, gate_scale, gate_scale_ok
+            from .gate_ops import gate_scale, gate_scale_ok
 
-            z, g = _rows16(main_emb), self.gate_nu.pre_sigmoid(gate_input)
+            z, g = _lib.rows16(main_emb), self.gate_nu.pre_sigmoid(gate_input)
             bg = [self.gate_nu.dense_layers[2].bias]
             if gate_scale_ok([z], [g], [None], bg):  # one launch: identity, no bias on the main embedding
                 return gate_scale([z], [None], [g], bg, self.gate_nu._gamma, relu=False)[0]
@@ -111,7 +112,7 @@ class PPNet(nn.Module):
             idx = [i * self.len_hidden + j for i in range(self.num_task)]
             outs = None
             if fused:
-                from .dense import gate_scale, gate_scale_ok
+                from .gate_ops import gate_scale, gate_scale_ok
 
                 zs = [nn.functional.linear(x, self.linears[k].weight) for x, k in zip(inputs, idx)]  # the GEMMs without bias
                 gs = [self.gate_nus[k].pre_sigmoid(gate_input) for k in idx]

@@ -2,7 +2,7 @@
 value (tzrec/modules/extraction_net.py:20-139): `expert_num_per_task` expert MLPs per task over that task's input, `share_num`
 shared ones over the shared input; task gate t = Linear + softmax over [its own experts | the shared ones] of its input, the
 shared gate (absent on the last level) over [all task experts in task order | the shared ones] of the shared input.  The
-gate-and-mix step of the whole level is one launch per direction (dense.cgc_mix, csrc/gate_mix.hip)."""
+gate-and-mix step of the whole level is one launch per direction (gate_ops.cgc_mix, csrc/gate_mix.hip)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
@@ -10,7 +10,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from .dlrm import MLP, OutputLinear, _on_emulator
+from . import _lib
+from .dlrm import MLP, OutputLinear
 
 FUSED_CGC_MIX = True  # A/B switch: False = the reference's stack / softmax / batched-matmul form per gate
 
@@ -54,8 +55,8 @@ class ExtractionNet(nn.Module):
         if self._shared_gate is not None:
             logits.append(self._shared_gate(shared_expert_fea))
         outs = None
-        if FUSED_CGC_MIX and shared_expert_fea.dim() == 2 and (shared_expert_fea.is_cuda or _on_emulator()):
-            from .dense import cgc_mix, cgc_mix_ok
+        if FUSED_CGC_MIX and shared_expert_fea.dim() == 2 and (shared_expert_fea.is_cuda or _lib.emulated()):
+            from .gate_ops import cgc_mix, cgc_mix_ok
 
             if cgc_mix_ok(logits, experts, self._sels):  # every gate of the level in one launch per direction, nothing stacked
                 outs = cgc_mix(logits, experts, self._sels)

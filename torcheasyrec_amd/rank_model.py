@@ -14,8 +14,9 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
+from . import _lib
 from .config import PipelineSpec
-from .dlrm import MLP, OutputLinear, _on_emulator
+from .dlrm import MLP, OutputLinear
 from .embedding import SparseOptimizerConfig
 from .embedding_group import Batch, EmbeddingGroup
 from .interaction import CIN, Cross, CrossV2, FactorizationMachine, dot_interaction
@@ -259,8 +260,8 @@ class MMoE(nn.Module):
     def forward(self, input: torch.Tensor):
         outs = [e(input) for e in self.expert_mlps]
         logits = [self.gate_finals[i](self.gate_mlps[i](input) if self.has_gate_mlp else input) for i in range(self.num_task)]
-        if FUSED_MOE_MIX and input.dim() == 2 and (input.is_cuda or _on_emulator()):
-            from .dense import moe_mix, moe_mix_ok
+        if FUSED_MOE_MIX and input.dim() == 2 and (input.is_cuda or _lib.emulated()):
+            from .gate_ops import moe_mix, moe_mix_ok
 
             if moe_mix_ok(logits, outs):  # softmax + mixing of every task in one launch per direction, nothing stacked (csrc/gate_mix.hip)
                 return moe_mix(logits, outs)
@@ -512,7 +513,7 @@ class ConfigDBMTL(MultiTaskRankModel):
     output); the relation output of a tower without one is its `mlp` output.  `task_mlps` and `relation_mlps` are ModuleDicts
     keyed by tower name, `task_outputs` a ModuleList, as in the reference.
 
-    All relation MLPs of the model run in one launch forward and two backward (dense.relation_chain, csrc/relation_chain.hip)
+    All relation MLPs of the model run in one launch forward and two backward (gate_ops.relation_chain, csrc/relation_chain.hip)
     with no concat tensor; the literal form runs with FUSED_RELATION_CHAIN off, with a relation MLP that is not plain Linear +
     bias + ReLU, with a shape outside the kernel's limits, or off the GPU / the emulator.
 
@@ -622,11 +623,11 @@ class ConfigDBMTL(MultiTaskRankModel):
         names = [name for name, _ in self._towers]
         mlps = [self.relation_mlps[n] if n in self.relation_mlps else None for n in names]
         x0 = task_net[0]
-        if FUSED_RELATION_CHAIN and any(m is not None for m in mlps) and x0.dim() == 2 and (x0.is_cuda or _on_emulator()) \
+        if FUSED_RELATION_CHAIN and any(m is not None for m in mlps) and x0.dim() == 2 and (x0.is_cuda or _lib.emulated()) \
                 and all(m is None or m._plain for m in mlps):
-            from .dense import _rows16, relation_chain, relation_chain_ok
+            from .gate_ops import relation_chain, relation_chain_ok
 
-            xs = [_rows16(x) for x in task_net]
+            xs = [_lib.rows16(x) for x in task_net]
             for i in range(len(xs)):  # (towers that read one tensor: one object, as they came)
                 for j in range(i):
                     if task_net[i] is task_net[j]:

@@ -10,7 +10,6 @@ backward run `distill_losses_literal`, the reference's `feature_based_sim` and `
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Sequence
 
 import torch
@@ -22,7 +21,7 @@ from .config import PipelineSpec
 from .dlrm import MLP
 from .embedding_group import Batch
 from .losses import Loss, output_to_prediction
-from .match import _div_no_nan, _rows_ok  # (the float4 row operand check and the reference's div_no_nan, shared with the match losses)
+from .match import _div_no_nan, _literal_grads  # (the reference's div_no_nan and the double-backward path, shared with the match losses)
 from .rank_model import RankModel, mlp_kwargs
 
 FUSED_DISTILL_LOSS = True  # profiles/distill_loss: the fused form against the literal one, without and with sample weights
@@ -70,21 +69,18 @@ def distill_losses_ok(light_feats: Sequence[torch.Tensor], booster_feats: Sequen
         return False
     B, dev = logits_light.shape[0], logits_light.device
     Cn = 1 if logits_light.dim() == 1 else logits_light.shape[1]
-    if (dev.type == "cpu") != (_lib.backend() == "emu") or B < 1 or not 1 <= Cn <= _lib.DISTILL_MAX_C:
+    if not _lib.takes(dev) or B < 1 or not 1 <= Cn <= _lib.DISTILL_MAX_C:
         return False
     for t in (logits_light, logits_booster):
         if not (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev):
             return False
     for l, b in zip(light_feats, booster_feats):
-        if not (l.dim() == 2 and _rows_ok(l, l.shape[1]) and _rows_ok(b, l.shape[1]) and l.shape[0] == b.shape[0] == B
+        if not (l.dim() == 2 and _lib.rows_ok(l) and _lib.rows_ok(b, l.shape[1]) and l.shape[0] == b.shape[0] == B
                 and l.device == dev and b.device == dev):
             return False
         if not (l.shape[1] % 4 == 0 and 4 <= l.shape[1] <= _lib.DISTILL_MAX_W):
             return False
-    if weights is not None and not (weights.shape == (B,) and weights.dtype == torch.float32 and weights.is_contiguous()
-                                    and weights.device == dev and logits_light.dim() == 1):
-        return False
-    return True
+    return weights is None or (_lib.packed_ok(weights, (B,), dev) and logits_light.dim() == 1)
 
 
 class _DistillLossFn(torch.autograd.Function):
@@ -102,7 +98,7 @@ class _DistillLossFn(torch.autograd.Function):
             m.W[p] = l.shape[1]
             m.light[p], m.light_stride[p], m.booster[p], m.booster_stride[p] = _lib.ptr(l), l.stride(0), _lib.ptr(b), b.stride(0)
         m.logits_light, m.logits_booster = _lib.ptr(logits_light), _lib.ptr(logits_booster)
-        m.w = _lib.ptr(weights) if weights is not None else 0
+        m.w = _lib.opt_ptr(weights)
         m.scale = _lib.ptr(scale)
 
     @staticmethod
@@ -114,10 +110,7 @@ class _DistillLossFn(torch.autograd.Function):
         m = _lib.TzrDistillLoss()
         _DistillLossFn._fill(m, logits_light, logits_booster, weights, cosine, lights, boosters, scale)
         m.loss = _lib.ptr(loss)
-        L = _lib.lib()
-        ws = _lib.workspace(L.tzr_distill_loss_workspace(C.byref(m)), dev)
-        m.ws, m.ws_bytes = _lib.ptr(ws), ws.numel()
-        _lib.check(L.tzr_distill_loss_fwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_distill_loss_fwd")
+        _lib.launch_ws("tzr_distill_loss", m, dev, "tzr_distill_loss_fwd")
         ctx.save_for_backward(logits_light, logits_booster, weights, scale, *feats)
         ctx.cfg = (cosine, P)
         ctx.set_materialize_grads(False)  # (no zero-filled gradient for a term nobody reads: a launch)
@@ -135,11 +128,8 @@ class _DistillLossFn(torch.autograd.Function):
             return (None,) * 5 + none + none
         if torch.is_grad_enabled():  # (create_graph: a double backward is coming)
             sims, hint = distill_losses_literal(lights, boosters, logits_light, logits_booster, cosine, weights)
-            total = sum(l * g for l, g in zip(sims + (hint,), grads) if g is not None)
-            wanted = [t for t, need in zip((logits_light,) + tuple(lights), (need_ll,) + tuple(need_l)) if need]
-            got = iter(torch.autograd.grad(total, wanted, create_graph=True, allow_unused=True))
-            d_ll = next(got) if need_ll else None
-            return (d_ll, None, None, None, None) + tuple(next(got) if need else None for need in need_l) + none
+            got = _literal_grads(sims + (hint,), grads, (logits_light,) + tuple(lights), (need_ll,) + tuple(need_l), allow_unused=True)
+            return (got[0], None, None, None, None) + got[1:] + none
         dev = logits_light.device
         grads = [None if g is None else g.to(torch.float32) for g in grads]
         m = _lib.TzrDistillLoss()
@@ -149,12 +139,11 @@ class _DistillLossFn(torch.autograd.Function):
             want = need_l[p] and grads[p] is not None
             d = torch.empty(lights[p].shape, dtype=torch.float32, device=dev) if want else None
             d_lights.append(d)
-            m.grad_sim[p] = _lib.ptr(grads[p]) if grads[p] is not None else 0
+            m.grad_sim[p] = _lib.opt_ptr(grads[p])
             m.dlight[p], m.dlight_stride[p] = (_lib.ptr(d), d.stride(0)) if want else (0, 0)
         d_ll = torch.empty_like(logits_light) if need_ll and grads[P] is not None else None
-        m.grad_hint = _lib.ptr(grads[P]) if grads[P] is not None else 0
-        m.dlogits_light = _lib.ptr(d_ll) if d_ll is not None else 0
-        _lib.check(_lib.lib().tzr_distill_loss_bwd(C.byref(m), _lib.stream_ptr(dev)), "tzr_distill_loss_bwd")
+        m.grad_hint, m.dlogits_light = _lib.opt_ptr(grads[P]), _lib.opt_ptr(d_ll)
+        _lib.launch("tzr_distill_loss_bwd", m, dev)
         return (d_ll, None, None, None, None) + tuple(d_lights) + none
 
 

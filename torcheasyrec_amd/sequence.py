@@ -643,20 +643,12 @@ JAGGED_ENCODER_MAX_LEN = 2048  # (JE_MAXLEN: tzr_jagged_dot_attn_* keep a sample
 JAGGED_ENCODER_MAX_DIM = 256  # (JE_MAXDIM: one lane per float4 piece of a row)
 
 
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """[n, D] rows as the kernels take them: unit column stride, row stride a multiple of 4 floats, 16-byte aligned (a column
-    slice of a wider tensor passes as it is), else a contiguous copy"""
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous()
-
-
 class _JaggedDotAttnFn(torch.autograd.Function):
     """out_b = sum_n softmax_n(k_n . q_b) k_n over sample b's rows, one node: tzr_jagged_dot_attn_fwd / _bwd"""
 
     @staticmethod
     def forward(ctx, values, query, offsets, max_len):
-        values, query = _rows(values), _rows(query)
+        values, query = _lib.rows16(values), _lib.rows16(query)
         N, D = values.shape
         B = offsets.numel() - 1
         dev = values.device
@@ -675,7 +667,7 @@ class _JaggedDotAttnFn(torch.autograd.Function):
         N, D = values.shape
         B = offsets.numel() - 1
         dev = values.device
-        gout = _rows(gout)
+        gout = _lib.rows16(gout)
         dkv = torch.empty(max(N, 1), D, dtype=torch.float32, device=dev)
         dq = torch.empty(max(B, 1), D, dtype=torch.float32, device=dev)
         _lib.check(_lib.lib().tzr_jagged_dot_attn_bwd(_lib.ptr(gout), gout.stride(0) if B else D, _lib.ptr(p), _lib.ptr(values),
@@ -690,7 +682,7 @@ class _JaggedPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, values, offsets, max_len, mode):
-        values = _rows(values)
+        values = _lib.rows16(values)
         N, D = values.shape
         B = offsets.numel() - 1
         out = torch.empty(max(B, 1), D, dtype=torch.float32, device=values.device)
@@ -704,7 +696,7 @@ class _JaggedPoolFn(torch.autograd.Function):
     def backward(ctx, gout):
         (offsets,) = ctx.saved_tensors
         N, D, max_len, mode = ctx.cfg
-        gout = _rows(gout)
+        gout = _lib.rows16(gout)
         B = offsets.numel() - 1
         dkv = torch.empty(max(N, 1), D, dtype=torch.float32, device=gout.device)
         _lib.check(_lib.lib().tzr_jagged_pool_bwd(_lib.ptr(gout), gout.stride(0) if B else D, D, _lib.ptr(offsets), B, N, max_len, mode,

@@ -1184,7 +1184,7 @@ def pack_dense_grads(grads: Sequence[torch.Tensor]) -> torch.Tensor:
     from .dense import materialize_pending, pack_gradients
 
     grads = list(grads)
-    if grads and (grads[0].is_cuda or _lib.backend() == "emu"):
+    if grads and (grads[0].is_cuda or _lib.emulated(load=True)):
         flat = pack_gradients(grads)
         if flat is not None:
             return flat

@@ -16,8 +16,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .dlrm import MLP, _on_emulator
-from .interaction import _row_stride, _rows, _traced
+from .dlrm import MLP
+from .interaction import _traced
 
 FUSED_WUKONG = True  # A/B switch: False = the reference's literal forward (permute, matmul, LayerNorm, concat, add, op by op)
 WUKONG_MAX_F, WUKONG_MAX_D = 64, 128  # WK_MAXF (F, Fo and k), WK_MAXD of csrc/wukong.hip
@@ -31,13 +31,13 @@ class _WukongFmFn(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
         B, F, D = x.shape
         k = weight.shape[1]
-        x2 = _rows(x.reshape(B, F * D))
+        x2 = _lib.scalar_rows(x.reshape(B, F * D))
         weight, gamma, beta = weight.contiguous(), gamma.contiguous(), beta.contiguous()
         dev = x.device
         out = torch.empty(B, F * k, dtype=torch.float32, device=dev)
         stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
-        rc = _lib.lib().tzr_wukong_fm_fwd(_lib.ptr(x2), _row_stride(x2), _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta), eps, B, F, D, k,
-                                          _lib.ptr(out), F * k, _lib.ptr(stats), _lib.stream_ptr(dev))
+        rc = _lib.lib().tzr_wukong_fm_fwd(_lib.ptr(x2), _lib.scalar_row_stride(x2), _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta),
+                                          eps, B, F, D, k, _lib.ptr(out), F * k, _lib.ptr(stats), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_wukong_fm_fwd")
         ctx.save_for_backward(x2, weight, gamma, stats)
         ctx.dims = (B, F, D, k)
@@ -48,14 +48,14 @@ class _WukongFmFn(torch.autograd.Function):
         x2, weight, gamma, stats = ctx.saved_tensors
         B, F, D, k = ctx.dims
         dev = x2.device
-        gout = _rows(gout)
+        gout = _lib.scalar_rows(gout)
         gx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
         dp = torch.empty(3 * F * k, dtype=torch.float32, device=dev)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_wukong_fm_bwd_workspace(B, F, D, k), dev)
-        rc = lib.tzr_wukong_fm_bwd(_lib.ptr(gout), _row_stride(gout), _lib.ptr(x2), _row_stride(x2), _lib.ptr(weight), _lib.ptr(gamma),
-                                   _lib.ptr(stats), B, F, D, k, _lib.ptr(gx), F * D, _lib.ptr(dp), _lib.ptr(ws), ws.numel(),
-                                   _lib.stream_ptr(dev))
+        rc = lib.tzr_wukong_fm_bwd(_lib.ptr(gout), _lib.scalar_row_stride(gout), _lib.ptr(x2), _lib.scalar_row_stride(x2),
+                                   _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(stats), B, F, D, k, _lib.ptr(gx), F * D,
+                                   _lib.ptr(dp), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_wukong_fm_bwd")
         n = F * k
         return gx, dp[:n].view(F, k), dp[n:2 * n], dp[2 * n:], None
@@ -72,15 +72,15 @@ class _WukongMixFn(torch.autograd.Function):
         Fl = wl.shape[1]
         Ff = fm.shape[1] // D
         Fo = Ff + Fl
-        x2, fm = _rows(x.reshape(B, F * D)), _rows(fm)
+        x2, fm = _lib.scalar_rows(x.reshape(B, F * D)), _lib.scalar_rows(fm)
         wl, gamma, beta = wl.contiguous(), gamma.contiguous(), beta.contiguous()
         wr = None if wr is None else wr.contiguous()
         dev = x.device
         out = torch.empty(B, Fo, D, dtype=torch.float32, device=dev)
         stats = torch.empty(B, Fo, 2, dtype=torch.float32, device=dev)
-        rc = _lib.lib().tzr_wukong_mix_fwd(_lib.ptr(x2), _row_stride(x2), _lib.ptr(fm), _row_stride(fm), _lib.ptr(wl), _lib.ptr(wr),
-                                           _lib.ptr(gamma), _lib.ptr(beta), eps, B, F, D, Ff, Fl, _lib.ptr(out), Fo * D, _lib.ptr(stats),
-                                           _lib.stream_ptr(dev))
+        rc = _lib.lib().tzr_wukong_mix_fwd(_lib.ptr(x2), _lib.scalar_row_stride(x2), _lib.ptr(fm), _lib.scalar_row_stride(fm),
+                                           _lib.ptr(wl), _lib.ptr(wr), _lib.ptr(gamma), _lib.ptr(beta), eps, B, F, D, Ff, Fl,
+                                           _lib.ptr(out), Fo * D, _lib.ptr(stats), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_wukong_mix_fwd")
         ctx.save_for_backward(x2, fm, wl, gamma, stats, *(() if wr is None else (wr,)))
         ctx.dims = (B, F, D, Ff, Fl)
@@ -93,15 +93,15 @@ class _WukongMixFn(torch.autograd.Function):
         B, F, D, Ff, Fl = ctx.dims
         Fo = Ff + Fl
         dev = x2.device
-        gout = _rows(gout.reshape(B, Fo * D))
+        gout = _lib.scalar_rows(gout.reshape(B, Fo * D))
         gx = torch.empty(B, F, D, dtype=torch.float32, device=dev)
         gfm = torch.empty(B, Ff * D, dtype=torch.float32, device=dev)
         dp = torch.empty(F * Fo + F * Fl + 2 * D, dtype=torch.float32, device=dev)
         lib = _lib.lib()
         ws = _lib.workspace(lib.tzr_wukong_mix_bwd_workspace(B, F, D, Ff, Fl), dev)
-        rc = lib.tzr_wukong_mix_bwd(_lib.ptr(gout), _row_stride(gout), _lib.ptr(x2), _row_stride(x2), _lib.ptr(fm), _row_stride(fm), _lib.ptr(wl),
-                                    _lib.ptr(wr), _lib.ptr(gamma), _lib.ptr(stats), B, F, D, Ff, Fl, _lib.ptr(gx), F * D, _lib.ptr(gfm), Ff * D,
-                                    _lib.ptr(dp), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        rc = lib.tzr_wukong_mix_bwd(_lib.ptr(gout), _lib.scalar_row_stride(gout), _lib.ptr(x2), _lib.scalar_row_stride(x2), _lib.ptr(fm),
+                                    _lib.scalar_row_stride(fm), _lib.ptr(wl), _lib.ptr(wr), _lib.ptr(gamma), _lib.ptr(stats),
+                                    B, F, D, Ff, Fl, _lib.ptr(gx), F * D, _lib.ptr(gfm), Ff * D, _lib.ptr(dp), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "tzr_wukong_mix_bwd")
         a, b = F * Fo, F * Fo + F * Fl
         return gx, gfm, dp[a:b].view(F, Fl), (None if wr is None else dp[:a].view(F, Fo)), dp[b:b + D], dp[b + D:], None
@@ -111,7 +111,7 @@ def wukong_ok(x: torch.Tensor, *params: torch.Tensor) -> bool:
     """the kernels take `x` [B, F, D] with these parameters"""
     return bool(x.dim() == 3 and x.dtype == torch.float32 and x.shape[0] > 0 and not _traced(x)
                 and 1 <= x.shape[1] <= WUKONG_MAX_F and 1 <= x.shape[2] <= WUKONG_MAX_D
-                and all(p.dtype == torch.float32 for p in params) and (x.is_cuda or _on_emulator()))
+                and all(p.dtype == torch.float32 for p in params) and (x.is_cuda or _lib.emulated()))
 
 
 class LinearCompressBlock(nn.Module):
