@@ -46,11 +46,16 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
     _lib.use_library(emu_path)
     dev = torch.device("cpu")
     torch.manual_seed(7)  # same dense init everywhere (also broadcast by the module)
-    rows = [5000, 300, 3, 4, 17, 1000, 2, 64][: 6 if mode == "jagged" else 8]
+    jagged = mode in ("jagged", "jagged_mean")
+    rows = [5000, 300, 3, 4, 17, 1000, 2, 64][: 6 if jagged else 8]
     F = len(rows)
     keys = [f"cat_{i}" for i in range(F)]
     lr = 0.05
     tables = criteo_tables(rows, init="seeded")[:F]
+    if mode == "jagged_mean":  # every second table mean-pooled: a table-wise one, a replicated one and a row-wise one
+        for cfg in tables[1::2]:
+            cfg.pooling = "mean"
+    poolings = [cfg.pooling for cfg in tables]
     # rows > 100 -> row-wise shards, the small ones are replicated (data_parallel)
     # ... and one table is pinned table-wise (whole table on one rank) like a tzrec embedding_constraint
     if planner:  # placement chosen by the DP planner (every rank computes the same plan)
@@ -69,7 +74,7 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
                             capacity_factor=0.5 if exchange == "overflow" else 1.5)
         if exchange == "overflow":  # no slack: some destination gets more than half the even share
             model.ebc.capacity_slack = 0
-        if mode == "jagged":  # ragged bags (0..3 ids): slices sized for 1.5 ids per bag (0.4 in the overflow case)
+        if jagged:  # ragged bags (0..3 ids): slices sized for 1.5 ids per bag (0.4 in the overflow case)
             model.ebc.capacity_bag_len = 0.4 if exchange == "overflow" else 1.5
     kinds = {n: p["sharding_type"] for n, p in model.ebc.plan().items()}
     assert "data_parallel" in kinds.values() and kinds["cat_1_emb"] == "table_wise"
@@ -78,7 +83,7 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
     Bl = Bg // world
     dense_g, kjt_g, label_g = synthetic_batch(2, Bg, rows)
     rng = np.random.default_rng(5)
-    if mode == "jagged":  # ragged bags incl. empties, per-id weights
+    if jagged:  # ragged bags incl. empties, per-id weights
         lens = rng.integers(0, 4, size=F * Bg).astype(np.int32)
         vals = np.concatenate([rng.integers(0, rows[f], size=int(lens[f * Bg:(f + 1) * Bg].sum())) for f in range(F)]).astype(np.int64)
         wts = rng.uniform(0.5, 1.5, size=len(vals)).astype(np.float32)
@@ -139,7 +144,7 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
         cfg.init_fn(w)
         full.append(w)
     psw = kjt.weights_or_none()
-    blocks = [b.clone().requires_grad_(True) for b in orc.pooled_lookup(full, ["sum"] * F, kjt.values(), kjt.lengths(), Bl, psw)]
+    blocks = [b.clone().requires_grad_(True) for b in orc.pooled_lookup(full, poolings, kjt.values(), kjt.lengths(), Bl, psw)]
     cpu_params = [p.detach().clone().requires_grad_(True) for p in model.dense_parameters()]
     it = iter(cpu_params)
     p = {"dim": 16, "dense_mlp": [(next(it), next(it)) for _ in range(2)],
@@ -156,7 +161,7 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
         dist.all_reduce(g)
         torch.testing.assert_close(q.grad, g / world, rtol=1e-4, atol=1e-6)
     # per-lookup gradients of my samples -> rank 0 assembles the global sparse update
-    lg = [orc.lookup_grads([grads[f].numpy()], kjt.lengths().numpy()[f * Bl:(f + 1) * Bl], Bl, ["sum"],
+    lg = [orc.lookup_grads([grads[f].numpy()], kjt.lengths().numpy()[f * Bl:(f + 1) * Bl], Bl, [poolings[f]],
                            None if psw is None else psw.numpy()[int(orc.lengths_to_offsets(kjt.lengths().numpy())[f * Bl]):int(orc.lengths_to_offsets(kjt.lengths().numpy())[(f + 1) * Bl])])
           for f in range(F)]
     loff = orc.lengths_to_offsets(kjt.lengths().numpy())
@@ -187,7 +192,8 @@ def _worker(rank, world, init_file, emu_path, mode, result_dir, via_step=False, 
 
 
 @pytest.mark.parametrize("mode,via_step,planner", [("uniform1", False, False), ("jagged", False, False),
-                                                   ("uniform1", True, False), ("jagged", True, True)])
+                                                   ("uniform1", True, False), ("jagged", True, True),
+                                                   ("jagged_mean", False, False), ("jagged_mean", True, False)])
 def test_sharded_dlrm_world2(emu_path, mode, via_step, planner):
     world = 2
     with tempfile.TemporaryDirectory() as d:
@@ -200,7 +206,8 @@ def test_sharded_dlrm_world2(emu_path, mode, via_step, planner):
                                                           (4, "uniform1", True, "capacity"), (4, "uniform1", False, "overflow"),
                                                           (8, "uniform1", True, "capacity"), (8, "uniform1", True, "overflow"),
                                                           (2, "jagged", False, "capacity"), (2, "jagged", True, "capacity"),
-                                                          (2, "jagged", False, "overflow"), (4, "jagged", True, "overflow")])
+                                                          (2, "jagged", False, "overflow"), (4, "jagged", True, "overflow"),
+                                                          (2, "jagged_mean", False, "capacity"), (2, "jagged_mean", True, "capacity")])
 def test_sharded_dlrm_capacity_exchange(emu_path, world, mode, via_step, exchange):
     """Capacity-bounded exchange (fixed message slices, one ids all-to-all, no counts through the host): same
     logits / gradients / shards as the unsharded oracle; a batch that does not fit is redone exactly by all ranks."""
