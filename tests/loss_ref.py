@@ -18,6 +18,10 @@ FOCAL_PARAMS = ((2.0, 0.5), (0.0, 0.25), (1.5, 0.75))
 SOFTMAX_C = (2, 3, 8, 9, 64, 65, 130)
 SOFTMAX_B = (1, 257)
 JRC_B = (1, 2, 64, 65, 300, 1025)
+# sorted sessions whose heads fall on lane 63 and lane 0 of a wave, that end on a wave boundary, span 2 to 5 waves and a workgroup
+# boundary, and whose end the kernel's binary search finds inside the array and at its end (tests/test_losses.py asserts each)
+JRC_PLACED_SIZES = (63, 1, 64, 65, 127, 1, 128, 63, 129, 1, 1, 62, 256, 257, 3)
+SATURATED_X = (17.0, -17.0, 88.0, -88.0, 104.0, -104.0, 1e4, -1e4, 0.0, -0.0, 1e-30, 3e38, -3e38)
 
 
 def pointwise_inputs(B: int, scale: float, seed: int = 0):
@@ -43,16 +47,43 @@ def jrc_inputs(B: int, sessions: int, scale: float = 1.0, seed: int = 0):
     return x, y, sid
 
 
+def jrc_placed_inputs(scale: float, shuffled: bool, sizes=JRC_PLACED_SIZES):
+    """sessions of `sizes` rows with ascending ids, in sorted row order or shuffled"""
+    sizes = torch.tensor(sizes)
+    B = int(sizes.sum())
+    x, y, _ = jrc_inputs(B, len(sizes), scale)
+    sid = torch.repeat_interleave(torch.arange(len(sizes)) * 7919 - 3, sizes)
+    if shuffled:
+        perm = torch.randperm(B, generator=torch.Generator().manual_seed(B + int(scale)))
+        sid = sid[perm]
+    return x, y, sid
+
+
+def masked_softmax_inputs(B: int, C: int, seed: int = 0):
+    """(logits, labels, mask): softmax_inputs with classes masked out by -inf, at least one per row and never the label's; for C > 64
+    also class 64 + row % (C - 64), which a lane of the wave kernel meets on its second trip; row 0's only unmasked class is its label"""
+    x, y = softmax_inputs(B, C, seed)
+    g = torch.Generator().manual_seed(99 * B + C + seed)
+    mask = torch.rand(B, C, generator=g) < 0.3
+    rows = torch.arange(B)
+    mask[rows, (y + 1 + rows % (C - 1)) % C] = True
+    if C > 64:
+        mask[rows, 64 + rows % (C - 64)] = True
+    mask[0] = True
+    mask[rows, y] = False
+    return x.masked_fill(mask, float("-inf")), y, mask
+
+
 def weight_inputs(B: int, seed: int = 0):
     """a positive weight column and an indicator label"""
     g = torch.Generator().manual_seed(555 + B + seed)
     return (torch.rand(B, generator=g) * 2 + 0.1).float(), (torch.rand(B, generator=g) < 0.5).to(torch.int64)
 
 
-def row_weights(B, weight=None, space_label=None, in_w=1.0, out_w=1.0):
-    w = torch.ones(B, dtype=torch.float64) if weight is None else weight.double()
+def row_weights(B, weight=None, space_label=None, in_w=1.0, out_w=1.0, dtype=torch.float64):
+    w = torch.ones(B, dtype=dtype) if weight is None else weight.to(dtype)
     if space_label is not None:
-        w = w * torch.where(space_label.double() > 0, torch.tensor(float(in_w), dtype=torch.float64), torch.tensor(float(out_w), dtype=torch.float64))
+        w = w * torch.where(space_label.to(dtype) > 0, torch.tensor(float(in_w), dtype=dtype), torch.tensor(float(out_w), dtype=dtype))
     return w
 
 
@@ -67,18 +98,18 @@ def bce_rows(x, y, label_smoothing=0.0):
     y = y.to(torch.float32)  # the reference smooths the float32 label (rank_model.py:235-239) whatever the logits' precision
     if label_smoothing > 0:
         y = y * (1.0 - label_smoothing) + 0.5 * label_smoothing
-    return F.binary_cross_entropy_with_logits(x, y.double(), reduction="none")
+    return F.binary_cross_entropy_with_logits(x, y.to(x.dtype), reduction="none")
 
 
 def focal_rows(x, y, gamma=2.0, alpha=0.5):
-    y = y.double()
+    y = y.to(x.dtype)
     p, omp = torch.sigmoid(x), torch.sigmoid(-x)
     f = (alpha * y * torch.pow(omp, gamma) + (1 - alpha) * (1 - y) * torch.pow(p, gamma)).detach()
     return f * F.binary_cross_entropy_with_logits(x, y, reduction="none")
 
 
 def l2_rows(x, y):
-    return F.mse_loss(x, y.double(), reduction="none")
+    return F.mse_loss(x, y.to(x.dtype), reduction="none")
 
 
 def softmax_rows(x, y, label_smoothing=0.0):
@@ -104,10 +135,20 @@ ROWS = {"binary_cross_entropy": bce_rows, "binary_focal_loss": focal_rows, "l2_l
         "softmax_cross_entropy": softmax_rows, "jrc_loss": jrc_rows}
 
 
-def loss_and_grad(kind, logits, labels, *args, weight=None, space_label=None, in_w=1.0, out_w=1.0, task_weight=1.0, **kw):
-    """(loss, d loss / d logits), both float64, of float32 (or float64) logits"""
-    x = logits.detach().double().requires_grad_(True)
+def _loss_and_grad(dtype, kind, logits, labels, *args, weight=None, space_label=None, in_w=1.0, out_w=1.0, task_weight=1.0, **kw):
+    x = logits.detach().to(dtype).requires_grad_(True)
     rows = ROWS[kind](x, labels, *args, **kw)
-    loss = combine(rows, row_weights(x.shape[0], weight, space_label, in_w, out_w), task_weight)
+    loss = combine(rows, row_weights(x.shape[0], weight, space_label, in_w, out_w, dtype), task_weight)
     (g,) = torch.autograd.grad(loss, x, allow_unused=True)
-    return loss.detach(), (g if g is not None else torch.zeros_like(x)).detach()
+    return loss.detach().double(), (g if g is not None else torch.zeros_like(x)).detach().double()
+
+
+def loss_and_grad(kind, logits, labels, *args, **kw):
+    """(loss, d loss / d logits), both float64, of float32 (or float64) logits"""
+    return _loss_and_grad(torch.float64, kind, logits, labels, *args, **kw)
+
+
+def loss_and_grad_fp32(kind, logits, labels, *args, **kw):
+    """the fp32 literal form: the same ROWS[kind] expression and the same weight combination on float32 tensors, with autograd
+    (returned as float64): what a kernel's distance to `loss_and_grad` is measured against"""
+    return _loss_and_grad(torch.float32, kind, logits, labels, *args, **kw)

@@ -18,10 +18,16 @@ def bins(preds: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
     return (preds[:, None] >= thresholds[None, :]).sum(dim=1)
 
 
-def histogram(preds, target, thresholds) -> torch.Tensor:
+def bins_sorted(preds: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
+    """`bins` without the [B, T] mask, for ascending thresholds: a binary search per sample (a NaN compares false: bin 0)"""
+    b = torch.searchsorted(thresholds, preds.contiguous(), right=True)
+    return torch.where(torch.isnan(preds), torch.zeros_like(b), b)
+
+
+def histogram(preds, target, thresholds, bins_of=bins) -> torch.Tensor:
     """int64 [T + 1, 2]: samples per (bin, class)"""
     T = thresholds.numel()
-    flat = bins(preds, thresholds) * 2 + (target != 0).to(torch.int64)
+    flat = bins_of(preds, thresholds) * 2 + (target != 0).to(torch.int64)
     return torch.bincount(flat, minlength=(T + 1) * 2).view(T + 1, 2)
 
 

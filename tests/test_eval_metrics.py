@@ -3,7 +3,11 @@ own test literals (tests/golden/reference_metric_cases.json): on the lane emulat
 
 Tolerances: counts are integers (equality).  The AUC is a float64 trapezoid over identical integers on both sides (rtol
 1e-12).  NE: the reference test's own atol 1e-6 on its literals; rtol 1e-5 against the float64 restatement (device logf /
-log1pf against host log, a couple of fp32 ulps per term).  Grouped AUC: the integer 2U divided once, rtol 1e-12."""
+log1pf against host log, a couple of fp32 ulps per term).  Grouped AUC: the integer 2U divided once, rtol 1e-12.
+
+The last section runs batches above the kernels' grid caps (restated there and checked against the source), where a lane's
+grid-stride loop and the block scan's top level take a second trip: the histogram is then compared with a binary-search
+restatement (metrics_ref.bins_sorted, itself checked against the [B, T] comparison at small B)."""
 import json
 import os
 
@@ -253,3 +257,135 @@ def test_abi_errors(dev):
     assert L.tzr_grouped_auc_reduce(p(rk), p(rp), p(rl), 4, p(out), p(cnt), p(ws) + 8, nbytes, None) == WORKSPACE
     assert L.tzr_grouped_auc_reduce(p(rk), p(rp), p(rl), 4, p(out), p(cnt), p(ws), nbytes, None) == OK
     assert L.tzr_grouped_auc_reduce(None, None, None, 0, p(out), p(cnt), None, 0, None) == OK
+
+
+# ---- past the grid caps: a lane's grid-stride loop runs twice, the block scan runs over more than 256 blocks --------------------
+EM_THREADS, EM_VEC, EM_MAX_UPDATE_WGS, EM_MAX_APPEND_WGS = 256, 4, 512, 1024  # csrc/eval_metrics.hip
+B_VEC = 524288 + 3079     # float4 form: above EM_MAX_UPDATE_WGS * EM_THREADS * EM_VEC, a whole-float4 tail and a scalar tail
+B_SCALAR = 131072 + 1283  # scalar form: above EM_MAX_UPDATE_WGS * EM_THREADS
+N_GROUPED = 300000
+
+
+def test_the_big_updates_take_the_second_trip_of_every_capped_grid():
+    src = open(os.path.join(os.path.dirname(__file__), "..", "torcheasyrec_amd", "csrc", "eval_metrics.hip")).read()
+    for text in (f"#define EM_THREADS {EM_THREADS}", f"#define EM_VEC {EM_VEC} ", f"#define EM_MAX_UPDATE_WGS {EM_MAX_UPDATE_WGS}",
+                 f"std::min<int64_t>({EM_MAX_APPEND_WGS}, (B + EM_THREADS - 1) / EM_THREADS)"):
+        assert text in src, text  # the caps restated above are the kernels'
+    assert B_VEC // EM_VEC > EM_MAX_UPDATE_WGS * EM_THREADS and B_VEC % EM_VEC != 0
+    assert EM_MAX_UPDATE_WGS * EM_THREADS < B_SCALAR < EM_MAX_UPDATE_WGS * EM_THREADS * EM_VEC
+    assert N_GROUPED > EM_MAX_APPEND_WGS * EM_THREADS                     # the append's loop
+    assert -(-(N_GROUPED + 1) // EM_THREADS) > EM_THREADS                 # tzr_scan_top_kernel and the part_sum finish: a second trip
+
+
+def test_the_searchsorted_restatement_bins_as_the_comparison_does():
+    for T in (2, 200, 1000, 4096):
+        thr = torch.linspace(0, 1, T)
+        p = torch.cat([thr, torch.nextafter(thr, torch.tensor(-1.0)), torch.nextafter(thr, torch.tensor(2.0)),
+                       torch.tensor([float("nan"), -0.0, 1.5, -3.0]), _preds(8199, T, seed=T)])
+        assert torch.equal(ref.bins_sorted(p, thr), ref.bins(p, thr))
+
+
+def _big_samples(B, T, seed):
+    p, y = _preds(B, T, seed), _labels(B, "mixed", seed)
+    p[:4], y[:4] = torch.tensor([0.0, 0.0, 1.0, 1.0]), torch.tensor([0, 1, 0, 1])  # the NE clamp, with both labels
+    return p, y
+
+
+def _misaligned(t, dev):
+    """`t` on the device, 4 (float32) or 8 (int64) bytes behind a 16-byte boundary: the update's scalar form"""
+    out = torch.cat([t[:1], t]).to(dev)[1:]
+    assert out.is_contiguous() and out.data_ptr() % 16 != 0
+    return out
+
+
+def _aligned(t, dev):
+    out = t.to(dev)
+    assert out.data_ptr() % 16 == 0
+    return out
+
+
+@pytest.mark.parametrize("form,B,T", [("float4", B_VEC, 200), ("float4", B_VEC, 4096), ("scalar", B_SCALAR, 200)])
+def test_metric_update_past_its_grid_cap(dev, form, B, T):
+    p, y = _big_samples(B, T, seed=B + T)
+    place = _aligned if form == "float4" else _misaligned
+    auc, ne = BinnedAUC(T, device=dev), NormalizedEntropy(device=dev)
+    metric_update(place(p, dev), place(y, dev), auc=auc, ne=ne)
+    _sync(dev)
+    assert torch.equal(auc.histogram().cpu(), ref.histogram(p, y, auc.thresholds.cpu(), ref.bins_sorted))
+    state = ne.state().cpu()
+    assert state[1].item() == B and state[2].item() == int(y.sum())
+    want, got = ref.normalized_entropy(p, y), ne.compute().cpu().to(torch.float64)
+    print(f"NE {form} B={B} on {dev.type}: got {got.item():.9g} want {want.item():.9g} rel {abs(got.item() - want.item()) / abs(want.item()):.3g}")
+    torch.testing.assert_close(got, want, rtol=1e-5, atol=0.0)
+
+
+def test_metric_updates_past_the_cap_accumulate(dev):
+    """the same samples in one aligned update, and as an aligned update above the float4 form's cap followed by a misaligned
+    one above the scalar form's"""
+    T = 200
+    p, y = _big_samples(B_VEC + B_SCALAR, T, seed=77)
+    whole_auc, whole_ne = BinnedAUC(T, device=dev), NormalizedEntropy(device=dev)
+    parts_auc, parts_ne = BinnedAUC(T, device=dev), NormalizedEntropy(device=dev)
+    metric_update(_aligned(p, dev), _aligned(y, dev), auc=whole_auc, ne=whole_ne)
+    metric_update(_aligned(p[:B_VEC], dev), _aligned(y[:B_VEC], dev), auc=parts_auc, ne=parts_ne)
+    metric_update(_misaligned(p[B_VEC:], dev), _misaligned(y[B_VEC:], dev), auc=parts_auc, ne=parts_ne)
+    _sync(dev)
+    want = ref.histogram(p, y, whole_auc.thresholds.cpu(), ref.bins_sorted)
+    assert torch.equal(whole_auc.histogram().cpu(), want) and torch.equal(parts_auc.histogram().cpu(), want)
+    for ne in (whole_ne, parts_ne):
+        state = ne.state().cpu()
+        assert state[1].item() == p.numel() and state[2].item() == int(y.sum())
+        torch.testing.assert_close(ne.compute().cpu().to(torch.float64), ref.normalized_entropy(p, y), rtol=1e-5, atol=0.0)
+    torch.testing.assert_close(whole_auc.compute().cpu(), parts_auc.compute().cpu(), rtol=0.0, atol=0.0)
+
+
+_BIG_GROUPED = {}
+
+
+def _big_grouped_rows():
+    """300 000 rows in about 9000 groups, one of them of about 12 000 rows; keys negative and above 2^40; predictions from 50
+    values (ties inside every group); with the pairwise restatement's (sum, groups), computed once"""
+    if not _BIG_GROUPED:
+        g = torch.Generator().manual_seed(300)
+        group = torch.cat([torch.zeros(12000, dtype=torch.int64), torch.randint(0, 9000, (N_GROUPED - 12000,), generator=g)])
+        keys = torch.where(group % 2 == 0, group + (1 << 41), -group - 5)
+        p = torch.randint(0, 50, (N_GROUPED,), generator=g).to(torch.float32) / 49.0
+        y = (torch.rand(N_GROUPED, generator=g) < 0.4).to(torch.int64)
+        perm = torch.randperm(N_GROUPED, generator=g)
+        p, y, keys = p[perm], y[perm], keys[perm]
+        assert int((keys == (1 << 41)).sum()) >= 12000 and bool((keys < 0).any()) and int(keys.max()) > (1 << 40)
+        _BIG_GROUPED["rows"] = (p, y, keys)
+        _BIG_GROUPED["want"] = ref.grouped_auc_parts(p, y, keys)
+    return _BIG_GROUPED["rows"], _BIG_GROUPED["want"]
+
+
+@pytest.mark.parametrize("chunks", [1, 3])
+def test_grouped_auc_past_the_append_cap_and_one_scan_level(dev, chunks):
+    (p, y, k), (want_sum, want_groups) = _big_grouped_rows()
+    n = p.numel()
+    m = GroupedAUC(capacity=n + 10, device=dev)
+    cuts = [n * i // chunks for i in range(chunks + 1)]
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        m.update(p[lo:hi].to(dev), y[lo:hi].to(dev), k[lo:hi].to(dev))
+    rp, ry, rk, overflow = m.rows()
+    assert overflow == 0 and torch.equal(rp.cpu(), p) and torch.equal(ry.cpu().to(torch.int64), y) and torch.equal(rk.cpu(), k)
+    parts = GroupedAUC.reduce_rows(rp, ry, rk).cpu()
+    assert int(parts[1]) == want_groups and want_groups > 8000
+    torch.testing.assert_close(parts[0], torch.tensor(want_sum, dtype=torch.float64), rtol=1e-12, atol=0.0)
+    torch.testing.assert_close(m.compute().cpu(), torch.tensor(want_sum / want_groups, dtype=torch.float64), rtol=1e-12, atol=0.0)
+
+
+def test_grouped_auc_overflow_in_the_second_trip_of_a_large_update(dev):
+    (p, y, k), _ = _big_grouped_rows()
+    n = p.numel()
+    cap = n + EM_MAX_APPEND_WGS * EM_THREADS + 5000  # the second update's rows stop fitting inside its lanes' second trip
+    assert n + EM_MAX_APPEND_WGS * EM_THREADS < cap < 2 * n
+    m = GroupedAUC(capacity=cap, device=dev)
+    m.update(p.to(dev), y.to(dev), k.to(dev))
+    m.update(p.flip(0).to(dev), y.flip(0).to(dev), k.flip(0).to(dev))
+    rp, ry, rk, overflow = m.rows()
+    assert overflow == 2 * n - cap and rp.numel() == cap
+    both = [torch.cat([t, t.flip(0)])[:cap] for t in (p, y, k)]
+    assert torch.equal(rp.cpu(), both[0]) and torch.equal(ry.cpu().to(torch.int64), both[1]) and torch.equal(rk.cpu(), both[2])
+    with pytest.raises(RuntimeError, match=f"{2 * n - cap} rows did not fit"):
+        m.compute()

@@ -5,7 +5,9 @@
 //   tzr_loss_pointwise   [B] logits: binary cross entropy with label smoothing, binary focal loss (the focal weight is
 //                        a constant of the gradient, as the reference detaches it), L2 -- tzr_bce_logits_kernel's tiling
 //   tzr_softmax_ce       [B, C] logits, label smoothing; one lane per row up to C = 8, one wave per row beyond; a label
-//                        outside [0, C) is counted, never used as an index
+//                        outside [0, C) is counted, never used as an index.  A class masked out by -inf (not the
+//                        label's own) has probability and gradient 0; the smoothing term u (C lse - sum x) is +inf
+//                        then, as torch's is, and is not formed at all when label_smoothing == 0 (0 * inf)
 //   tzr_jrc_loss         JRC (tzrec/loss/jrc_loss.py) grouped by session: O(B) memory where the reference builds [B, B]
 //                        masks (17 GB each at B = 65536).  A batch with no positive or no negative row makes the
 //                        reference's mean form NaN (mean of an empty tensor times 0); here it is the finite sum.
@@ -203,12 +205,15 @@ __global__ __launch_bounds__(LS_THREADS) void tzr_softmax_ce_small_kernel(
       if (c == (int)y) xy = x[c];
     }
   }
-  const float lse = m + logf(s);
+  // lse = m + ls is formed for the smoothing term alone: lse - x = (m - x) + ls keeps the rounding at the size of the difference,
+  // not of lse (logits of scale 120: an ulp of lse is 3e-5, and so was the relative error of exp(x - lse))
+  const float ls = logf(s), lse = m + ls;
   const float u = eps / (float)C;
-  rowloss[i] = (1.0f - eps) * (lse - xy) + u * ((float)C * lse - sx);
+  const float ce = (1.0f - eps) * ((m - xy) + ls);
+  rowloss[i] = eps > 0.f ? ce + u * ((float)C * lse - sx) : ce;  // (uniform: 0 * (sx = -inf) would be NaN)
 #pragma unroll
   for (int c = 0; c < LS_SMALL_C; ++c)
-    if (c < C) grad[i * C + c] = w * (expf(x[c] - lse) - ((c == (int)y ? 1.0f - eps : 0.f) + u));
+    if (c < C) grad[i * C + c] = w * (expf((x[c] - m) - ls) - ((c == (int)y ? 1.0f - eps : 0.f) + u));
 }
 
 // one wave per row, lanes stride over the classes
@@ -243,11 +248,14 @@ __global__ __launch_bounds__(LS_THREADS) void tzr_softmax_ce_wave_kernel(
   }
   s = __shfl(s, 0, TZR_WAVE);
   sx = __shfl(sx, 0, TZR_WAVE);
-  const float lse = m + logf(s);
+  const float ls = logf(s), lse = m + ls;  // (as in the small kernel)
   const float u = eps / (float)C;
-  if (lane == 0) rowloss[i] = (1.0f - eps) * (lse - x[y]) + u * ((float)C * lse - sx);
+  if (lane == 0) {
+    const float ce = (1.0f - eps) * ((m - x[y]) + ls);
+    rowloss[i] = eps > 0.f ? ce + u * ((float)C * lse - sx) : ce;  // (uniform, as in the small kernel)
+  }
   for (int c = lane; c < C; c += TZR_WAVE)
-    grad[i * C + c] = w * (expf(x[c] - lse) - ((c == (int)y ? 1.0f - eps : 0.f) + u));
+    grad[i * C + c] = w * (expf((x[c] - m) - ls) - ((c == (int)y ? 1.0f - eps : 0.f) + u));
 }
 
 // ---- JRC -------------------------------------------------------------------------------------------------------------
