@@ -945,6 +945,75 @@ size_t tzr_distill_loss_workspace(const TzrDistillLoss* h_dst);
 int tzr_distill_loss_fwd(const TzrDistillLoss* h_dst, void* stream);
 int tzr_distill_loss_bwd(const TzrDistillLoss* h_dst, void* stream);
 
+/* TDM's multi-window DIN encoder (tzrec/modules/sequence.py:288-367), restated on the jagged rows: one launch forward, one plus
+ * the finishing launch backward; no padding position is computed and nothing of shape [N, H] or [N, 3 C] is in memory.
+ *   k [N, C] fp32 jagged rows (unit column stride, row stride a multiple of 4 floats and no narrower than C, 16-byte aligned
+ *   rows: a column slice of a wider buffer is fine), offsets [B + 1] int64 (offsets outside [0, N] are clamped), q [B, C] the query
+ *   zero-padded to C.  Layer l (l < layers): w[l] [H[l], in_l] contiguous (nn.Linear's layout; in_0 = 3 C over [k, q * k, q], in_l =
+ *   H[l-1]), b[l] [H[l]], slope[l] [1] the leaky slope of its activation (PReLU's weight) or 0 for ReLU; w3 [H[layers-1]], b3 [1]
+ *   the score layer; alpha [1] the slope of the final PReLU.  windows_len[0 .. W-1], cum_w = windows_len[0] + .. + windows_len[w-1],
+ *   Sw = cum_W.  Sample b: len_b = offsets[b + 1] - offsets[b]; positions n < s_b = min(len_b, max_len, Sw) take part;
+ *     a_n = <w3, act(.. act(W_0 [k_n, q * k_n, q] + b_0) ..)> + b3,  s_n = a_n > 0 ? a_n : alpha a_n,
+ *     out[b, w, :] = (sum of s_n k_n over cum_w <= n < min(cum_w + windows_len[w], s_b)) / max(min(len_b - cum_w, windows_len[w]), 1)
+ *     (len_b UNTRUNCATED in the divisor, as the padded form's sequence_length; a window not reached is a zero row),
+ *     out[b, W, :] = q_b.  act(z) = z > 0 ? z : slope z; its derivative at 0 is the slope (torch's).
+ * forward writes out [B, (W + 1) C] (row stride out_stride), every float of every row, also for samples without rows.
+ * backward recomputes the pre-activations as the forward does (the same bits) and writes dk [N, C] (rows at or behind s_b: zeros;
+ *   so are the rows in front of offsets[0] and behind offsets[B], which belong to no sample: every row of dk is written),
+ *   dq [B, C] (the caller crops it to the query's width) and dparams, one float a parameter: per layer [dw_l | db_l] in order,
+ *   then dw3, db3, one slope gradient a layer (0 for a ReLU layer), dalpha.  A launch of min(B, TZR_MWDIN_BWD_MAX_GRID) workgroups
+ *   (workgroup g takes the samples g, g + grid, .. in that order) leaves one partial row per workgroup in `ws` (tzr_mwdin_workspace
+ *   bytes), a finishing launch adds the rows in the interleaved order (csrc/parts_sum.h).  No atomics; every sum's order is a
+ *   function of the shapes and the offsets alone: two runs are bit-equal.
+ * Limits (TZR_ERR_UNSUPPORTED beyond): C and every H[l] multiples of 4 in [4, TZR_MWDIN_MAX_DIM]; 1 <= layers <=
+ *   TZR_MWDIN_MAX_LAYERS; 1 <= W <= TZR_MWDIN_MAX_WINDOWS, every windows_len >= 1; max_len >= 1; S = min(max_len, Sw) <=
+ *   TZR_MWDIN_MAX_S and ceil16(S) * max(C, H[l]) <= TZR_MWDIN_MAX_SH (a sample's tile in LDS); the parameter count (3 C + 1) H[0] +
+ *   (H[0] + 1) H[1] + .. + H[layers-1] + 1 + layers + 1 <= TZR_MWDIN_MAX_PARAMS (a workgroup's partial row is 128 KB at most, one
+ *   CU's share of its L2); B, N < 2^31; a row stride that is no multiple of 4 or below the width.  TZR_ERR_INVALID: a null or
+ *   misaligned pointer (k / q / out / grad_out / dk / dq and w[l] 16 bytes, offsets 8, the others 4; k and dk may be 0 when N == 0,
+ *   slope[l] may be 0), B < 0, N < 0.  TZR_ERR_WORKSPACE (backward): `ws` null, not 256-byte aligned or below the query less its
+ *   256 bytes of slack.  Limits are checked first, then pointers.  B == 0: TZR_OK without a launch; N == 0 with B > 0 still writes
+ *   the rows.  A refused call launches nothing.  A new struct and entry points, no change to existing ones: the ABI version stays 15. */
+#define TZR_MWDIN_MAX_DIM 128
+#define TZR_MWDIN_MAX_LAYERS 3
+#define TZR_MWDIN_MAX_WINDOWS 32
+#define TZR_MWDIN_MAX_S 128
+#define TZR_MWDIN_MAX_SH 8192
+#define TZR_MWDIN_MAX_PARAMS 32768
+#define TZR_MWDIN_BWD_MAX_GRID 512
+typedef struct TzrMwdin {
+  int64_t B, N;
+  int32_t C, W, max_len, layers;
+  int32_t H[TZR_MWDIN_MAX_LAYERS];
+  int32_t reserved;
+  int32_t windows_len[TZR_MWDIN_MAX_WINDOWS];
+  uint64_t k;                        /* const float* [N, C] */
+  int64_t k_stride;
+  uint64_t q;                        /* const float* [B, C] */
+  int64_t q_stride;
+  uint64_t offsets;                  /* const int64_t* [B + 1] */
+  uint64_t w[TZR_MWDIN_MAX_LAYERS];      /* const float* [H[l], in_l] */
+  uint64_t b[TZR_MWDIN_MAX_LAYERS];      /* const float* [H[l]] */
+  uint64_t slope[TZR_MWDIN_MAX_LAYERS];  /* const float* [1], nullable: ReLU */
+  uint64_t w3;                       /* const float* [H[layers - 1]] */
+  uint64_t b3;                       /* const float* [1] */
+  uint64_t alpha;                    /* const float* [1] */
+  uint64_t out;                      /* float* [B, (W + 1) C]        (forward writes) */
+  int64_t out_stride;
+  uint64_t grad_out;                 /* const float* [B, (W + 1) C]  (backward) */
+  int64_t grad_out_stride;
+  uint64_t dk;                       /* float* [N, C]                (backward) */
+  int64_t dk_stride;
+  uint64_t dq;                       /* float* [B, C]                (backward) */
+  int64_t dq_stride;
+  uint64_t dparams;                  /* float* [params]              (backward) */
+  uint64_t ws;                       /* workspace                    (backward) */
+  uint64_t ws_bytes;
+} TzrMwdin;
+size_t tzr_mwdin_workspace(const TzrMwdin* h_mw);
+int tzr_mwdin_fwd(const TzrMwdin* h_mw, void* stream);
+int tzr_mwdin_bwd(const TzrMwdin* h_mw, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

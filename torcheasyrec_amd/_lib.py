@@ -200,6 +200,23 @@ class TzrDistillLoss(C.Structure):
 
 
 assert C.sizeof(TzrDistillLoss) == 576
+# limits of tzr_mwdin_* (include/tzrec_hip.h: TZR_MWDIN_*)
+MWDIN_MAX_DIM, MWDIN_MAX_LAYERS, MWDIN_MAX_WINDOWS, MWDIN_MAX_S, MWDIN_MAX_SH, MWDIN_MAX_PARAMS, MWDIN_BWD_MAX_GRID = 128, 3, 32, 128, 8192, 32768, 512
+
+
+class TzrMwdin(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("N", C.c_int64), ("C", C.c_int32), ("W", C.c_int32), ("max_len", C.c_int32), ("layers", C.c_int32),
+        ("H", C.c_int32 * MWDIN_MAX_LAYERS), ("reserved", C.c_int32), ("windows_len", C.c_int32 * MWDIN_MAX_WINDOWS),
+        ("k", C.c_uint64), ("k_stride", C.c_int64), ("q", C.c_uint64), ("q_stride", C.c_int64), ("offsets", C.c_uint64),
+        ("w", C.c_uint64 * MWDIN_MAX_LAYERS), ("b", C.c_uint64 * MWDIN_MAX_LAYERS), ("slope", C.c_uint64 * MWDIN_MAX_LAYERS),
+        ("w3", C.c_uint64), ("b3", C.c_uint64), ("alpha", C.c_uint64), ("out", C.c_uint64), ("out_stride", C.c_int64),
+        ("grad_out", C.c_uint64), ("grad_out_stride", C.c_int64), ("dk", C.c_uint64), ("dk_stride", C.c_int64),
+        ("dq", C.c_uint64), ("dq_stride", C.c_int64), ("dparams", C.c_uint64), ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrMwdin) == 400
 
 
 class TzrSparseOptim(C.Structure):
@@ -445,6 +462,9 @@ _SIGNATURES = {
     "tzr_distill_loss_workspace": (_sz, [_vp]),
     "tzr_distill_loss_fwd": (_i32, [_vp, _vp]),
     "tzr_distill_loss_bwd": (_i32, [_vp, _vp]),
+    "tzr_mwdin_workspace": (_sz, [_vp]),
+    "tzr_mwdin_fwd": (_i32, [_vp, _vp]),
+    "tzr_mwdin_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

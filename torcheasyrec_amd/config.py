@@ -150,6 +150,7 @@ class SeqEncoderSpec:
     max_seq_length: int = 0
     attn_mlp: Optional[dict] = None  # din_encoder: {"hidden_units": [...]}
     pooling_type: str = "mean"  # pooling_encoder: sum | mean
+    windows_len: Optional[list] = None  # multi_window_din_encoder (sequence.create_seq_encoder; not among SEQ_ENCODER_KINDS)
 
 
 @dataclass

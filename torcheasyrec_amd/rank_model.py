@@ -234,6 +234,59 @@ class ConfigMultiTowerDIN(RankModel):
         return self._output_to_prediction(self.output_mlp(y))
 
 
+class ConfigTDM(RankModel):
+    """`tdm { multiwindow_din { windows_len attn_mlp {} } final {} }` (tzrec/models/tdm.py:38-98): the multi-window DIN encoder over
+    the one SEQUENCE group, `deep_mlp` over cat([encoder output, every other group in config order]), the logits layer.  The
+    tree sampler is data-side and is not built: the model trains on rows that are already (user, node, label)."""
+
+    _FIELDS = ("multiwindow_din", "final")
+    _DIN_FIELDS = ("windows_len", "attn_mlp")
+
+    def __init__(self, spec: PipelineSpec, device=None, sparse_optimizer=None) -> None:
+        from .sequence import MultiWindowDINEncoder
+
+        m = spec.model
+        if "tdm_sampler" in getattr(spec, "sampler_kinds", ()):
+            raise NotImplementedError("tdm: data_config `tdm_sampler` is not built: the tree sampler is data-side, the model trains on rows "
+                                      "that are already (user, node, label)")
+        other = sorted(k for k in m if k not in self._FIELDS)
+        if other:
+            raise ValueError(f"tdm: tdm has no field {other[0]!r} (fields: {', '.join(self._FIELDS)})")
+        din = m.one("multiwindow_din", None)
+        other = sorted(k for k in (din or {}) if k not in self._DIN_FIELDS)
+        if other:
+            raise ValueError(f"tdm: multiwindow_din has no field {other[0]!r} (fields: {', '.join(self._DIN_FIELDS)})")
+        windows = [int(w) for w in din.many("windows_len")] if din is not None else []
+        if not windows:
+            raise ValueError("tdm: multiwindow_din.windows_len is empty")
+        seq = [g.group_name for g in spec.feature_groups if g.group_type == "SEQUENCE"]
+        if len(seq) != 1:
+            raise ValueError(f"tdm: exactly one SEQUENCE feature group feeds multiwindow_din (got {len(seq)}: {seq})")
+        super().__init__(spec, device, sparse_optimizer)
+        eg, g = self.embedding_group, seq[0]
+        self._seq_group = g
+        self._other_groups = [fg.group_name for fg in spec.feature_groups if fg.group_type != "SEQUENCE"]
+        self.multiwindow_din = MultiWindowDINEncoder(eg.group_total_dim(f"{g}.sequence"), eg.group_total_dim(f"{g}.query"), g, windows,
+                                                     mlp_kwargs(din.one("attn_mlp")))
+        # the group goes to the encoder as rows under multi_tower_din's conditions (one sequence_feature block, a configured
+        # sequence_length, one id a step) plus the kernel's own limits
+        info = eg._seq_info.get(g)
+        if info is not None and info.get("max_len") and len({f.name.split("__")[0] for f in info["sequence"]}) == 1 \
+                and not any(getattr(f, "value_dim", 1) not in (0, 1) for f in info["sequence"]) \
+                and self.multiwindow_din.jagged_limit(int(info["max_len"])) is None:
+            eg.jagged_sequence_groups.add(g)
+        self.deep_mlp = mlp_from_msg(self.multiwindow_din.output_dim() + sum(eg.group_total_dim(n) for n in self._other_groups), m.one("final"))
+        self.output_mlp = nn.Linear(self.deep_mlp.output_dim(), spec.num_class)
+        if device is not None:
+            for mod in (self.multiwindow_din, self.deep_mlp, self.output_mlp):
+                mod.to(device)
+
+    def forward(self, batch: Batch) -> Dict[str, torch.Tensor]:
+        g = self.build_input(batch)
+        y = torch.cat([self.multiwindow_din(g)] + [g[n] for n in self._other_groups], dim=1)
+        return self._output_to_prediction(self.output_mlp(self.deep_mlp(y)))
+
+
 FUSED_MOE_MIX = True  # A/B switch: False = the reference's stack / softmax / batched-matmul form
 
 
@@ -881,7 +934,8 @@ class ConfigWuKong(RankModel):
 
 _MODELS = {"dlrm": ConfigDLRM, "deepfm": ConfigDeepFM, "multi_tower_din": ConfigMultiTowerDIN, "mmoe": ConfigMMoE, "ple": ConfigPLE,
            "pepnet": ConfigPEPNet, "dbmtl": ConfigDBMTL,
-           "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong}
+           "dcn_v1": ConfigDCNV1, "dcn_v2": ConfigDCNV2, "xdeepfm": ConfigXDeepFM, "mask_net": ConfigMaskNet, "wukong": ConfigWuKong,
+           "tdm": ConfigTDM}
 
 
 from .match import ConfigDAT, ConfigDSSM, ConfigMIND  # noqa: E402  (the match models; match.py reads this module's helpers when a tower is built)

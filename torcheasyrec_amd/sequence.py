@@ -823,8 +823,228 @@ class PoolingEncoder(nn.Module):
         return feature
 
 
+# ---- multi-window DIN on the jagged positions (csrc/mwdin.hip) ---------------------------------------------------------
+FUSED_MWDIN = True  # profiles/mwdin: the fused encoder against the literal one, forward + backward
+
+
+def mwdin_literal(query: torch.Tensor, sequence: torch.Tensor, sequence_length: torch.Tensor, enc: "MultiWindowDINEncoder") -> torch.Tensor:
+    """The reference's padded form (tzrec/modules/sequence.py:330-367): query [B, Dq], sequence [B, T, C], sequence_length [B]
+    -> [B, (W + 1) C].  A negative pad CROPS the positions behind sum(windows_len); the divisor takes the length as handed over."""
+    T = sequence.size(1)
+    mask = torch.arange(T, device=sequence_length.device).unsqueeze(0) < sequence_length.unsqueeze(1)
+    if enc._query_dim < enc._sequence_dim:
+        query = nn.functional.pad(query, (0, enc._sequence_dim - enc._query_dim))
+    queries = query.unsqueeze(1).expand(-1, T, -1)
+    a = enc.active(enc.linear(enc.mlp(torch.cat([sequence, queries * sequence, queries], dim=-1))))  # [B, T, 1]
+    att = a * mask.unsqueeze(2) * sequence
+    padded = nn.functional.pad(att, (0, 0, 0, enc._sum_windows_len - T)).transpose(0, 1)
+    result = torch.segment_reduce(padded, reduce="sum", lengths=enc.windows_len, axis=0).transpose(0, 1)  # [B, W, C]
+    seg = torch.min(sequence_length.unsqueeze(1) - enc.cumsum_windows_len.unsqueeze(0), enc.windows_len)
+    result = result / torch.max(seg, torch.ones_like(seg)).unsqueeze(2)
+    return torch.cat([result, query.unsqueeze(1)], dim=1).reshape(result.shape[0], -1)
+
+
+def mwdin_limit(C: int, hidden: Sequence[int], windows: Sequence[int], max_len: int) -> Optional[str]:
+    """None when tzr_mwdin_* has a kernel for the shape, else the limit of csrc/mwdin.hip it misses (include/tzrec_hip.h)"""
+    D = _lib.MWDIN_MAX_DIM
+    if C % 4 or not 4 <= C <= D:
+        return f"sequence_dim {C} must be a multiple of 4 in [4, {D}]"
+    if not 1 <= len(hidden) <= _lib.MWDIN_MAX_LAYERS:
+        return f"the attention MLP must have 1 to {_lib.MWDIN_MAX_LAYERS} layers (got {len(hidden)})"
+    for h in hidden:
+        if h % 4 or not 4 <= h <= D:
+            return f"attention-MLP width {h} must be a multiple of 4 in [4, {D}]"
+    if not 1 <= len(windows) <= _lib.MWDIN_MAX_WINDOWS or min(windows) < 1:
+        return f"1 to {_lib.MWDIN_MAX_WINDOWS} windows of length >= 1 (got {list(windows)})"
+    S = min(int(max_len), sum(windows))
+    if S < 1 or S > _lib.MWDIN_MAX_S:
+        return f"min(max_len, sum(windows_len)) = {S} must be in [1, {_lib.MWDIN_MAX_S}]"
+    if (S + 15) // 16 * 16 * max([C] + list(hidden)) > _lib.MWDIN_MAX_SH:
+        return f"ceil16({S}) * {max([C] + list(hidden))} must be at most {_lib.MWDIN_MAX_SH} (a sample's tile in LDS)"
+    params, d = 0, 3 * C
+    for h in hidden:
+        params, d = params + (d + 1) * h, h
+    if params + d + 1 + len(hidden) + 1 > _lib.MWDIN_MAX_PARAMS:
+        return f"{params + d + 2 + len(hidden)} attention parameters, at most {_lib.MWDIN_MAX_PARAMS}"
+    return None
+
+
+def mwdin_ok(values: torch.Tensor, query: torch.Tensor, offsets: torch.Tensor, max_len: int, windows: Sequence[int], layers, w3, b3, alpha) -> bool:
+    """what tzr_mwdin_* takes: fp32 values [N, C] as `_lib.rows_ok` rows (a column slice of a wider buffer is fine), query [B, C]
+    already padded, offsets int64 [B + 1] contiguous, layers [(weight, bias, slope or None)] contiguous fp32, a shape inside
+    `mwdin_limit`, everything on the device of the loaded library"""
+    if values.dim() != 2 or query.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 2:
+        return False
+    (N, C), B, dev = values.shape, offsets.numel() - 1, values.device
+    if not _lib.takes(values) or query.device != dev or offsets.device != dev or values.dtype != torch.float32:
+        return False
+    hidden = [w.shape[0] for w, _, _ in layers]
+    if mwdin_limit(C, hidden, windows, max_len) is not None or N >= 2 ** 31 or B >= 2 ** 31:
+        return False
+    if query.shape != (B, C) or query.dtype != torch.float32 or (N > 0 and not _lib.rows_ok(values, C)):
+        return False
+    if offsets.dtype != torch.int64 or not offsets.is_contiguous():
+        return False
+    d = 3 * C
+    for w, b, s in layers:
+        if not (_lib.packed_ok(w, (w.shape[0], d), dev, aligned=True) and _lib.packed_ok(b, (w.shape[0],), dev) and (s is None or _lib.packed_ok(s, (1,), dev))):
+            return False
+        d = w.shape[0]
+    return _lib.packed_ok(w3, (1, d), dev) and _lib.packed_ok(b3, (1,), dev) and _lib.packed_ok(alpha, (1,), dev)
+
+
+class _MwdinFn(torch.autograd.Function):
+    """Inputs: values [N, C], query [B, C] (padded), offsets [B + 1], max_len, windows, alpha [1], w3 [1, H], b3 [1], the layers'
+    (weight, bias) pairs, then their slopes (None: ReLU).  Output [B, (W + 1) C].  Saved for the backward: the inputs alone -- the
+    backward launch recomputes the pre-activations.  Capturable: every buffer is torch's, nothing is read back.  The gradient of `values`
+    comes from torch.empty: the backward kernel writes every one of its N rows (zeros for the rows behind a sample's S positions and for
+    rows outside offsets[0] .. offsets[B]), no fill launch."""
+
+    calls = 0  # forwards that took the kernel (tests)
+
+    @staticmethod
+    def _fill(m, values, query, offsets, max_len, windows, alpha, w3, b3, wb, slopes):
+        nl = len(slopes)
+        m.B, m.N, m.C, m.W, m.max_len, m.layers = offsets.numel() - 1, values.shape[0], values.shape[1], len(windows), max_len, nl
+        for i, wl in enumerate(windows):
+            m.windows_len[i] = wl
+        for l in range(nl):
+            m.H[l], m.w[l], m.b[l], m.slope[l] = wb[2 * l].shape[0], _lib.ptr(wb[2 * l]), _lib.ptr(wb[2 * l + 1]), _lib.opt_ptr(slopes[l])
+        if values.shape[0] > 0:
+            m.k, m.k_stride = _lib.ptr(values), values.stride(0)
+        else:
+            m.k_stride = values.shape[1]
+        m.q, m.q_stride, m.offsets = _lib.ptr(query), query.stride(0), _lib.ptr(offsets)
+        m.w3, m.b3, m.alpha = _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(alpha)
+
+    @staticmethod
+    def forward(ctx, values, query, offsets, max_len, windows, alpha, w3, b3, nl, *params):
+        _MwdinFn.calls += 1
+        wb, slopes = [p.detach() for p in params[:2 * nl]], [None if p is None else p.detach() for p in params[2 * nl:]]
+        query = _lib.rows16(query)
+        B, C, dev = offsets.numel() - 1, values.shape[1], values.device
+        out = torch.empty(B, (len(windows) + 1) * C, dtype=torch.float32, device=dev)
+        m = _lib.TzrMwdin()
+        _MwdinFn._fill(m, values, query, offsets, max_len, windows, alpha.detach(), w3.detach(), b3.detach(), wb, slopes)
+        m.out, m.out_stride = _lib.ptr(out), out.stride(0)
+        _lib.launch("tzr_mwdin_fwd", m, dev)
+        ctx.save_for_backward(values, query, offsets, alpha, w3, b3, *params)
+        ctx.cfg = (max_len, tuple(windows), nl)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        values, query, offsets, alpha, w3, b3 = ctx.saved_tensors[:6]
+        params = ctx.saved_tensors[6:]
+        max_len, windows, nl = ctx.cfg
+        wb, slopes = params[:2 * nl], list(params[2 * nl:]) + [None] * (3 * nl - len(params))
+        dev, (N, C), B = values.device, values.shape, offsets.numel() - 1
+        g = _lib.rows16(gout.to(torch.float32))
+        sizes = [t.numel() for t in wb] + [w3.numel(), 1] + [1] * nl + [1]
+        dk = torch.empty(N, C, dtype=torch.float32, device=dev)
+        dq = torch.empty(B, C, dtype=torch.float32, device=dev)
+        dp = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        m = _lib.TzrMwdin()
+        _MwdinFn._fill(m, values, query, offsets, max_len, windows, alpha, w3, b3, wb, slopes)
+        m.grad_out, m.grad_out_stride, m.dq, m.dq_stride, m.dparams = _lib.ptr(g), g.stride(0), _lib.ptr(dq), dq.stride(0), _lib.ptr(dp)
+        if N > 0:
+            m.dk, m.dk_stride = _lib.ptr(dk), dk.stride(0)
+        else:
+            m.dk_stride = C
+        _lib.launch_ws("tzr_mwdin", m, dev, "tzr_mwdin_bwd")
+        parts = torch.split(dp, sizes)
+        dwb = [p.view(t.shape) for p, t in zip(parts[:2 * nl], wb)]
+        dsl = [p if s is not None else None for p, s in zip(parts[2 * nl + 2:3 * nl + 2], slopes)]
+        return (dk, dq, None, None, None, parts[-1], parts[2 * nl].view(w3.shape), parts[2 * nl + 1], None, *dwb, *dsl)
+
+
+class MultiWindowDINEncoder(nn.Module):
+    """TDM's multi-window DIN (constructor, `output_dim` and parameter names of the reference's MultiWindowDINEncoder,
+    tzrec/modules/sequence.py:288-367): score = PReLU(linear(MLP([k, q * k, q]))) per position, NOT soft-maxed; per window the sum of
+    score * k over the window's positions divided by the positions the sample has there; the query as the last slot.
+
+    Evaluated on the padded `<input>.sequence` [B, T, C] by the reference's formula (`mwdin_literal`), or -- when the dict
+    carries `<input>.sequence_jagged`, `_offsets` and `_max_len` -- on the jagged rows in one launch each way (csrc/mwdin.hip).
+    The literal form also runs on the rows (padded first) when FUSED_MWDIN is off, the attention MLP is not plain (bias off,
+    use_bn, use_ln, dropout, an activation other than ReLU / PReLU), the shape is outside `mwdin_limit`, or `double_backward` is
+    set (the fused backward is differentiable once)."""
+
+    def __init__(self, sequence_dim: int, query_dim: int, input: str, windows_len: Sequence[int], attn_mlp: Dict[str, object], **kwargs) -> None:
+        super().__init__()
+        if query_dim > sequence_dim:
+            raise ValueError("query_dim > sequence_dim not supported yet.")
+        windows_len = [int(w) for w in windows_len]
+        if not windows_len:
+            raise ValueError(f"multi_window_din_encoder on {input!r}: windows_len is empty")
+        self._input = input
+        self._query_dim, self._sequence_dim, self._windows_len = query_dim, sequence_dim, windows_len
+        self.register_buffer("windows_len", torch.tensor(windows_len))
+        self.register_buffer("cumsum_windows_len", torch.tensor(np.cumsum([0] + windows_len[:-1])))
+        self._sum_windows_len = sum(windows_len)
+        self.mlp = MLP(sequence_dim * 3, **attn_mlp)
+        self.linear = nn.Linear(self.mlp.hidden_units[-1], 1)
+        self.active = nn.PReLU()
+        self._query_name = f"{input}.query"
+        self._sequence_name = f"{input}.sequence"
+        self._sequence_length_name = f"{input}.sequence_length"
+        self.double_backward = False  # True: the literal form, whose autograd graph can be differentiated again
+
+    def input(self) -> str:
+        return self._input
+
+    def output_dim(self) -> int:
+        return self._sequence_dim * (len(self._windows_len) + 1)
+
+    def _layers(self):
+        """[(weight, bias, slope or None)] of a plain attention MLP -- Linear with bias, then ReLU or a one-slope PReLU -- else None"""
+        mods, out = list(self.mlp.mlp), []
+        if len(mods) != 2 * len(self.mlp.hidden_units):
+            return None
+        for lin, act in zip(mods[0::2], mods[1::2]):
+            if not isinstance(lin, nn.Linear) or lin.bias is None:
+                return None
+            if isinstance(act, nn.PReLU) and act.weight.numel() == 1:
+                out.append((lin.weight, lin.bias, act.weight))
+            elif isinstance(act, nn.ReLU):
+                out.append((lin.weight, lin.bias, None))
+            else:
+                return None
+        return out
+
+    def jagged_limit(self, max_len: int = 0) -> Optional[str]:
+        """None when the kernel evaluates this encoder on sequences padded / truncated to `max_len`, else the limit missed"""
+        if self._layers() is None:
+            return "multi_window_din_encoder: the attention MLP must be plain Linear + bias + ReLU / PReLU layers"
+        lim = mwdin_limit(self._sequence_dim, self.mlp.hidden_units, self._windows_len, max_len)
+        return None if lim is None else f"multi_window_din_encoder: {lim}"
+
+    def forward_jagged(self, query: torch.Tensor, values: torch.Tensor, offsets: torch.Tensor, max_len: int) -> torch.Tensor:
+        """query [B, query_dim]; values [N, C] rows, sample b = rows [offsets[b], offsets[b + 1]); max_len: the padded length of the
+        reference's `sequence` tensor.  Same output and gradients as `forward` on the padded form, whose `sequence_length` is
+        offsets[1:] - offsets[:-1], not truncated.  Rows of `values` in front of offsets[0] or behind offsets[B] belong to no sample
+        and get a zero gradient, as in the padded form."""
+        layers = self._layers()
+        if FUSED_MWDIN and not self.double_backward and layers is not None and (values.is_cuda or _lib.emulated()):
+            q = nn.functional.pad(query, (0, self._sequence_dim - self._query_dim)) if self._query_dim < self._sequence_dim else query
+            if mwdin_ok(values, q, offsets, max_len, self._windows_len, layers, self.linear.weight, self.linear.bias, self.active.weight):
+                wb = [t for w, b, _ in layers for t in (w, b)]
+                return _MwdinFn.apply(values, q, offsets, int(max_len), self._windows_len, self.active.weight, self.linear.weight,
+                                      self.linear.bias, len(layers), *wb, *[s for _, _, s in layers])
+        return mwdin_literal(query, jagged_to_padded_dense(values, offsets, int(max_len)), offsets[1:] - offsets[:-1], self)
+
+    def forward(self, sequence_embedded: Dict[str, torch.Tensor]) -> torch.Tensor:
+        jag = sequence_embedded.get(self._sequence_name + "_jagged")
+        if jag is not None:
+            return self.forward_jagged(sequence_embedded[self._query_name], jag, sequence_embedded[self._sequence_name + "_offsets"],
+                                       int(sequence_embedded[self._sequence_name + "_max_len"]))
+        return mwdin_literal(sequence_embedded[self._query_name], sequence_embedded[self._sequence_name],
+                             sequence_embedded[self._sequence_length_name], self)
+
+
 def encoder_jagged_limit(enc: nn.Module, max_len: int) -> Optional[str]:
-    """None when `enc` evaluates a sequence group handed over as rows with padded length `max_len`, else why not"""
+    """None when `enc` evaluates a sequence group handed over as rows with padded length `max_len`, else why not (DINEncoder has
+    its own rule; SimpleAttention, PoolingEncoder and MultiWindowDINEncoder answer through `jagged_limit(max_len)`)"""
     if isinstance(enc, DINEncoder):
         lim = enc.jagged_limit()
         eff = min(max_len, enc._max_seq_length) if enc._max_seq_length > 0 else max_len
@@ -844,4 +1064,6 @@ def create_seq_encoder(spec, group_total_dim: Dict[str, int]) -> nn.Module:
         return SimpleAttention(sequence_dim, query_dim, spec.input, max_seq_length=spec.max_seq_length)
     if spec.kind == "pooling_encoder":
         return PoolingEncoder(sequence_dim, spec.input, pooling_type=spec.pooling_type, max_seq_length=spec.max_seq_length)
+    if spec.kind == "multi_window_din_encoder":  # (handed over as a spec directly: the loader refuses it inside a DEEP group's sequence_encoders)
+        return MultiWindowDINEncoder(sequence_dim, query_dim, spec.input, windows_len=list(spec.windows_len or []), attn_mlp=dict(spec.attn_mlp))
     raise NotImplementedError(f"sequence encoder {spec.kind!r} is not built")
