@@ -1014,6 +1014,63 @@ size_t tzr_mwdin_workspace(const TzrMwdin* h_mw);
 int tzr_mwdin_fwd(const TzrMwdin* h_mw, void* stream);
 int tzr_mwdin_bwd(const TzrMwdin* h_mw, void* stream);
 
+/* HSTU's jagged pointwise-SiLU attention (tzrec/ops/hstu_attention.py::hstu_mha under the STU layer, tzrec/modules/gr/stu.py),
+ * causal, fp32, no dropout: one launch forward, two backward (a row pass for dq, a column pass for dk and dv), no workspace.
+ *   q, k [N, H, Da], v [N, H, Dv] fp32, each given as pointer + floats between rows + floats between heads (unit column stride,
+ *   both strides multiples of 4, 16-byte aligned, head stride >= the width, row stride >= (H - 1) head stride + width): the column
+ *   slices of one [N, (2 Dv + 2 Da) H] uvqk matrix are read where they lie, and dq / dk / dv may be slices of one gradient matrix.
+ *   offsets [B + 1] int64 (offsets outside [0, N] are clamped), num_targets [B] int64 or 0.  Sample b has n = min(offsets[b + 1] -
+ *   offsets[b], max_seq_len) rows; for each head h and rows i, j in [0, n):
+ *     out[i, h, :] = sum_j valid(i, j) silu(alpha <q[i, h], k[j, h]>) / scale v[j, h, :],   scale = scaling_seqlen > 0 ?
+ *     scaling_seqlen : max_seq_len; valid is _get_valid_attn_mask (tzrec/ops/_pytorch/pt_hstu_attention.py) with causal = True on
+ *     the n rows, with c = contextual_seq_len, L = max_attn_len, t = num_targets[b]:
+ *       id(i) = c == 0 ? i : max(i - c + 1, 0);  max_id = (c == 0 ? n : n - c + 1) - t;  id(i) = min(id(i), max_id) when
+ *       num_targets is given;  d = id(i) - id(j);  valid = (i == j or d > 0), and (d <= L) when L > 0, or (id(i) == 0 and
+ *       id(j) < max_id) when c > 0.
+ *   backward: with s = alpha <q, k>, sig = sigmoid(s): silu'(s) = sig (1 + s (1 - sig)); every score tile is recomputed.
+ * A call that launches writes every row of out (forward) and dq, dk, dv (backward): rows at or behind max_seq_len of a sample, and
+ * rows in front of offsets[0] or behind offsets[B], get zeros from the kernels themselves.  B == 0 launches nothing, so with
+ * B == 0 and N > 0 the N rows are NOT written: a caller with rows and no sample clears them itself.  Nothing of size n x n or [B, H, max_seq_len, .]
+ * is in memory; work follows the sum of n_b^2 (key tiles without a valid pair are not visited).  No atomics, every sum's order
+ * is a function of the shapes, the offsets and num_targets alone: two runs are bit-equal.  Nothing is read back on the host.
+ * Limits (TZR_ERR_UNSUPPORTED beyond): Da, Dv multiples of 4 in [4, TZR_HSTU_MAX_DIM] (independently); H >= 1; 1 <= max_seq_len
+ *   <= TZR_HSTU_MAX_SEQ_LEN, max_attn_len and contextual_seq_len at most that; N < 2^31; ceil(max_seq_len / TZR_HSTU_BLOCK) B H
+ *   < 2^31 (the grid); strides as above.  TZR_ERR_INVALID: a null or misaligned pointer (operands 16 bytes, offsets and a given
+ *   num_targets 8), B, N, max_attn_len or contextual_seq_len < 0.  Order of the checks: negative sizes
+ *   (INVALID), then the limits (UNSUPPORTED), then -- only when B > 0 and N > 0 -- pointers and strides.  B == 0 or N == 0:
+ *   TZR_OK without a launch, whatever the pointers are.  A refused call launches nothing.  TZR_HSTU_BLOCK rows (keys in the column pass) a workgroup,
+ *   TZR_HSTU_TILE keys (rows) a tile.  A new struct and entry points, no change to existing ones: the ABI version stays 15. */
+#define TZR_HSTU_MAX_DIM 128
+#define TZR_HSTU_MAX_SEQ_LEN 268435456
+#define TZR_HSTU_BLOCK 64
+#define TZR_HSTU_TILE 16
+typedef struct TzrHstuAttn {
+  int64_t B, N;
+  int32_t H, Da, Dv, max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen, reserved;
+  float alpha;
+  int32_t reserved2;
+  uint64_t q;                        /* const float* [N, H, Da] */
+  int64_t q_stride, q_head_stride;
+  uint64_t k;                        /* const float* [N, H, Da] */
+  int64_t k_stride, k_head_stride;
+  uint64_t v;                        /* const float* [N, H, Dv] */
+  int64_t v_stride, v_head_stride;
+  uint64_t offsets;                  /* const int64_t* [B + 1] */
+  uint64_t num_targets;              /* const int64_t* [B], nullable */
+  uint64_t out;                      /* float* [N, H, Dv]        (forward writes) */
+  int64_t out_stride, out_head_stride;
+  uint64_t grad_out;                 /* const float* [N, H, Dv]  (backward) */
+  int64_t grad_out_stride, grad_out_head_stride;
+  uint64_t dq;                       /* float* [N, H, Da]        (backward) */
+  int64_t dq_stride, dq_head_stride;
+  uint64_t dk;                       /* float* [N, H, Da]        (backward) */
+  int64_t dk_stride, dk_head_stride;
+  uint64_t dv;                       /* float* [N, H, Dv]        (backward) */
+  int64_t dv_stride, dv_head_stride;
+} TzrHstuAttn;
+int tzr_hstu_attn_fwd(const TzrHstuAttn* h_at, void* stream);
+int tzr_hstu_attn_bwd(const TzrHstuAttn* h_at, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

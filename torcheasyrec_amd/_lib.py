@@ -217,6 +217,28 @@ class TzrMwdin(C.Structure):
 
 
 assert C.sizeof(TzrMwdin) == 400
+# limits and tile sizes of tzr_hstu_attn_* (include/tzrec_hip.h: TZR_HSTU_*)
+HSTU_MAX_DIM, HSTU_MAX_SEQ_LEN, HSTU_BLOCK, HSTU_TILE = 128, 268435456, 64, 16
+
+
+class TzrHstuAttn(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("N", C.c_int64), ("H", C.c_int32), ("Da", C.c_int32), ("Dv", C.c_int32), ("max_seq_len", C.c_int32),
+        ("max_attn_len", C.c_int32), ("contextual_seq_len", C.c_int32), ("scaling_seqlen", C.c_int32), ("reserved", C.c_int32),
+        ("alpha", C.c_float), ("reserved2", C.c_int32),
+        ("q", C.c_uint64), ("q_stride", C.c_int64), ("q_head_stride", C.c_int64),
+        ("k", C.c_uint64), ("k_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v", C.c_uint64), ("v_stride", C.c_int64), ("v_head_stride", C.c_int64),
+        ("offsets", C.c_uint64), ("num_targets", C.c_uint64),
+        ("out", C.c_uint64), ("out_stride", C.c_int64), ("out_head_stride", C.c_int64),
+        ("grad_out", C.c_uint64), ("grad_out_stride", C.c_int64), ("grad_out_head_stride", C.c_int64),
+        ("dq", C.c_uint64), ("dq_stride", C.c_int64), ("dq_head_stride", C.c_int64),
+        ("dk", C.c_uint64), ("dk_stride", C.c_int64), ("dk_head_stride", C.c_int64),
+        ("dv", C.c_uint64), ("dv_stride", C.c_int64), ("dv_head_stride", C.c_int64),
+    ]
+
+
+assert C.sizeof(TzrHstuAttn) == 264
 
 
 class TzrSparseOptim(C.Structure):
@@ -465,6 +487,8 @@ _SIGNATURES = {
     "tzr_mwdin_workspace": (_sz, [_vp]),
     "tzr_mwdin_fwd": (_i32, [_vp, _vp]),
     "tzr_mwdin_bwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_attn_fwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_attn_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
@@ -628,6 +652,16 @@ def rows3_ok(t: torch.Tensor) -> bool:
     """fp32 [B, K, D] whose B K rows lie one row stride apart: a `rows_ok` operand [B K, D] (a column slice of a [B K, .] buffer is)"""
     s0, s1, s2 = t.stride()
     return t.dtype == torch.float32 and s2 == 1 and s1 % 4 == 0 and s1 >= t.shape[2] and s0 == t.shape[1] * s1 and t.data_ptr() % 16 == 0
+
+
+def heads_ok(t: torch.Tensor) -> bool:
+    """what `tzr_hstu_attn_*` takes as an [N, H, D] operand by row and head stride: fp32, unit column stride, both strides multiples
+    of 4 floats, heads and rows that share no float, 16-byte aligned data (the [N, H D] column slice of a wider matrix, viewed
+    [N, H, D], passes)"""
+    if t.dim() != 3 or t.dtype != torch.float32:
+        return False
+    (_, H, D), (rs, hs, one) = t.shape, t.stride()
+    return one == 1 and rs % 4 == 0 and hs % 4 == 0 and hs >= D and rs >= (H - 1) * hs + D and t.data_ptr() % 16 == 0
 
 
 def rows16(t: torch.Tensor) -> torch.Tensor:

@@ -1,0 +1,263 @@
+"""HSTU's jagged pointwise-SiLU attention and the STU layer around it (tzrec/ops/hstu_attention.py::hstu_mha,
+tzrec/modules/gr/stu.py: STULayer, STUStack): the operation under hstu_match, dlrm_hstu and ultra_hstu.
+
+`hstu_mha` runs csrc/hstu_attention.hip (tzr_hstu_attn_fwd / _bwd: one launch forward, two backward, nothing of size N x N in
+memory, work following sum(n_i^2)) when FUSED_HSTU_MHA is on and `hstu_mha_ok` takes the operands; otherwise -- the switch off, a
+shape outside `hstu_mha_limit`, a double backward -- the literal padded form [B, H, N, N] out of plain torch ops.  Built: causal,
+no attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32; the rest is refused by name.  Everything around the
+attention in the layer (norms, the uvqk and output products) stays torch ops."""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import _lib
+
+FUSED_HSTU_MHA = True  # profiles/hstu_attention, forward + backward: 24.4 ms fused against 32.4 ms literal, 0.72 against 14.06 GB
+
+
+def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int) -> torch.Tensor:
+    """_get_valid_attn_mask (tzrec/ops/_pytorch/pt_hstu_attention.py) with causal=True on the rows each sample keeps: n [B] -> bool [B, N, N]"""
+    ids = torch.arange(N, device=n.device).view(1, N)
+    max_ids = n.view(-1, 1)
+    if contextual_seq_len > 0:
+        ids = torch.clamp(ids - contextual_seq_len + 1, min=0)
+        max_ids = max_ids - contextual_seq_len + 1
+    if num_targets is not None:
+        max_ids = max_ids - num_targets.view(-1, 1)
+        ids = torch.minimum(ids, max_ids)
+    ids = ids.expand(n.numel(), N)
+    row, col, max_ids = ids.unsqueeze(2), ids.unsqueeze(1), max_ids.unsqueeze(2)
+    dist = row - col
+    valid = torch.eye(N, device=n.device, dtype=torch.bool).unsqueeze(0) | (dist > 0)
+    if max_attn_len > 0:
+        valid = valid & (dist <= max_attn_len)
+    if contextual_seq_len > 0:
+        valid = valid | ((row == 0) & (col < max_ids))
+    return valid
+
+
+def hstu_mha_literal(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+                     num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0,
+                     scaling_seqlen: int = -1) -> torch.Tensor:
+    """The reference's padded form (pytorch_hstu_mha) out of plain torch ops: pads to [B, H, N, .], builds the [B, H, N, N] scores.
+    A sample keeps its first max_seq_len rows; the rows behind them get zero output."""
+    L, H, _ = q.shape
+    N, B = int(max_seq_len), seq_offsets.numel() - 1
+    scale = float(scaling_seqlen if scaling_seqlen > 0 else max_seq_len)
+    n = torch.clamp(seq_offsets[1:] - seq_offsets[:-1], max=N)
+    pos = torch.arange(N, device=q.device).view(1, N)
+    keep = pos < n.view(-1, 1)
+    # a position a sample does not have reads a later row (wrapping over a spare zero row behind the last) and is zeroed by `keep`:
+    # one shared padding row would take every padded position's (zero) gradient in the gather's backward, a scatter that
+    # serialises on the one row -- 62 of 94 ms of a pass at the profile's shape (NOTES.md; capsule_literal pads the same way)
+    idx = (seq_offsets[:-1].view(-1, 1) + pos) % (L + 1)
+
+    def pad(x):  # [L, H, D] -> [B, H, N, D], zeros for the rows a sample does not have
+        rows = torch.cat([x.reshape(L, -1), x.new_zeros(1, x.shape[1] * x.shape[2])])[idx]
+        return torch.where(keep.unsqueeze(2), rows, rows.new_zeros(())).view(B, N, H, x.shape[2]).transpose(1, 2)
+
+    qk = F.silu(torch.einsum("bhxa,bhya->bhxy", pad(q), pad(k)) * alpha) / scale
+    qk = qk * hstu_valid_mask(n, N, num_targets, max_attn_len, contextual_seq_len).unsqueeze(1)
+    dense = torch.einsum("bhxy,bhyv->bhxv", qk, pad(v)).transpose(1, 2)  # [B, N, H, V]
+    return v.new_zeros(L, H, v.shape[2]).index_put((idx[keep],), dense[keep])
+
+
+def hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, max_attn_len: int = 0, contextual_seq_len: int = 0, B: int = 1) -> Optional[str]:
+    """None when tzr_hstu_attn_* has a kernel for the shape, else the limit of csrc/hstu_attention.hip it misses (include/tzrec_hip.h)"""
+    D, S = _lib.HSTU_MAX_DIM, _lib.HSTU_MAX_SEQ_LEN
+    for name, d in (("attention_dim", Da), ("hidden_dim", Dv)):
+        if d % 4 or not 4 <= d <= D:
+            return f"{name} {d} must be a multiple of 4 in [4, {D}]"
+    if H < 1:
+        return f"num_heads {H} must be at least 1"
+    if not 1 <= max_seq_len <= S:
+        return f"max_seq_len {max_seq_len} must be in [1, {S}]"
+    if not 0 <= max_attn_len <= S:
+        return f"max_attn_len {max_attn_len} must be in [0, {S}]"
+    if not 0 <= contextual_seq_len <= S:
+        return f"contextual_seq_len {contextual_seq_len} must be in [0, {S}]"
+    if (max_seq_len + _lib.HSTU_BLOCK - 1) // _lib.HSTU_BLOCK * max(B, 1) * H >= 2 ** 31:
+        return f"grid: ceil({max_seq_len} / {_lib.HSTU_BLOCK}) x {B} x {H} workgroups must stay below 2^31"
+    return None
+
+
+def hstu_mha_ok(max_seq_len: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+                num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0) -> bool:
+    """what tzr_hstu_attn_* takes: q, k [L, H, Da], v [L, H, Dv] as `_lib.heads_ok` operands (column slices of one uvqk matrix
+    are fine), offsets int64 [B + 1] and num_targets int64 [B] contiguous, a shape inside `hstu_mha_limit`, everything on the
+    device of the loaded library"""
+    if q.dim() != 3 or k.shape != q.shape or v.dim() != 3 or v.shape[:2] != q.shape[:2] or seq_offsets.dim() != 1 or seq_offsets.numel() < 1:
+        return False
+    dev, (L, H, Da), B = q.device, q.shape, seq_offsets.numel() - 1
+    if not _lib.takes(q) or any(t.device != dev for t in (k, v, seq_offsets)) or L >= 2 ** 31:
+        return False
+    if hstu_mha_limit(H, Da, v.shape[2], max_seq_len, max_attn_len, contextual_seq_len, B) is not None or (B == 0 and L > 0):
+        return False  # (no sample, yet rows: the entry points launch nothing, so nobody would write the rows)
+    if seq_offsets.dtype != torch.int64 or not seq_offsets.is_contiguous():
+        return False
+    if num_targets is not None and not (num_targets.shape == (B,) and num_targets.dtype == torch.int64 and num_targets.is_contiguous() and num_targets.device == dev):
+        return False
+    return L == 0 or all(_lib.heads_ok(t) for t in (q, k, v))
+
+
+def _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen):
+    m.B, m.N, m.H, m.Da, m.Dv = seq_offsets.numel() - 1, q.shape[0], q.shape[1], q.shape[2], v.shape[2]
+    m.max_seq_len, m.max_attn_len, m.contextual_seq_len, m.scaling_seqlen, m.alpha = max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen, alpha
+    m.offsets, m.num_targets = _lib.ptr(seq_offsets), _lib.opt_ptr(num_targets)
+    _operands(m, q=q, k=k, v=v)
+
+
+def _operands(m, **tensors):
+    for name, t in tensors.items():
+        if t.shape[0] > 0:
+            setattr(m, name, _lib.ptr(t))
+        setattr(m, name + "_stride", t.stride(0) if t.shape[0] > 1 else max(t.stride(0), (t.shape[1] - 1) * t.stride(1) + t.shape[2]))
+        setattr(m, name + "_head_stride", t.stride(1) if t.shape[1] > 1 else max(t.stride(1), t.shape[2]))
+
+
+def hstu_attn_fwd(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen) -> torch.Tensor:
+    """tzr_hstu_attn_fwd on operands `hstu_mha_ok` took -> out [L, H, Dv] (torch.empty: the kernel writes every row)"""
+    out = torch.empty(q.shape[0], q.shape[1], v.shape[2], dtype=torch.float32, device=q.device)
+    m = _lib.TzrHstuAttn()
+    _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
+    _operands(m, out=out)
+    _lib.launch("tzr_hstu_attn_fwd", m, q.device)
+    return out
+
+
+def hstu_attn_bwd(gout, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len,
+                  scaling_seqlen) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """tzr_hstu_attn_bwd -> dq, dk, dv: column slices of ONE [L, H (2 Da + Dv)] buffer, every row written by the kernels"""
+    (L, H, Da), Dv = q.shape, v.shape[2]
+    g = gout.to(torch.float32)
+    if L > 0 and not _lib.heads_ok(g):
+        g = g.clone(memory_format=torch.contiguous_format)  # (.contiguous() keeps the odd strides of a one-row gradient: _lib.rows16)
+    buf = torch.empty(L, H * (2 * Da + Dv), dtype=torch.float32, device=q.device)
+    dq, dk, dv = (t.view(L, H, d) for t, d in zip(torch.split(buf, [H * Da, H * Da, H * Dv], dim=1), (Da, Da, Dv)))
+    m = _lib.TzrHstuAttn()
+    _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
+    _operands(m, grad_out=g, dq=dq, dk=dk, dv=dv)
+    _lib.launch("tzr_hstu_attn_bwd", m, q.device)
+    return dq, dk, dv
+
+
+class _HstuMhaFn(torch.autograd.Function):
+    """Saved for the backward: the inputs alone -- the backward recomputes every score tile.  Capturable: every buffer is torch's,
+    nothing is read back.  Differentiable once (`hstu_mha(.., double_backward=True)` takes the literal form)."""
+
+    calls = 0  # forwards that took the kernel (tests)
+
+    @staticmethod
+    def forward(ctx, q, k, v, seq_offsets, num_targets, cfg):
+        _HstuMhaFn.calls += 1
+        max_seq_len, alpha, rest = cfg[0], cfg[1], cfg[2:]
+        ctx.save_for_backward(q, k, v, seq_offsets, num_targets)
+        ctx.cfg = cfg
+        return hstu_attn_fwd(max_seq_len, alpha, q.detach(), k.detach(), v.detach(), seq_offsets, num_targets, *rest)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        q, k, v, seq_offsets, num_targets = ctx.saved_tensors
+        dq, dk, dv = hstu_attn_bwd(gout, ctx.cfg[0], ctx.cfg[1], q, k, v, seq_offsets, num_targets, *ctx.cfg[2:])
+        return dq, dk, dv, None, None, None
+
+
+def hstu_mha(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+             causal: bool = True, dropout_pr: float = 0.0, training: bool = True, num_targets: Optional[torch.Tensor] = None,
+             max_attn_len: int = 0, contextual_seq_len: int = 0, min_full_attn_seq_len: int = 0, sort_by_length: bool = False,
+             attn_func: Optional[torch.Tensor] = None, scaling_seqlen: int = -1, double_backward: bool = False) -> torch.Tensor:
+    """The reference's hstu_mha: q, k [L, H, Da], v [L, H, Dv] jagged by seq_offsets [B + 1] -> [L, H, Dv].  `sort_by_length`
+    changes no result (the kernels issue the long blocks first themselves)."""
+    if not causal:
+        raise NotImplementedError("hstu_mha: causal=False is not built")
+    if dropout_pr > 0.0:
+        raise NotImplementedError("hstu_mha: dropout_pr > 0 (attention dropout) is not built")
+    if min_full_attn_seq_len > 0:
+        raise NotImplementedError("hstu_mha: min_full_attn_seq_len > 0 is not built")
+    if attn_func is not None:
+        raise NotImplementedError("hstu_mha: attn_func (SLA / NFUNC masks) is not built")
+    max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen = int(max_seq_len), int(max_attn_len), int(contextual_seq_len), int(scaling_seqlen)
+    if FUSED_HSTU_MHA and not double_backward and (q.is_cuda or _lib.emulated()) and q.dtype == torch.float32 and \
+            hstu_mha_ok(max_seq_len, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len):
+        return _HstuMhaFn.apply(q, k, v, seq_offsets, num_targets, (max_seq_len, float(alpha), max_attn_len, contextual_seq_len, scaling_seqlen))
+    return hstu_mha_literal(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
+
+
+class STULayer(nn.Module):
+    """One STU layer (constructor arguments and parameter names of the reference's STULayer): LayerNorm(eps 1e-6) -> addmm with
+    `_uvqk_weight` -> split u, v, q, k with SiLU on u -> `hstu_mha` on the slices where the product left them (no copy) ->
+    u * norm(attn) (layer or group norm) -> [u, attn, y] -> dropout -> addmm(x, ., `_output_weight`).  `recompute_*` and
+    `sort_by_length` are accepted and change no result."""
+
+    def __init__(self, embedding_dim: int, num_heads: int, hidden_dim: int, attention_dim: int, output_dropout_ratio: float = 0.3,
+                 causal: bool = True, target_aware: bool = True, max_attn_len: Optional[int] = None, attn_alpha: Optional[float] = None,
+                 use_group_norm: bool = False, recompute_normed_x: bool = True, recompute_uvqk: bool = True, recompute_y: bool = True,
+                 sort_by_length: bool = True, contextual_seq_len: int = 0, sla_k1: int = 0, sla_k2: int = 0, scaling_seqlen: int = -1,
+                 is_inference: bool = False) -> None:
+        super().__init__()
+        if sla_k1 > 0 or sla_k2 > 0:
+            raise NotImplementedError("STULayer: sla_k1 / sla_k2 (SLA masks) are not built")
+        if not causal:
+            raise NotImplementedError("STULayer: causal=False is not built")
+        self._num_heads, self._embedding_dim, self._hidden_dim, self._attention_dim = num_heads, embedding_dim, hidden_dim, attention_dim
+        self._output_dropout_ratio, self._target_aware = output_dropout_ratio, target_aware
+        self._max_attn_len = max_attn_len or 0
+        self._attn_alpha = attn_alpha or 1.0 / (attention_dim ** 0.5)
+        self._use_group_norm, self._contextual_seq_len, self._scaling_seqlen = use_group_norm, contextual_seq_len, scaling_seqlen
+        width = (hidden_dim * 2 + attention_dim * 2) * num_heads
+        self._uvqk_weight = nn.Parameter(torch.empty(embedding_dim, width))
+        nn.init.xavier_uniform_(self._uvqk_weight)
+        self._uvqk_beta = nn.Parameter(torch.zeros(width))
+        self._input_norm_weight = nn.Parameter(torch.ones(embedding_dim))
+        self._input_norm_bias = nn.Parameter(torch.zeros(embedding_dim))
+        self._output_weight = nn.Parameter(torch.empty(hidden_dim * num_heads * 3, embedding_dim))
+        nn.init.xavier_uniform_(self._output_weight)
+        norm_shape = num_heads if use_group_norm else hidden_dim * num_heads
+        self._output_norm_weight = nn.Parameter(torch.ones(norm_shape))
+        self._output_norm_bias = nn.Parameter(torch.zeros(norm_shape))
+
+    def forward(self, x: torch.Tensor, x_offsets: torch.Tensor, max_seq_len: int, num_targets: Optional[torch.Tensor] = None,
+                max_kv_caching_len: int = 0, kv_caching_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if max_kv_caching_len > 0 or kv_caching_lengths is not None:
+            raise NotImplementedError("STULayer: max_kv_caching_len / kv_caching_lengths (the kv cache) are not built")
+        H, Dv, Da = self._num_heads, self._hidden_dim, self._attention_dim
+        normed = F.layer_norm(x, (self._embedding_dim,), self._input_norm_weight, self._input_norm_bias, 1e-6)
+        uvqk = torch.addmm(self._uvqk_beta, normed, self._uvqk_weight)
+        u, v, q, k = torch.split(uvqk, [Dv * H, Dv * H, Da * H, Da * H], dim=1)
+        u, L = F.silu(u), x.shape[0]
+        attn = hstu_mha(max_seq_len, self._attn_alpha, q.view(L, H, Da), k.view(L, H, Da), v.view(L, H, Dv), x_offsets,
+                        num_targets=num_targets if self._target_aware else None, max_attn_len=self._max_attn_len,
+                        contextual_seq_len=self._contextual_seq_len, scaling_seqlen=self._scaling_seqlen).reshape(L, H * Dv)
+        if self._use_group_norm:
+            y = u * F.group_norm(attn.view(L, H, Dv), H, self._output_norm_weight, self._output_norm_bias, 1e-6).view(L, H * Dv)
+        else:
+            y = u * F.layer_norm(attn, (H * Dv,), self._output_norm_weight, self._output_norm_bias, 1e-6)
+        y = F.dropout(torch.cat([u, attn, y], dim=1), p=self._output_dropout_ratio, training=self.training)
+        return torch.addmm(x, y, self._output_weight)
+
+    def cached_forward(self, *args, **kwargs):
+        raise NotImplementedError("STULayer: cached_forward (the delta / kv-cache attention) is not built")
+
+
+class STUStack(nn.Module):
+    """The layers in order (the reference's STUStack without mid-stack truncation)"""
+
+    def __init__(self, stu_list: Sequence[nn.Module], truncate_split_layer: int = 0, truncate_tail_len: int = 0, is_inference: bool = False) -> None:
+        super().__init__()
+        if truncate_split_layer > 0 or truncate_tail_len > 0:
+            raise NotImplementedError("STUStack: truncate_split_layer / truncate_tail_len (mid-stack truncation) are not built")
+        self._stu_layers = nn.ModuleList(stu_list)
+
+    def forward(self, x: torch.Tensor, x_offsets: torch.Tensor, max_seq_len: int, num_targets: Optional[torch.Tensor] = None,
+                max_kv_caching_len: int = 0, kv_caching_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        for layer in self._stu_layers:
+            x = layer(x, x_offsets, max_seq_len, num_targets, max_kv_caching_len, kv_caching_lengths)
+        return x
+
+    def cached_forward(self, *args, **kwargs):
+        raise NotImplementedError("STUStack: cached_forward (the delta / kv-cache attention) is not built")

@@ -251,5 +251,50 @@ def _(tables, states, d_tables, d_feats, values, offsets, weights, grads, lr, st
     return None
 
 
+# ---- HSTU jagged attention ---------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::hstu_mha_fwd", mutates_args=())
+def hstu_mha_fwd(q: Tensor, k: Tensor, v: Tensor, seq_offsets: Tensor, num_targets: Optional[Tensor], max_seq_len: int, alpha: float,
+                 max_attn_len: int, contextual_seq_len: int, scaling_seqlen: int) -> Tensor:
+    """tzr_hstu_attn_fwd: q, k [L, H, Da], v [L, H, Dv] (operands `hstu.hstu_mha_ok` takes) -> [L, H, Dv]"""
+    from . import hstu
+
+    return hstu.hstu_attn_fwd(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
+
+
+@hstu_mha_fwd.register_fake
+def _(q, k, v, seq_offsets, num_targets, max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen):
+    return q.new_empty(q.shape[0], q.shape[1], v.shape[2], dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_NS}::hstu_mha_bwd", mutates_args=())
+def hstu_mha_bwd(gout: Tensor, q: Tensor, k: Tensor, v: Tensor, seq_offsets: Tensor, num_targets: Optional[Tensor], max_seq_len: int,
+                 alpha: float, max_attn_len: int, contextual_seq_len: int, scaling_seqlen: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """tzr_hstu_attn_bwd -> (dq, dk, dv)"""
+    from . import hstu
+
+    dq, dk, dv = hstu.hstu_attn_bwd(gout, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len,
+                                    scaling_seqlen)
+    # an op's outputs may not alias one another, and .contiguous() returns the slice itself where it is one row
+    return tuple(t.clone(memory_format=torch.contiguous_format) for t in (dq, dk, dv))
+
+
+@hstu_mha_bwd.register_fake
+def _(gout, q, k, v, seq_offsets, num_targets, max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen):
+    return (q.new_empty(q.shape, dtype=torch.float32), q.new_empty(q.shape, dtype=torch.float32), v.new_empty(v.shape, dtype=torch.float32))
+
+
+def _hstu_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:5])
+    ctx.cfg = inputs[5:]
+
+
+def _hstu_backward(ctx, gout):
+    dq, dk, dv = torch.ops.tzrec_hip.hstu_mha_bwd(gout, *ctx.saved_tensors, *ctx.cfg)
+    return (dq, dk, dv) + (None,) * 7
+
+
+hstu_mha_fwd.register_autograd(_hstu_backward, setup_context=_hstu_setup)
+
+
 OPS = ("dot_interaction_fwd", "dot_interaction_bwd", "fm_fwd", "fm_bwd", "kjt_permute", "block_bucketize", "pooled_fwd",
-       "pooled_bwd_adagrad", "pooled_bwd_rowwise_adagrad")
+       "pooled_bwd_adagrad", "pooled_bwd_rowwise_adagrad", "hstu_mha_fwd", "hstu_mha_bwd")
