@@ -1071,6 +1071,65 @@ typedef struct TzrHstuAttn {
 int tzr_hstu_attn_fwd(const TzrHstuAttn* h_at, void* stream);
 int tzr_hstu_attn_bwd(const TzrHstuAttn* h_at, void* stream);
 
+/* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
+ * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
+ *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied
+ *     nh = (attn - mean) rstd               attn [L, W]; layer norm: mean, rstd [L] over the W columns; group norm: [L, H] over the
+ *                                           Dv columns of each head; biased variance, rstd = 1 / sqrt(var + eps)
+ *     y  = us (nh gamma + beta)             gamma, beta [W] (layer norm) or [H] (group norm: the head's pair for its Dv columns)
+ *     C  = [us | attn | y] keep / (1 - p)   [L, 3 W], never in memory
+ *     out = x + C Wo                        x [L, E], Wo [3 W, E] contiguous
+ *   Dropout (training != 0 and p > 0; otherwise keep = 1 and nothing is read from `seed`): for row i and concat column c in
+ *   [0, 3 W), in 64-bit unsigned arithmetic (wrapping), with G = 0x9E3779B97F4A7C15 and s = the int64 at `seed` (DEVICE memory,
+ *   one element, read by the kernels: a captured launch replayed with another value there draws another mask):
+ *       z = s + (i 3 W + c + 1) G;   z = z + G;   z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9;   z = (z ^ (z >> 27)) 0x94D049BB133111EB;
+ *       z = z ^ (z >> 31);           keep(i, c) = (z >> 40) >= floor(p 2^24)       (p: the float of the struct; the last four
+ *   steps are zch_mix of csrc/zch.hip).  The factor 1 / (1 - p) is computed in float.  No mask is stored: the backward recomputes it.
+ *   backward from g = d out [L, E] (d x = g is the caller's: no copy):  dC = (g Wo^T) keep / (1 - p) = [dC_u | dC_a | dC_y];
+ *     du = (dC_u + dC_y (nh gamma + beta)) silu'(u), silu'(u) = sig (1 + u (1 - sig));   t = dC_y us gamma;
+ *     dattn = dC_a + rstd (t - mean_n(t) - nh mean_n(t nh))  (means over the norm's columns);   dgamma = sum dC_y us nh, dbeta = sum
+ *     dC_y us over the rows (group norm: and over the head's columns);   dWo = C^T g.
+ *   The forward writes mean / rstd, the backward reads them (and u, attn, gamma, beta, wo, seed, grad_out).  dgamma / dbeta: one
+ *   row of partial sums per TZR_STU_OUT_BLOCK rows in `ws` (tzr_stu_output_bwd_workspace), added in the interleaved order.  No
+ *   atomics, one owner and one order of additions per output element: two runs are bit-equal.
+ * Limits (TZR_ERR_UNSUPPORTED beyond, nothing launched): E and W multiples of 4 in [4, TZR_STU_OUT_MAX_DIM]; group norm: Dv a
+ *   multiple of 4; L < 2^31; row strides multiples of 4 floats and >= the width.  TZR_ERR_INVALID: L < 0, H or Dv < 1, p outside
+ *   [0, 1), a null or misaligned pointer (16 bytes; seed 8, and only where it is read).  TZR_ERR_WORKSPACE: ws null, not 256-byte
+ *   aligned or too small.  L == 0: TZR_OK without a launch, whatever the pointers are.  A new struct and entry points, no change
+ *   to existing ones: the ABI version stays 15. */
+#define TZR_STU_OUT_MAX_DIM 512
+#define TZR_STU_OUT_BLOCK 32
+typedef struct TzrStuOutput {
+  int64_t L;
+  int32_t E, H, Dv, group_norm, training, reserved;
+  float eps, p;
+  uint64_t u;                        /* const float* [L, W] */
+  int64_t u_stride;
+  uint64_t attn;                     /* const float* [L, W] */
+  int64_t attn_stride;
+  uint64_t x;                        /* const float* [L, E]      (forward) */
+  int64_t x_stride;
+  uint64_t gamma, beta;              /* const float* [W] or [H] */
+  uint64_t wo;                       /* const float* [3 W, E] */
+  uint64_t seed;                     /* const int64_t* [1], device memory; read when training and p > 0 */
+  uint64_t mean, rstd;               /* float* [L] or [L, H]     (forward writes, backward reads) */
+  uint64_t out;                      /* float* [L, E]            (forward writes) */
+  int64_t out_stride;
+  uint64_t grad_out;                 /* const float* [L, E]      (backward) */
+  int64_t grad_out_stride;
+  uint64_t du;                       /* float* [L, W]            (backward) */
+  int64_t du_stride;
+  uint64_t dattn;                    /* float* [L, W]            (backward) */
+  int64_t dattn_stride;
+  uint64_t dwo;                      /* float* [3 W, E]          (backward) */
+  uint64_t dgamma, dbeta;            /* float* [W] or [H]        (backward) */
+  uint64_t ws;                       /* workspace                (backward) */
+  uint64_t ws_bytes;
+} TzrStuOutput;
+int tzr_stu_output_fwd(const TzrStuOutput* h_so, void* stream);
+size_t tzr_stu_output_bwd_workspace(const TzrStuOutput* h_so);
+int tzr_stu_output_bwd(const TzrStuOutput* h_so, void* stream);
+
 /* Linear layers with a handful of output units, n_out <= 8: the logits layer of the rank models
  * (tzrec/models/rank_model.py:190-191) and the gates of MMoE (tzrec/modules/mmoe.py: Linear(in, num_expert)).
  * forward: d_y[b, j] = sum_k d_x[b, k] * d_w[j, k] + d_bias[j] (d_bias nullable); one pass over x.

@@ -239,6 +239,23 @@ class TzrHstuAttn(C.Structure):
 
 
 assert C.sizeof(TzrHstuAttn) == 264
+# limit and rows per workgroup of tzr_stu_output_* (include/tzrec_hip.h: TZR_STU_OUT_*)
+STU_OUT_MAX_DIM, STU_OUT_BLOCK = 512, 32
+
+
+class TzrStuOutput(C.Structure):
+    _fields_ = [
+        ("L", C.c_int64), ("E", C.c_int32), ("H", C.c_int32), ("Dv", C.c_int32), ("group_norm", C.c_int32), ("training", C.c_int32),
+        ("reserved", C.c_int32), ("eps", C.c_float), ("p", C.c_float),
+        ("u", C.c_uint64), ("u_stride", C.c_int64), ("attn", C.c_uint64), ("attn_stride", C.c_int64), ("x", C.c_uint64), ("x_stride", C.c_int64),
+        ("gamma", C.c_uint64), ("beta", C.c_uint64), ("wo", C.c_uint64), ("seed", C.c_uint64), ("mean", C.c_uint64), ("rstd", C.c_uint64),
+        ("out", C.c_uint64), ("out_stride", C.c_int64), ("grad_out", C.c_uint64), ("grad_out_stride", C.c_int64),
+        ("du", C.c_uint64), ("du_stride", C.c_int64), ("dattn", C.c_uint64), ("dattn_stride", C.c_int64),
+        ("dwo", C.c_uint64), ("dgamma", C.c_uint64), ("dbeta", C.c_uint64), ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrStuOutput) == 240
 
 
 class TzrSparseOptim(C.Structure):
@@ -489,6 +506,9 @@ _SIGNATURES = {
     "tzr_mwdin_bwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_fwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_bwd": (_i32, [_vp, _vp]),
+    "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
+    "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
+    "tzr_stu_output_bwd": (_i32, [_vp, _vp]),
     "tzr_skinny_linear_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "tzr_skinny_linear_bwd_workspace": (_sz, [_i64, _i32, _i32]),
     "tzr_skinny_linear_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),

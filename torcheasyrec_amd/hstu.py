@@ -4,8 +4,14 @@ tzrec/modules/gr/stu.py: STULayer, STUStack): the operation under hstu_match, dl
 `hstu_mha` runs csrc/hstu_attention.hip (tzr_hstu_attn_fwd / _bwd: one launch forward, two backward, nothing of size N x N in
 memory, work following sum(n_i^2)) when FUSED_HSTU_MHA is on and `hstu_mha_ok` takes the operands; otherwise -- the switch off, a
 shape outside `hstu_mha_limit`, a double backward -- the literal padded form [B, H, N, N] out of plain torch ops.  Built: causal,
-no attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32; the rest is refused by name.  Everything around the
-attention in the layer (norms, the uvqk and output products) stays torch ops."""
+no attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32; the rest is refused by name.
+
+`stu_output` is the layer's stage behind the attention (the reference's hstu_compute_output): silu(u), the layer or group norm of
+the attention's rows, their product, the concat [u, attn, y], dropout and addmm(x, ., `_output_weight`) on csrc/stu_output.hip
+(tzr_stu_output_fwd / _bwd: one launch forward, two backward and a finishing one; the concat, the normed rows and the dropout
+mask are never in memory, the mask follows the counter rule of include/tzrec_hip.h from a seed on the device) when
+FUSED_STU_OUTPUT is on and `stu_output_ok` takes the operands; otherwise `stu_output_literal`, the torch ops.  What stays torch ops
+in the layer: the input norm and the uvqk product in front of the attention."""
 from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple
@@ -16,6 +22,7 @@ from torch import nn
 
 from . import _lib
 
+FUSED_STU_OUTPUT = False  # profiles/stu_output, forward + backward: 6.20 ms fused against 2.84 ms literal (0.56 against 0.94 GB): the literal form stays
 FUSED_HSTU_MHA = True  # profiles/hstu_attention, forward + backward: 24.4 ms fused against 32.4 ms literal, 0.72 against 14.06 GB
 
 
@@ -188,10 +195,133 @@ def hstu_mha(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.Tensor, v
     return hstu_mha_literal(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
 
 
+def stu_output_literal(u: torch.Tensor, attn: torch.Tensor, x: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tensor,
+                       output_weight: torch.Tensor, num_heads: int, group_norm: bool, dropout_ratio: float, training: bool,
+                       eps: float = 1e-6) -> torch.Tensor:
+    """the stage out of plain torch ops, on the RAW u slice (silu not yet applied)"""
+    u, L, H = F.silu(u), x.shape[0], num_heads
+    Dv = attn.shape[1] // H
+    if group_norm:
+        y = u * F.group_norm(attn.view(L, H, Dv), H, norm_weight, norm_bias, eps).view(L, H * Dv)
+    else:
+        y = u * F.layer_norm(attn, (H * Dv,), norm_weight, norm_bias, eps)
+    y = F.dropout(torch.cat([u, attn, y], dim=1), p=dropout_ratio, training=training)
+    return torch.addmm(x, y, output_weight)
+
+
+def stu_output_limit(E: int, H: int, Dv: int, group_norm: bool) -> Optional[str]:
+    """None when tzr_stu_output_* has a kernel for the shape, else the limit of csrc/stu_output.hip it misses (include/tzrec_hip.h)"""
+    D = _lib.STU_OUT_MAX_DIM
+    if H < 1 or Dv < 1:
+        return f"num_heads {H} and hidden_dim {Dv} must be at least 1"
+    if E % 4 or not 4 <= E <= D:
+        return f"embedding_dim {E} must be a multiple of 4 in [4, {D}]"
+    if (H * Dv) % 4 or not 4 <= H * Dv <= D:
+        return f"num_heads x hidden_dim {H * Dv} must be a multiple of 4 in [4, {D}]"
+    if group_norm and Dv % 4:
+        return f"hidden_dim {Dv} must be a multiple of 4 under group norm"
+    return None
+
+
+def stu_output_ok(u: torch.Tensor, attn: torch.Tensor, x: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tensor,
+                  output_weight: torch.Tensor, num_heads: int, group_norm: bool, dropout_ratio: float = 0.0) -> bool:
+    """what tzr_stu_output_* takes: u, attn [L, W] and x [L, E] as `_lib.rows_ok` operands (u a column slice of the uvqk matrix),
+    the norm's pair [W] or [H] and the weight [3 W, E] contiguous fp32, a shape inside `stu_output_limit`, 0 <= p < 1, everything
+    on the device of the loaded library"""
+    if u.dim() != 2 or attn.shape != u.shape or x.dim() != 2 or x.shape[0] != u.shape[0] or num_heads < 1 or u.shape[1] % num_heads:
+        return False
+    dev, (L, W), E, H = x.device, u.shape, x.shape[1], num_heads
+    if not _lib.takes(x) or any(t.device != dev for t in (u, attn)) or L >= 2 ** 31 or not 0.0 <= dropout_ratio < 1.0:
+        return False
+    if stu_output_limit(E, H, W // H, group_norm) is not None:
+        return False
+    n = (H,) if group_norm else (W,)
+    if not (_lib.packed_ok(norm_weight, n, dev, True) and _lib.packed_ok(norm_bias, n, dev, True) and _lib.packed_ok(output_weight, (3 * W, E), dev, True)):
+        return False
+    return L == 0 or (_lib.rows_ok(u) and _lib.rows_ok(attn) and _lib.rows_ok(x))
+
+
+def _stu_fill(m, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd, cfg):
+    H, group_norm, p, training, eps = cfg
+    m.L, m.E, m.H, m.Dv = u.shape[0], output_weight.shape[1], H, u.shape[1] // H
+    m.group_norm, m.training, m.eps, m.p = int(group_norm), int(training), eps, p
+    m.u, m.u_stride, m.attn, m.attn_stride = _lib.ptr(u), _lib.scalar_row_stride(u), _lib.ptr(attn), _lib.scalar_row_stride(attn)
+    m.gamma, m.beta, m.wo, m.seed = _lib.ptr(norm_weight), _lib.ptr(norm_bias), _lib.ptr(output_weight), _lib.opt_ptr(seed)
+    m.mean, m.rstd = _lib.ptr(mean), _lib.ptr(rstd)
+
+
+def stu_output_fwd(u, attn, x, norm_weight, norm_bias, output_weight, seed, cfg) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """tzr_stu_output_fwd on operands `stu_output_ok` took -> out [L, E], mean, rstd [L] or [L, H] (the kernel writes every row)"""
+    L, groups = u.shape[0], cfg[0] if cfg[1] else 1
+    out = torch.empty(L, x.shape[1], dtype=torch.float32, device=x.device)
+    mean, rstd = torch.empty(L, groups, dtype=torch.float32, device=x.device), torch.empty(L, groups, dtype=torch.float32, device=x.device)
+    if L > 0:
+        m = _lib.TzrStuOutput()
+        _stu_fill(m, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd, cfg)
+        m.x, m.x_stride, m.out, m.out_stride = _lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr(out), out.shape[1]
+        _lib.launch("tzr_stu_output_fwd", m, x.device)
+    return out, mean, rstd
+
+
+def stu_output_bwd(gout, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd, cfg):
+    """tzr_stu_output_bwd -> du, dattn [L, W], dWo [3 W, E], dgamma, dbeta; every element written by the kernels (zeros at L == 0)"""
+    (L, W), E, dev = u.shape, output_weight.shape[1], u.device
+    if L == 0:
+        return u.new_zeros(0, W), u.new_zeros(0, W), torch.zeros_like(output_weight), torch.zeros_like(norm_weight), torch.zeros_like(norm_bias)
+    g = _lib.rows16(gout.to(torch.float32))
+    du, dattn = torch.empty(L, W, dtype=torch.float32, device=dev), torch.empty(L, W, dtype=torch.float32, device=dev)
+    dwo, dgamma, dbeta = torch.empty_like(output_weight), torch.empty_like(norm_weight), torch.empty_like(norm_bias)
+    m = _lib.TzrStuOutput()
+    _stu_fill(m, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd, cfg)
+    m.grad_out, m.grad_out_stride = _lib.ptr(g), _lib.scalar_row_stride(g)
+    m.du, m.du_stride, m.dattn, m.dattn_stride = _lib.ptr(du), W, _lib.ptr(dattn), W
+    m.dwo, m.dgamma, m.dbeta = _lib.ptr(dwo), _lib.ptr(dgamma), _lib.ptr(dbeta)
+    _lib.launch_ws("tzr_stu_output_bwd", m, dev, "tzr_stu_output_bwd")
+    return du, dattn, dwo, dgamma, dbeta
+
+
+class _StuOutputFn(torch.autograd.Function):
+    """Saved for the backward: the inputs, mean, rstd and the seed tensor -- nothing of width 3 W, no mask.  Capturable: every
+    buffer is torch's, the seed stays on the device.  Differentiable once (`stu_output(.., double_backward=True)` takes the
+    literal form)."""
+
+    calls = 0  # forwards that took the kernel (tests)
+
+    @staticmethod
+    def forward(ctx, u, attn, x, norm_weight, norm_bias, output_weight, seed, cfg):
+        _StuOutputFn.calls += 1
+        out, mean, rstd = stu_output_fwd(u.detach(), attn.detach(), x.detach(), norm_weight.detach(), norm_bias.detach(), output_weight.detach(), seed, cfg)
+        ctx.save_for_backward(u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        du, dattn, dwo, dgamma, dbeta = stu_output_bwd(gout, *ctx.saved_tensors, ctx.cfg)
+        return du, dattn, gout, dgamma, dbeta, dwo, None, None
+
+
+def stu_output(u: torch.Tensor, attn: torch.Tensor, x: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tensor,
+               output_weight: torch.Tensor, num_heads: int, group_norm: bool, dropout_ratio: float, training: bool, eps: float = 1e-6,
+               seed: Optional[torch.Tensor] = None, double_backward: bool = False) -> torch.Tensor:
+    """x + dropout([silu(u), attn, silu(u) norm(attn)]) @ output_weight: u the RAW [L, H Dv] slice of the uvqk matrix, attn [L, H Dv],
+    x [L, E].  `seed`: a one-element int64 tensor on the device, taken as given (tests); by default one is drawn on the device per
+    forward (nothing is read back: the op captures into a hipGraph, and a replay draws a new mask)."""
+    if FUSED_STU_OUTPUT and not double_backward and (x.is_cuda or _lib.emulated()) and x.dtype == torch.float32 and u.dtype == torch.float32 and \
+            attn.dtype == torch.float32 and stu_output_ok(u, attn, x, norm_weight, norm_bias, output_weight, num_heads, group_norm, dropout_ratio):
+        drop = bool(training) and dropout_ratio > 0.0
+        if drop and seed is None:
+            seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=x.device)
+        return _StuOutputFn.apply(u, attn, x, norm_weight, norm_bias, output_weight, seed if drop else None,
+                                  (int(num_heads), bool(group_norm), float(dropout_ratio), bool(training), float(eps)))
+    return stu_output_literal(u, attn, x, norm_weight, norm_bias, output_weight, num_heads, group_norm, dropout_ratio, training, eps)
+
+
 class STULayer(nn.Module):
     """One STU layer (constructor arguments and parameter names of the reference's STULayer): LayerNorm(eps 1e-6) -> addmm with
-    `_uvqk_weight` -> split u, v, q, k with SiLU on u -> `hstu_mha` on the slices where the product left them (no copy) ->
-    u * norm(attn) (layer or group norm) -> [u, attn, y] -> dropout -> addmm(x, ., `_output_weight`).  `recompute_*` and
+    `_uvqk_weight` -> split u, v, q, k -> `hstu_mha` on the slices where the product left them (no copy) -> `stu_output` on the raw
+    u slice: silu(u) * norm(attn) (layer or group norm) -> [u, attn, y] -> dropout -> addmm(x, ., `_output_weight`).  `recompute_*` and
     `sort_by_length` are accepted and change no result."""
 
     def __init__(self, embedding_dim: int, num_heads: int, hidden_dim: int, attention_dim: int, output_dropout_ratio: float = 0.3,
@@ -229,16 +359,12 @@ class STULayer(nn.Module):
         normed = F.layer_norm(x, (self._embedding_dim,), self._input_norm_weight, self._input_norm_bias, 1e-6)
         uvqk = torch.addmm(self._uvqk_beta, normed, self._uvqk_weight)
         u, v, q, k = torch.split(uvqk, [Dv * H, Dv * H, Da * H, Da * H], dim=1)
-        u, L = F.silu(u), x.shape[0]
+        L = x.shape[0]
         attn = hstu_mha(max_seq_len, self._attn_alpha, q.view(L, H, Da), k.view(L, H, Da), v.view(L, H, Dv), x_offsets,
                         num_targets=num_targets if self._target_aware else None, max_attn_len=self._max_attn_len,
                         contextual_seq_len=self._contextual_seq_len, scaling_seqlen=self._scaling_seqlen).reshape(L, H * Dv)
-        if self._use_group_norm:
-            y = u * F.group_norm(attn.view(L, H, Dv), H, self._output_norm_weight, self._output_norm_bias, 1e-6).view(L, H * Dv)
-        else:
-            y = u * F.layer_norm(attn, (H * Dv,), self._output_norm_weight, self._output_norm_bias, 1e-6)
-        y = F.dropout(torch.cat([u, attn, y], dim=1), p=self._output_dropout_ratio, training=self.training)
-        return torch.addmm(x, y, self._output_weight)
+        return stu_output(u, attn, x, self._output_norm_weight, self._output_norm_bias, self._output_weight, H, self._use_group_norm,
+                          self._output_dropout_ratio, self.training)
 
     def cached_forward(self, *args, **kwargs):
         raise NotImplementedError("STULayer: cached_forward (the delta / kv-cache attention) is not built")

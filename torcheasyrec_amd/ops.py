@@ -296,5 +296,52 @@ def _hstu_backward(ctx, gout):
 hstu_mha_fwd.register_autograd(_hstu_backward, setup_context=_hstu_setup)
 
 
+# ---- the STU layer's output stage --------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::stu_output_fwd", mutates_args=())
+def stu_output_fwd(u: Tensor, attn: Tensor, x: Tensor, norm_weight: Tensor, norm_bias: Tensor, output_weight: Tensor, seed: Optional[Tensor],
+                   num_heads: int, group_norm: bool, dropout_ratio: float, training: bool, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """tzr_stu_output_fwd on operands `hstu.stu_output_ok` takes -> (out [L, E], mean, rstd [L, groups])"""
+    from . import hstu
+
+    return hstu.stu_output_fwd(u, attn, x, norm_weight, norm_bias, output_weight, seed, (num_heads, group_norm, dropout_ratio, training, eps))
+
+
+@stu_output_fwd.register_fake
+def _(u, attn, x, norm_weight, norm_bias, output_weight, seed, num_heads, group_norm, dropout_ratio, training, eps):
+    groups = num_heads if group_norm else 1
+    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty(x.shape[0], groups, dtype=torch.float32),
+            x.new_empty(x.shape[0], groups, dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{_NS}::stu_output_bwd", mutates_args=())
+def stu_output_bwd(gout: Tensor, u: Tensor, attn: Tensor, norm_weight: Tensor, norm_bias: Tensor, output_weight: Tensor, seed: Optional[Tensor],
+                   mean: Tensor, rstd: Tensor, num_heads: int, group_norm: bool, dropout_ratio: float, training: bool,
+                   eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """tzr_stu_output_bwd -> (du, dattn, dWo, dgamma, dbeta); d x is gout itself"""
+    from . import hstu
+
+    return hstu.stu_output_bwd(gout, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd,
+                               (num_heads, group_norm, dropout_ratio, training, eps))
+
+
+@stu_output_bwd.register_fake
+def _(gout, u, attn, norm_weight, norm_bias, output_weight, seed, mean, rstd, num_heads, group_norm, dropout_ratio, training, eps):
+    return (u.new_empty(u.shape, dtype=torch.float32), u.new_empty(u.shape, dtype=torch.float32), torch.empty_like(output_weight),
+            torch.empty_like(norm_weight), torch.empty_like(norm_bias))
+
+
+def _stu_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:2], *inputs[3:7], output[1], output[2])
+    ctx.cfg = inputs[7:]
+
+
+def _stu_backward(ctx, gout, gmean, grstd):
+    du, dattn, dwo, dgamma, dbeta = torch.ops.tzrec_hip.stu_output_bwd(gout, *ctx.saved_tensors, *ctx.cfg)
+    return (du, dattn, gout, dgamma, dbeta, dwo) + (None,) * 6
+
+
+stu_output_fwd.register_autograd(_stu_backward, setup_context=_stu_setup)
+
+
 OPS = ("dot_interaction_fwd", "dot_interaction_bwd", "fm_fwd", "fm_bwd", "kjt_permute", "block_bucketize", "pooled_fwd",
-       "pooled_bwd_adagrad", "pooled_bwd_rowwise_adagrad", "hstu_mha_fwd", "hstu_mha_bwd")
+       "pooled_bwd_adagrad", "pooled_bwd_rowwise_adagrad", "hstu_mha_fwd", "hstu_mha_bwd", "stu_output_fwd", "stu_output_bwd")
