@@ -29,7 +29,6 @@ struct AmmArgs {
   int64_t duas, dias;
 };
 
-__device__ __forceinline__ float amm_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 amm_diff(float4 a, float ra, float4 t, float rt) {
   return make_float4(a.x * ra - t.x * rt, a.y * ra - t.y * rt, a.z * ra - t.z * rt, a.w * ra - t.w * rt);
 }
@@ -37,13 +36,13 @@ __device__ __forceinline__ float4 amm_diff(float4 a, float ra, float4 t, float r
 // one side of one sample in the forward: -> l_b; *rn = 1 / n, NEGATED where |a| < 1e-12 (the backward's clamp branch), *rt = 1 /
 // max(|t|, 1e-12) under COSINE, else 1
 __device__ __forceinline__ float amm_side_fwd(float4 a, float4 t, int cosine, float* rn, float* rt) {
-  const float na = sqrtf(tzr_wave_sum(amm_dot4(a, a)));
+  const float na = sqrtf(tzr_wave_sum(tzr_dot4(a, a)));
   const float ra = 1.0f / fmaxf(na, AMM_EPS);
-  const float r = cosine ? 1.0f / fmaxf(sqrtf(tzr_wave_sum(amm_dot4(t, t))), AMM_EPS) : 1.0f;
+  const float r = cosine ? 1.0f / fmaxf(sqrtf(tzr_wave_sum(tzr_dot4(t, t))), AMM_EPS) : 1.0f;
   const float4 d = amm_diff(a, ra, t, r);
   *rn = na >= AMM_EPS ? ra : -ra;
   *rt = r;
-  return tzr_wave_sum(amm_dot4(d, d));
+  return tzr_wave_sum(tzr_dot4(d, d));
 }
 
 // grid ceil(B / 4).  rows [6, B]: l_u, l_i, 1/n_u, 1/n_i, 1/|t| of the user side's target, of the item side's
@@ -101,7 +100,7 @@ __device__ __forceinline__ float4 amm_side_bwd(float4 a, float4 t, float k, floa
   const float4 y = make_float4(a.x * ra, a.y * ra, a.z * ra, a.w * ra);
   const float k2 = 2.0f * k;
   const float4 dy = make_float4(k2 * (y.x - t.x * rt), k2 * (y.y - t.y * rt), k2 * (y.z - t.z * rt), k2 * (y.w - t.w * rt));
-  const float yd = tzr_wave_sum(amm_dot4(y, dy));
+  const float yd = tzr_wave_sum(tzr_dot4(y, dy));
   const float p = rn > 0.f ? yd : 0.f;  // (the clamp branch passes nothing through the norm)
   return make_float4((dy.x - y.x * p) * ra, (dy.y - y.y * p) * ra, (dy.z - y.z * p) * ra, (dy.w - y.w * p) * ra);
 }

@@ -40,8 +40,6 @@ static_assert(sizeof(TzrCapsule) == 192, "TzrCapsule: the layout _lib.py mirrors
 static_assert(CP_MAXD <= 2 * TZR_WAVE, "squash: two elements a lane");
 static_assert(CP_MAXS <= CP_THREADS, "softmax: one thread a position");
 
-typedef float cp_f4 __attribute__((ext_vector_type(4)));
-
 struct CpArgs {
   const float* X;
   const int64_t* off;
@@ -62,14 +60,10 @@ struct CpArgs {
   float* parts;
 };
 
-// sample b: its first row, its length, the rows that take part, its valid capsules (offsets outside [0, N] are clamped: no
-// access leaves the buffers whatever the offsets hold)
+// sample b: its first row, its length (the clamped span: no access leaves the buffers whatever the offsets hold), the rows that
+// take part, its valid capsules
 __device__ __forceinline__ void cp_sample(const CpArgs& A, int64_t b, int64_t* start, int64_t* len, int* s, int* kb) {
-  int64_t s0 = A.off[b], s1 = A.off[b + 1];
-  s0 = s0 < 0 ? 0 : (s0 > A.N ? A.N : s0);
-  s1 = s1 < s0 ? s0 : (s1 > A.N ? A.N : s1);
-  *start = s0;
-  *len = s1 - s0;
+  tzr_jagged_span(A.off, b, b + 1, A.N, start, len);
   *s = (int)(*len < (int64_t)A.S ? *len : (int64_t)A.S);
   int k = 0;
   for (int j = 0; j < A.K; ++j) k += ((int64_t)1 << j) < *len ? 1 : 0;
@@ -98,9 +92,8 @@ __global__ __launch_bounds__(CP_THREADS) void tzr_capsule_fwd_kernel(CpArgs A) {
     const int row = 16 * rb + li, col = 16 * ct + li;
     const bool rok = row < s, cok = col < H;
     const float* xp = A.X + (start + (rok ? row : 0)) * A.xs;  // (s > 0 here: row 0 exists)
-    cp_f4 acc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = cp_f4{0.f, 0.f, 0.f, 0.f};
+    tzr_f32x4 acc[4];
+    tzr_acc_zero(acc, 4);
     for (int k0 = 0; k0 < L; k0 += 16) {
       const int k = k0 + 4 * q;
       const bool kok = k < L;
@@ -108,12 +101,9 @@ __global__ __launch_bounds__(CP_THREADS) void tzr_capsule_fwd_kernel(CpArgs A) {
       float w[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) w[e] = cok && kok ? A.W[(int64_t)(k + e) * H + col] : 0.f;
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[0], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[1], acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[2], acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[3], acc[3], 0, 0, 0);
+      tzr_mfma4(a, make_float4(w[0], w[1], w[2], w[3]), acc);
     }
-    const cp_f4 u = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    const tzr_f32x4 u = tzr_join4(acc);
     if (cok) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) Us[(16 * rb + 4 * q + r) * HS + col] = u[r];
@@ -257,8 +247,7 @@ __global__ __launch_bounds__(CP_THREADS) void tzr_capsule_bwd_kernel(CpArgs A) {
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-static inline int64_t cp_bwd_grid(int64_t B) { return B < TZR_CAPSULE_BWD_MAX_GRID ? B : TZR_CAPSULE_BWD_MAX_GRID; }
-static inline size_t cp_ws_bytes(const TzrCapsule* c) { return tzr_align_up((size_t)cp_bwd_grid(c->B) * c->L * c->H * sizeof(float)); }
+static inline size_t cp_ws_bytes(const TzrCapsule* c) { return tzr_align_up((size_t)tzr_capped_grid(c->B, TZR_CAPSULE_BWD_MAX_GRID) * c->L * c->H * sizeof(float)); }
 
 static bool cp_limits(const TzrCapsule* c) {
   if (c->L < 4 || (c->L & 3) || c->L > CP_MAXD || c->H < 4 || (c->H & 3) || c->H > CP_MAXD) return false;
@@ -322,7 +311,7 @@ extern "C" int tzr_capsule_bwd(const TzrCapsule* h_cap, void* stream) {
   A.dxs = h_cap->dx_stride;
   A.parts = reinterpret_cast<float*>(h_cap->ws);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int G = (int)cp_bwd_grid(h_cap->B), LH = h_cap->L * h_cap->H;
+  const int G = (int)tzr_capped_grid(h_cap->B, TZR_CAPSULE_BWD_MAX_GRID), LH = h_cap->L * h_cap->H;
   if (LH <= 4096) hipLaunchKernelGGL(tzr_capsule_bwd_kernel<4096>, dim3((unsigned)G), dim3(CP_THREADS), 0, s, A);
   else hipLaunchKernelGGL(tzr_capsule_bwd_kernel<CP_MAXD * CP_MAXD>, dim3((unsigned)G), dim3(CP_THREADS), 0, s, A);
   TZR_CHECK_LAUNCH();

@@ -46,8 +46,6 @@
 #define CIN_TARGET_WGS 1024        // cin_bwd_w_kernel: parts of the column range until a launch has about this many workgroups,
 #define CIN_PART_FLOATS (512 << 10)  // while a layer's parts stay below this many floats (or 4 parts)
 
-typedef float cin_f4 __attribute__((ext_vector_type(4)));
-
 struct CinParams {
   const float* w[CIN_MAXL];  // W_i [O_i, H_i F]
   const float* c[CIN_MAXL];  // c_i [O_i]
@@ -55,8 +53,8 @@ struct CinParams {
   int O[CIN_MAXL];
 };
 
-__device__ __forceinline__ cin_f4 cin_zero() {
-  cin_f4 z = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ tzr_f32x4 cin_zero() {
+  tzr_f32x4 z = {0.f, 0.f, 0.f, 0.f};
   return z;
 }
 
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(CIN_THREADS) void cin_fwd_kernel(const float* __res
         const float* __restrict__ W = P.w[i];
         // two accumulators per tile, even and odd h: halves the length of each fp32 chain (H F / 2 terms) and keeps two
         // independent MFMAs in flight per tile
-        cin_f4 acc[4][2], acc1[4][2];
+        tzr_f32x4 acc[4][2], acc1[4][2];
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(CIN_THREADS) void cin_bwd_w_kernel(const float* __r
   const int64_t per = (chunks + gridDim.z - 1) / gridDim.z;
   const int64_t ch0 = per * blockIdx.z, ch1 = ch0 + per < chunks ? ch0 + per : chunks;
   part += (size_t)blockIdx.z * part_stride;
-  cin_f4 acc[4][4];
+  tzr_f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(CIN_THREADS) void cin_bwd_x_kernel(const float* __r
         if (q == 0 && nok[nt]) v = xi ? xi[(nb[nt] * H + h) * D + nd[nt]] : x[nb[nt] * xs + h * D + nd[nt]];
         xiv[nt] = __shfl(v, li);
       }
-      cin_f4 U[4][2];
+      tzr_f32x4 U[4][2];
 #pragma unroll
       for (int k = 0; k < 4; ++k) U[k][0] = U[k][1] = cin_zero();
       // W_i[o, h F + 16 k + li], row and column clamped into W and the value dropped afterwards: no branch around a load, and

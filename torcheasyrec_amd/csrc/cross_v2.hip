@@ -57,18 +57,11 @@
 #define CV_WG_THREADS 512
 #define CV_WG_WAVES (CV_WG_THREADS / TZR_WAVE)
 
-typedef float cv_f4 __attribute__((ext_vector_type(4)));
-
 struct CvParams {  // the layers' parameters: L separate [r, D], [D, r] and [D] tensors, passed by value
   const float* u[CV_MAXL];
   const float* v[CV_MAXL];
   const float* c[CV_MAXL];
 };
-
-__device__ __forceinline__ cv_f4 cv_zero() {
-  cv_f4 z = {0.f, 0.f, 0.f, 0.f};
-  return z;
-}
 
 // The partial [16, r] tile row of A W over the wave's quarter of K = D, into Tp[wv]: A(i, k) = Xs[i XS + k] (LDS), W(k, j) =
 // W[k wks + j wjs] (memory), j < R.  The same code is t_l = x_l U_l^T (wks = 1, wjs = D) and dt = dy V_l (wks = R, wjs = 1).
@@ -85,9 +78,9 @@ __device__ __forceinline__ void cv_split_k(const float* Xs, int XS, const float*
   for (int nt = 0; nt < NT; ++nt) {
     const int j = 16 * nt + li;
     const bool jok = j < R;
-    cv_f4 acc[CV_CHAINS];
+    tzr_f32x4 acc[CV_CHAINS];
 #pragma unroll
-    for (int c = 0; c < CV_CHAINS; ++c) acc[c] = cv_zero();
+    for (int c = 0; c < CV_CHAINS; ++c) acc[c] = tzr_acc_zero();
     for (int k0 = kb; k0 < ke; k0 += 4 * CV_CHAINS) {
 #pragma unroll
       for (int c = 0; c < CV_CHAINS; ++c) {
@@ -98,7 +91,7 @@ __device__ __forceinline__ void cv_split_k(const float* Xs, int XS, const float*
         acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kok ? a : 0.f, ok ? b : 0.f, acc[c], 0, 0, 0);
       }
     }
-    const cv_f4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    const tzr_f32x4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
 #pragma unroll
     for (int r = 0; r < 4; ++r) tp[(4 * q + r) * CV_RS + j] = sum[r];
   }
@@ -118,7 +111,7 @@ __device__ __forceinline__ void cv_join_k(const float* Tp, float* Ts, int R, flo
 
 // acc[u] += Ts[16, R] W over K = R for the wave's tiles wv + 4 (c0 + u), u = 0..3: W(k, j) = W[k wks + j wjs], j < D
 __device__ __forceinline__ void cv_tiles_r(const float* Ts, const float* __restrict__ W, int wks, int wjs, int D, int R, int c0, int wv, int q, int li,
-                                           cv_f4* acc) {
+                                           tzr_f32x4* acc) {
   const int DT = (D + 15) >> 4;
   for (int k0 = 0; k0 < R; k0 += 4) {
     const int k = k0 + q;
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(CV_THREADS) void tzr_cross_v2_fwd_kernel(const floa
   const int64_t nblk = (B + CV_ROWS - 1) / CV_ROWS;
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t b0 = blk * CV_ROWS;
-    cv_f4 x0[TPW], xl[TPW];
+    tzr_f32x4 x0[TPW], xl[TPW];
 #pragma unroll
     for (int a = 0; a < TPW; ++a) {
       const int tile = wv + CV_WAVES * a, col = 16 * tile + li;
@@ -177,7 +170,7 @@ __global__ __launch_bounds__(CV_THREADS) void tzr_cross_v2_fwd_kernel(const floa
       float* xo = last ? nullptr : (xsave ? xsave + (size_t)l * B * D : nullptr);
 #pragma unroll
       for (int c0 = 0; c0 < TPW; c0 += 4) {
-        cv_f4 acc[4] = {cv_zero(), cv_zero(), cv_zero(), cv_zero()};
+        tzr_f32x4 acc[4] = {tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero()};
         cv_tiles_r(Ts, P.v[l], 1, R, D, R, c0, wv, q, li, acc);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(CV_THREADS) void tzr_cross_v2_bwd_rows_kernel(const
   const int64_t nblk = (B + CV_ROWS - 1) / CV_ROWS;
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t b0 = blk * CV_ROWS;
-    cv_f4 x0[TPW], g[TPW], d0[TPW];
+    tzr_f32x4 x0[TPW], g[TPW], d0[TPW];
 #pragma unroll
     for (int a = 0; a < TPW; ++a) {
       const int col = 16 * (wv + CV_WAVES * a) + li;
@@ -244,7 +237,7 @@ __global__ __launch_bounds__(CV_THREADS) void tzr_cross_v2_bwd_rows_kernel(const
       float* dyl = dyw + (size_t)l * B * D;
 #pragma unroll
       for (int c0 = 0; c0 < TPW; c0 += 4) {
-        cv_f4 acc[4] = {cv_zero(), cv_zero(), cv_zero(), cv_zero()};
+        tzr_f32x4 acc[4] = {tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero()};
         cv_tiles_r(Ts, P.v[l], 1, R, D, R, c0, wv, q, li, acc);  // y_l - c_l by the forward's instruction sequence
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(CV_THREADS) void tzr_cross_v2_bwd_rows_kernel(const
       // magnitude; over eight layers that measured 5.4 x the literal form's distance to float64 in the bias gradient.
 #pragma unroll
       for (int c0 = 0; c0 < TPW; c0 += 4) {
-        cv_f4 acc[4] = {cv_zero(), cv_zero(), cv_zero(), cv_zero()};
+        tzr_f32x4 acc[4] = {tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero(), tzr_acc_zero()};
         cv_tiles_r(Ts, P.u[l], D, 1, D, R, c0, wv, q, li, acc);
 #pragma unroll
         for (int u = 0; u < 4; ++u) g[c0 + u] += acc[u];
@@ -308,9 +301,9 @@ __global__ __launch_bounds__(CV_WG_THREADS) void tzr_cross_v2_wgrad_kernel(const
   const float* pd = isv ? dyw + (size_t)l * B * D : (l == 0 ? x : xsave + (size_t)(l - 1) * B * D);
   const int64_t pds = isv || l > 0 ? (int64_t)D : xs;
   const float* pr = (isv ? tsave : dtw) + (size_t)l * B * R;
-  cv_f4 acc[CV_NT];
+  tzr_f32x4 acc[CV_NT];
 #pragma unroll
-  for (int nt = 0; nt < CV_NT; ++nt) acc[nt] = cv_zero();
+  for (int nt = 0; nt < CV_NT; ++nt) acc[nt] = tzr_acc_zero();
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
   const int64_t steps = (B + 3) >> 2;
   for (int64_t s0 = wv; s0 < steps; s0 += 4 * CV_WG_WAVES) {  // four of the wave's steps at a time: their loads in flight together

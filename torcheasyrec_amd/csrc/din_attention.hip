@@ -212,13 +212,6 @@ extern "C" int tzr_din_assemble2_bwd(const float* d_dX, int64_t x_stride, const 
 // ---- scores, softmax over a sample's positions, weighted sum of its rows: one wave per sample ------------------------
 // 16 lanes per position (float4 pieces of its row: a 64-float hidden row is one 256-byte read of the group), four positions
 // per wave pass; the group's dot product by a fixed shuffle tree.
-__device__ __forceinline__ float da_group16_sum(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
 
 // row_n . w for the positions [s, s + len) of one sample -> sc[0 .. len) (LDS of this wave); lanes (g = lane / 16, j = lane % 16)
 __device__ __forceinline__ void da_row_dots(const float* __restrict__ rows, int64_t stride, int64_t s, int len, int cols4,
@@ -242,7 +235,7 @@ __device__ __forceinline__ void da_row_dots(const float* __restrict__ rows, int6
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = i0 + 4 * u + g;
-      const float t = da_group16_sum(a[u]);
+      const float t = tzr_sum16(a[u]);
       if (i < len && j == 0) sc[i] = t + bias;
     }
   }

@@ -44,8 +44,6 @@ struct DistillArgs {
   float *loss, *scale, *parts;
 };
 
-__device__ __forceinline__ float dst_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
 // grid ceil(B / 4).  parts [G, P + 2]: sum_b q_p w (q: the cosine of the two rows, or |t - l|^2), sum_b h w, sum_b w
 __global__ __launch_bounds__(DST_THREADS) void tzr_distill_loss_fwd_kernel(DistillArgs A) {
   __shared__ float sm[DST_WAVES][DST_COLS];
@@ -65,10 +63,10 @@ __global__ __launch_bounds__(DST_THREADS) void tzr_distill_loss_fwd_kernel(Disti
         const float4 x = c < W ? tzr_ld4(lr + c) : tzr_zero4();
         const float4 y = c < W ? tzr_ld4(tr + c) : tzr_zero4();
         if (A.cosine) {
-          s0 += dst_dot4(x, x), s1 += dst_dot4(y, y), s2 += dst_dot4(x, y);
+          s0 += tzr_dot4(x, x), s1 += tzr_dot4(y, y), s2 += tzr_dot4(x, y);
         } else {
           const float4 d = make_float4(y.x - x.x, y.y - x.y, y.z - x.z, y.w - x.w);
-          s0 += dst_dot4(d, d);
+          s0 += tzr_dot4(d, d);
         }
       }
       if (A.cosine) {
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(DST_THREADS) void tzr_distill_loss_bwd_kernel(Disti
         const int c = c0 + 4 * lane;
         const float4 x = c < W ? tzr_ld4(lr + c) : tzr_zero4();
         const float4 y = c < W ? tzr_ld4(tr + c) : tzr_zero4();
-        s0 += dst_dot4(x, x), s1 += dst_dot4(y, y), s2 += dst_dot4(x, y);
+        s0 += tzr_dot4(x, x), s1 += tzr_dot4(y, y), s2 += tzr_dot4(x, y);
       }
       const float nl = sqrtf(tzr_wave_sum(s0));
       const float rl = 1.0f / fmaxf(nl, DST_EPS), rt = 1.0f / fmaxf(sqrtf(tzr_wave_sum(s1)), DST_EPS);

@@ -258,6 +258,7 @@ static int gm_run(const Mix* m, int G, bool subset, bool fwd, GmArgs& A, void* s
 }
 
 // tzr_moe_mix_*: whatever is wrong with an operand is TZR_ERR_INVALID; a row stride below H is not looked at
+// (not tzr_rows_operand: that one answers TZR_ERR_UNSUPPORTED for a stride that is no multiple of 4 or is below H)
 static bool mx_rows_bad(uint64_t ptr, int64_t stride) { return !ptr || (stride & 3) || (ptr & 15); }
 
 static int mx_mix(const TzrMoeMix* m, bool fwd, void* stream) {

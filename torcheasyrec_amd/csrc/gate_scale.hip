@@ -46,7 +46,7 @@ struct GsArgs {
   int64_t dg_stride[GS_N];
 };
 
-// s = sigmoid(x); *sq = s (1 - s)
+// s = sigmoid(x); *sq = s (1 - s)  (not tzr_sigmoid: the overflow-safe form through exp(-|x|), other roundings for x < 0)
 __device__ __forceinline__ float gs_sigmoid(float x, float* sq) {
   float e = expf(-fabsf(x));
   if (e < 1.17549435e-38f) e = 0.f;

@@ -31,8 +31,6 @@
 #define GR_MAX_WG 768
 #define GR_WG_MAX_WG 512
 
-typedef float gr_f32x4 __attribute__((ext_vector_type(4)));
-
 int g_tzr_gemm_rows_wg = 0;  // tzr_tune("gemm_rows_wg"): > 0 caps the workgroups of both kernels (tests: many tiles per workgroup)
 
 // ---- out = act(in W + bias) ------------------------------------------------------------------------------------------
@@ -66,11 +64,11 @@ __global__ __launch_bounds__(WAVES* TZR_WAVE) TZR_WAVES_PER_EU(WPE) void tzr_gem
 #pragma unroll
       for (int s = 0; s < KS; ++s) Wa[jb][s] = tzr_ldg(W + (int64_t)(16 * (s >> 2) + 4 * q + (s & 3)) * w_stride + cb + 16 * jb + r);
   }
-  gr_f32x4 bv[HB];  // the accumulators START from the bias
+  tzr_f32x4 bv[HB];  // the accumulators START from the bias
 #pragma unroll
   for (int jb = 0; jb < HB; ++jb) {
     const float4 b4 = bias ? tzr_ldg4(bias + cb + 16 * jb + 4 * q) : tzr_zero4();
-    bv[jb] = gr_f32x4{b4.x, b4.y, b4.z, b4.w};
+    bv[jb] = tzr_f32x4{b4.x, b4.y, b4.z, b4.w};
   }
   // the thread's pieces of a turn's rows (a piece index beyond the tile: the thread repeats its first piece -- no branch in the loop)
   int srow[NST], sc4[NST];
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(WAVES* TZR_WAVE) TZR_WAVES_PER_EU(WPE) void tzr_gem
         for (int jb = 0; jb < HB; ++jb) rv[tt][jb] = tzr_ldg4(rp + 16 * jb);
       }
     }
-    gr_f32x4 acc[TT][HB];
+    tzr_f32x4 acc[TT][HB];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
@@ -240,11 +238,11 @@ __global__ __launch_bounds__(WAVES* TZR_WAVE) TZR_WAVES_PER_EU(WPE) void tzr_gem
     if (skind[i] == 0) tzr_st4(&TG[b][srow[i] * SG + 4 * sc4[i]], v);
     else if (skind[i] == 1) tzr_st4(&TX[b][srow[i] * SX + 4 * sc4[i]], v);
   };
-  gr_f32x4 acc[HBW][KB];
+  tzr_f32x4 acc[HBW][KB];
 #pragma unroll
   for (int i = 0; i < HBW; ++i)
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) acc[i][kb] = gr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < KB; ++kb) acc[i][kb] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   const int64_t nblocks = (N + GR_TS - 1) / GR_TS;
   int64_t t = blockIdx.x;
   if (t < nblocks) {

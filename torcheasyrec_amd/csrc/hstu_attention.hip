@@ -40,8 +40,6 @@
 static_assert(sizeof(TzrHstuAttn) == 264, "TzrHstuAttn: the layout _lib.py mirrors");
 static_assert(HS_BLOCK == 64 && HS_TILE == 16, "four waves of one 16 x 16 MFMA tile each");
 
-typedef float hs_f4 __attribute__((ext_vector_type(4)));
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define HS_NOPK __attribute__((target("no-packed-fp32-ops")))
 #else
@@ -69,10 +67,7 @@ struct HsSample {
 
 __device__ __forceinline__ HsSample hs_sample(const HsArgs& A, int b) {
   HsSample S;
-  int64_t s0 = A.off[b], s1 = A.off[b + 1];  // (offsets outside [0, N] are clamped: no access leaves the buffers)
-  s0 = s0 < 0 ? 0 : (s0 > A.N ? A.N : s0);
-  s1 = s1 < s0 ? s0 : (s1 > A.N ? A.N : s1);
-  S.start = s0, S.len = s1 - s0;
+  tzr_jagged_span(A.off, b, b + 1, A.N, &S.start, &S.len);
   S.n = (int)(S.len < (int64_t)A.max_len ? S.len : (int64_t)A.max_len);
   int64_t t = A.nt ? A.nt[b] : 0;
   t = t < -(int64_t)TZR_HSTU_MAX_SEQ_LEN ? -(int64_t)TZR_HSTU_MAX_SEQ_LEN : (t > TZR_HSTU_MAX_SEQ_LEN ? TZR_HSTU_MAX_SEQ_LEN : t);  // (int arithmetic below)
@@ -98,8 +93,6 @@ __device__ __forceinline__ bool hs_valid(const HsArgs& A, const HsSample& S, int
   if (A.c > 0) ok = ok || (ii == 0 && jj < S.max_id);
   return ok && i < S.n && j < S.n;
 }
-
-__device__ __forceinline__ float hs_sigmoid(float s) { return 1.0f / (1.0f + expf(-s)); }
 
 // two runs of tiles: a0 .. a0 + na - 1, then b0 .. b0 + nb - 1
 struct HsWalk {
@@ -150,17 +143,6 @@ __device__ __forceinline__ HsWalk hs_col_walk(const HsArgs& A, const HsSample& S
   }
   W.b0 = c0t, W.nb = (hi + HS_TILE - 1) / HS_TILE - c0t;
   return W;
-}
-
-__device__ __forceinline__ void hs_zero(hs_f4* acc, int n) {
-#pragma unroll
-  for (int e = 0; e < n; ++e) acc[e] = hs_f4{0.f, 0.f, 0.f, 0.f};
-}
-__device__ __forceinline__ void hs_mfma4(float4 a, float4 b, hs_f4* acc) {  // four k-slots of one float4, four chains
-  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[0], 0, 0, 0);
-  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[1], 0, 0, 0);
-  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[2], 0, 0, 0);
-  acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[3], 0, 0, 0);
 }
 
 // A tile of 16 rows of two operands (X: width wx, Y: width wy) of one (sample, head): global -> registers -> LDS rows
@@ -215,24 +197,24 @@ __device__ __forceinline__ void hs_frags(float4* f, const float* rowp, int w, in
 
 // acc (four chains) += T[li][0 .. w) (an LDS tile, row stride w + 4) against the fragments f: A operand the tile, B the fragments
 template <int D>
-__device__ __forceinline__ hs_f4 hs_tile_dot(const float* T, int w, const float4* f, int li, int g) {
-  hs_f4 acc[4];
-  hs_zero(acc, 4);
+__device__ __forceinline__ tzr_f32x4 hs_tile_dot(const float* T, int w, const float4* f, int li, int g) {
+  tzr_f32x4 acc[4];
+  tzr_acc_zero(acc, 4);
   const float* tr = T + li * (w + 4);
 #pragma unroll
   for (int ch = 0; ch < D / 16; ++ch) {
     if (16 * ch < w) {
       const int a = 16 * ch + 4 * g;
       const float4 t = tzr_ld4(tr + (a < w ? a : 0));  // (unconditional, from a clamped column: no branch around the read)
-      hs_mfma4(a < w ? t : tzr_zero4(), f[ch], acc);
+      tzr_mfma4(a < w ? t : tzr_zero4(), f[ch], acc);
     }
   }
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  return tzr_join4(acc);
 }
 
 // o[ct] += p^T-trick: step e takes p[e] as the A operand and T's row 4 g + e as the B operand
 template <int D>
-__device__ __forceinline__ void hs_tile_acc(hs_f4* o, const hs_f4 p, const float* T, int w, int li, int g) {
+__device__ __forceinline__ void hs_tile_acc(tzr_f32x4* o, const tzr_f32x4 p, const float* T, int w, int li, int g) {
 #pragma unroll
   for (int ct = 0; ct < D / 16; ++ct) {
     if (16 * ct < w) {
@@ -249,7 +231,7 @@ __device__ __forceinline__ void hs_tile_acc(hs_f4* o, const hs_f4 p, const float
 
 // accumulator register r of lane (li, g) is (row r0 + 4 g + r, column 16 ct + li): rows below n, columns below w
 template <int D>
-__device__ __forceinline__ void hs_store(const HsOperand& O, const hs_f4* o, int64_t start, int h, int r0, int n, int w, int li, int g) {
+__device__ __forceinline__ void hs_store(const HsOperand& O, const tzr_f32x4* o, int64_t start, int h, int r0, int n, int w, int li, int g) {
 #pragma unroll
   for (int ct = 0; ct < D / 16; ++ct) {
     const int col = 16 * ct + li;
@@ -303,8 +285,8 @@ HS_NOPK __global__ __launch_bounds__(HS_THREADS) void tzr_hstu_rows_kernel(HsArg
   float4 qf[D / 16], gf[BWD ? D / 16 : 1];
   hs_frags<D>(qf, i < S.n ? A.q.p + (S.start + i) * A.q.rs + h * A.q.hs : nullptr, A.Da, g);
   if (BWD) hs_frags<D>(gf, i < S.n ? A.dout.p + (S.start + i) * A.dout.rs + h * A.dout.hs : nullptr, A.Dv, g);
-  hs_f4 o[D / 16];
-  hs_zero(o, D / 16);
+  tzr_f32x4 o[D / 16];
+  tzr_acc_zero(o, D / 16);
   const HsWalk W = hs_row_walk(A, S, r0, r1);
   const int total = W.na + W.nb;
   HsLoader<D> ld;
@@ -319,22 +301,22 @@ HS_NOPK __global__ __launch_bounds__(HS_THREADS) void tzr_hstu_rows_kernel(HsArg
     const float* Vs = Ks + YB;
     if (s + 1 < total) ld.fetch(W.tile(s + 1) * HS_TILE, S.n);
     if (w0 < S.n && (W.ctx || k0 <= w0 + 15)) {  // (uniform in the wave)
-      const hs_f4 st = hs_tile_dot<D>(Ks, A.Da, qf, li, g);  // (key 4 g + e, query li)
-      hs_f4 p;
+      const tzr_f32x4 st = hs_tile_dot<D>(Ks, A.Da, qf, li, g);  // (key 4 g + e, query li)
+      tzr_f32x4 p;
       if (!BWD) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int j = k0 + 4 * g + e;
           const float x = A.alpha * st[e];
-          p[e] = hs_valid(A, S, i, ii, j, hs_id(A, S, j)) ? x * hs_sigmoid(x) * A.inv_scale : 0.f;
+          p[e] = hs_valid(A, S, i, ii, j, hs_id(A, S, j)) ? x * tzr_sigmoid(x) * A.inv_scale : 0.f;
         }
         hs_tile_acc<D>(o, p, Vs, A.Dv, li, g);
       } else {
-        const hs_f4 dp = hs_tile_dot<D>(Vs, A.Dv, gf, li, g);  // dP^T = V dO^T
+        const tzr_f32x4 dp = hs_tile_dot<D>(Vs, A.Dv, gf, li, g);  // dP^T = V dO^T
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int j = k0 + 4 * g + e;
-          const float x = A.alpha * st[e], sg = hs_sigmoid(x);
+          const float x = A.alpha * st[e], sg = tzr_sigmoid(x);
           p[e] = hs_valid(A, S, i, ii, j, hs_id(A, S, j)) ? dp[e] * (sg * (1.0f + x * (1.0f - sg))) * ds_scale : 0.f;
         }
         hs_tile_acc<D>(o, p, Ks, A.Da, li, g);
@@ -364,8 +346,8 @@ HS_NOPK __global__ __launch_bounds__(HS_THREADS) void tzr_hstu_cols_kernel(HsArg
   float4 kf[D / 16], vf[D / 16];
   hs_frags<D>(kf, j < S.n ? A.k.p + (S.start + j) * A.k.rs + h * A.k.hs : nullptr, A.Da, g);
   hs_frags<D>(vf, j < S.n ? A.v.p + (S.start + j) * A.v.rs + h * A.v.hs : nullptr, A.Dv, g);
-  hs_f4 ok_[D / 16], ov[D / 16];
-  hs_zero(ok_, D / 16), hs_zero(ov, D / 16);
+  tzr_f32x4 ok_[D / 16], ov[D / 16];
+  tzr_acc_zero(ok_, D / 16), tzr_acc_zero(ov, D / 16);
   const HsWalk W = hs_col_walk(A, S, c0, c1);
   const int total = W.na + W.nb;
   HsLoader<D> ld;
@@ -380,13 +362,13 @@ HS_NOPK __global__ __launch_bounds__(HS_THREADS) void tzr_hstu_cols_kernel(HsArg
     const float* Gs = Qs + YB;
     if (s + 1 < total) ld.fetch(W.tile(s + 1) * HS_TILE, S.n);
     if (w0 < S.n && (s < W.na || q0 + 15 >= w0 || (W.ctx && q0 < A.c))) {  // (uniform in the wave)
-      const hs_f4 sc = hs_tile_dot<D>(Qs, A.Da, kf, li, g);  // (query 4 g + e, key li)
-      const hs_f4 dp = hs_tile_dot<D>(Gs, A.Dv, vf, li, g);  // dP = dO V^T
-      hs_f4 p, ds;
+      const tzr_f32x4 sc = hs_tile_dot<D>(Qs, A.Da, kf, li, g);  // (query 4 g + e, key li)
+      const tzr_f32x4 dp = hs_tile_dot<D>(Gs, A.Dv, vf, li, g);  // dP = dO V^T
+      tzr_f32x4 p, ds;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = q0 + 4 * g + e;
-        const float x = A.alpha * sc[e], sg = hs_sigmoid(x);
+        const float x = A.alpha * sc[e], sg = tzr_sigmoid(x);
         const bool ok = hs_valid(A, S, i, hs_id(A, S, i), j, jj);
         p[e] = ok ? x * sg * A.inv_scale : 0.f;
         ds[e] = ok ? dp[e] * (sg * (1.0f + x * (1.0f - sg))) * ds_scale : 0.f;
@@ -414,12 +396,10 @@ static int hs_operand(uint64_t ptr, int64_t rs, int64_t hs, int H, int D, HsOper
   return TZR_OK;
 }
 
-static bool hs_dim_ok(int d) { return d >= 4 && d <= TZR_HSTU_MAX_DIM && !(d & 3); }
-
 // sizes, limits, then the operands both directions read
 static int hs_check(const TzrHstuAttn* m, HsArgs* A) {
   if (m->B < 0 || m->N < 0 || m->max_attn_len < 0 || m->contextual_seq_len < 0) return TZR_ERR_INVALID;
-  if (!hs_dim_ok(m->Da) || !hs_dim_ok(m->Dv) || m->H < 1 || m->max_seq_len < 1 || m->max_seq_len > TZR_HSTU_MAX_SEQ_LEN ||
+  if (!tzr_dim4_ok(m->Da, TZR_HSTU_MAX_DIM) || !tzr_dim4_ok(m->Dv, TZR_HSTU_MAX_DIM) || m->H < 1 || m->max_seq_len < 1 || m->max_seq_len > TZR_HSTU_MAX_SEQ_LEN ||
       m->max_attn_len > TZR_HSTU_MAX_SEQ_LEN || m->contextual_seq_len > TZR_HSTU_MAX_SEQ_LEN || m->N >= (1ll << 31))
     return TZR_ERR_UNSUPPORTED;
   const int64_t nblk = ((int64_t)m->max_seq_len + HS_BLOCK - 1) / HS_BLOCK;

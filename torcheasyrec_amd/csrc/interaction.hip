@@ -18,8 +18,6 @@
 #define IA_D 16
 #define IA_MAXP (IA_MAXN * (IA_MAXN - 1) / 2)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct __attribute__((packed, aligned(4))) tzr_f4u {
   float x, y, z, w;
 };
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(IA_THREADS) void tzr_dot_interaction_fwd_kernel(
       if (r < n) n0 = tzr_ld4(ia_row(dense, dense_stride, sparse, sparse_stride, b + step, r, hd) + 4 * q);
       if (16 + r < n) n1 = tzr_ld4(ia_row(dense, dense_stride, sparse, sparse_stride, b + step, 16 + r, hd) + 4 * q);
     }
-    f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+    tzr_f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
     const float x0[4] = {a0.x, a0.y, a0.z, a0.w};
     const float x1[4] = {a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
@@ -207,7 +205,7 @@ __global__ __launch_bounds__(IA_THREADS) void tzr_dot_interaction_bwd_pipe_kerne
     ia_bwd_fetch(nxt, dense, dense_stride, sparse, sparse_stride, n, hd, b + step, b + step < B, gout, gout_stride,
                  cat_dense, cat_sparse, P, pd, ps, lane);
     ia_wave_sync();
-    f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+    tzr_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
 #pragma unroll
     for (int ks = 0; ks < IA_MAXN / 4; ++ks) {
       const int k = 4 * ks + q;
@@ -392,9 +390,9 @@ __global__ __launch_bounds__(IA_THREADS) void tzr_dot_interaction_fwd_mfma_kerne
     const int64_t b = b0 + wv;
     const bool on = b < B;
     float* o = out + b * out_stride;
-    f32x4 acc[NPAIR];
+    tzr_f32x4 acc[NPAIR];
 #pragma unroll
-    for (int p = 0; p < NPAIR; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < NPAIR; ++p) acc[p] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
     // column blocks go in groups of G: all loads of a group are issued before its pass-through stores
     // and MFMAs.  NB = 2: G = 4 (64 columns, 8 float4 per lane in flight, 4 waves per SIMD);
     // NB = 4: G = 1 with the next block prefetched (the 10 accumulators leave fewer registers).
@@ -563,9 +561,9 @@ __global__ __launch_bounds__(WAVES * TZR_WAVE, (NB <= 2 ? 4 : (WAVES == 4 ? 3 : 
     ia_wave_sync();  // S[wv] is private to this wave
     for (int cb = 0; cb < D; cb += 16) {
       const bool kin = on && (cb + 4 * q < D);      // output float4 of this lane
-      f32x4 d[NB];
+      tzr_f32x4 d[NB];
 #pragma unroll
-      for (int bi = 0; bi < NB; ++bi) d[bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int bi = 0; bi < NB; ++bi) d[bi] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
       float4 pt[NB];
 #pragma unroll
       for (int bi = 0; bi < NB; ++bi) {

@@ -46,8 +46,6 @@
 #define IT_ZP (16 * IT_MAXBLK + 4)   // floats per sample of the LDS z tile (virtual columns; +4: banks of the b128 A-operand reads)
 #define IT_YP (IT_H + 1)
 
-typedef float it_f32x4 __attribute__((ext_vector_type(4)));
-
 // -DIT_PROF (scripts/bench_interaction_top.py --prof builds a second library with it): every wave sums the shader
 // clocks it spends in each phase of the tile loop into a global table; not compiled into the product.
 #ifdef IT_PROF
@@ -244,9 +242,9 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
   auto product = [&](int gbuf, int zbuf) {
     const float* gp = Gs + gbuf * (IT_TS * IT_GP) + r * IT_GP + 16 * q;
     float* zo = Z + zbuf * zt + (4 * q) * zp + r;
-    it_f32x4 acc[NB];
+    tzr_f32x4 acc[NB];
 #pragma unroll
-    for (int m = 0; m < NB; ++m) acc[m] = it_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < NB; ++m) acc[m] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) {
       const float4 av = tzr_ld4(gp + 4 * k4);
@@ -263,7 +261,7 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
         for (int j = 0; j < 4; ++j) zo[j * zp + 16 * (wv + IT_WAVES * m)] = acc[m][j];
       }
     if (XL && wv == 0) {
-      it_f32x4 accx = {0.f, 0.f, 0.f, 0.f};
+      tzr_f32x4 accx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k4 = 0; k4 < 4; ++k4) {
         const float4 av = tzr_ld4(gp + 4 * k4);
@@ -363,7 +361,7 @@ __device__ __forceinline__ void it_bwd_loop(const ItBwdArgs& a, float* __restric
     // was ~15 VALU instructions x 16 elements per tile and wave -- and VALU instructions share the fp32 MFMAs' pipe
     // (283 -> ~60 VALU instructions per tile and wave, profiles/r04al).  The table is in LDS, XL's in registers.
     const char* zs = reinterpret_cast<const char*>(Z + zcur * zt + wv * zp);
-    it_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+    tzr_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
     if (XL) {
       const char* zb = reinterpret_cast<const char*>(Z + cur * zt);
 #pragma unroll
@@ -465,7 +463,7 @@ __device__ __forceinline__ void it_fwd_row(const ItX X, float* __restrict__ zs, 
   const bool v0 = r < n, v1 = 16 + r < n;
   const int rr0 = v0 ? r : n - 1, rr1 = v1 ? 16 + r : n - 1;
   const float4 a0 = v0 ? X.lo : tzr_zero4(), a1 = v1 ? X.hi : tzr_zero4();
-  it_f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+  tzr_f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
   const float x0[4] = {a0.x, a0.y, a0.z, a0.w};
   const float x1[4] = {a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
@@ -633,7 +631,7 @@ __device__ __forceinline__ void it_fwd_loop(const ItFwdArgs& a, float* __restric
     };
     if (row_first) next_row();
     IT_PROF_MARK(1);  // row (first half of the waves)
-    it_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    tzr_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     {
       // A operand of block m, k-steps 0..3 = columns 4 q + kk: one ds_read_b128, issued two blocks ahead of its MFMAs and
       // pinned there (left alone, hipcc hoists all NB reads to the top: 52 registers, and spills W1 fragments)
@@ -784,7 +782,7 @@ __device__ __forceinline__ void it_fwd_criteo(const ItFwdArgs& a, float* __restr
   };
   // one sample's row of a z tile (buffer offset `zo`): pairwise products by MFMA to their targets, X rows behind them
   auto row = [&](const ItX& X, const int zo) {
-    it_f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
+    tzr_f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = c00, c11 = c00;
     const float x0[4] = {X.lo.x, X.lo.y, X.lo.z, X.lo.w};
     const float x1[4] = {X.hi.x, X.hi.y, X.hi.z, X.hi.w};
 #pragma unroll
@@ -839,7 +837,7 @@ __device__ __forceinline__ void it_fwd_criteo(const ItFwdArgs& a, float* __restr
     constexpr bool row_first = decltype(RF)::value;
     constexpr int zo = cur * IT_C_ZT, zn = (cur ^ 1) * IT_C_ZT, yo = cur * IT_C_YT, yp = (cur ^ 1) * IT_C_YT;
     auto product = [&]() {
-      it_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      tzr_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       // A operand of block m, k-steps 0..3 = columns 4 q + kk: one ds_read_b128, issued a block ahead of its MFMAs and pinned
       // there (left alone, hipcc hoists all twelve reads to the top: 48 registers)
       float4 av[2];

@@ -48,8 +48,6 @@
 #define WG_PG 80           // ... of its g1 row (64 + 16)
 #define WG_MAXB 16         // column blocks (of 16) per group
 
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
-
 // -DIT_PROF (scripts/build_prof_lib.sh): per wave, the clocks spent in each phase of the tile loop, into the table of
 // tzr_it_prof_table (interaction_top.hip); not compiled into the product.
 #ifdef IT_PROF
@@ -229,7 +227,7 @@ __device__ __forceinline__ void wg_body(const WgArgs& a, const WgGroup& G, float
     // issued; the 1 KB-per-instruction loads take the CU's memory pipe ~16 clocks each), the pair stores last.
     auto step = [&](int buf, Regs& R, int tt, int tn, bool build, bool load) {
       float* zb = zT + buf * WG_ZT + (4 * lw) * WG_P;  // rows of this wave's four samples
-      wg_f32x4 c[4];
+      tzr_f32x4 c[4];
       if (build) {
         // the group's X rows out of the registers: row -> block npb + (row - x0), this lane's 16 bytes of it, per sample
         float* xb = zb + 16 * G.npb + 4 * q;
@@ -258,7 +256,7 @@ __device__ __forceinline__ void wg_body(const WgArgs& a, const WgGroup& G, float
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float4 av = SRC == 3 ? R.hi[HI ? e : 0] : R.lo[LO ? e : 0], bv = SRC == 1 ? R.lo[LO ? e : 0] : R.hi[HI ? e : 0];
-            c[e] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+            c[e] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
             c[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, c[e], 0, 0, 0);
             c[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, c[e], 0, 0, 0);
             c[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, c[e], 0, 0, 0);
@@ -332,9 +330,9 @@ __device__ __forceinline__ void wg_body(const WgArgs& a, const WgGroup& G, float
   // branches.
   const int hb = wv & 3, ch = (wv & 7) >> 2;
   const int nbw = G.nb > ch ? (G.nb - ch + 1) >> 1 : 0;  // blocks ch, ch + 2, ... of this wave
-  wg_f32x4 acc[8];
+  tzr_f32x4 acc[8];
 #pragma unroll
-  for (int m = 0; m < 8; ++m) acc[m] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < 8; ++m) acc[m] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   int bb[8];  // LDS offsets of this wave's blocks (scalar)
 #pragma unroll
   for (int m = 0; m < 8; ++m) bb[m] = wg_block_base(ch + 2 * m < WG_MAXB ? ch + 2 * m : WG_MAXB - 1, G.npb);

@@ -38,6 +38,7 @@ __device__ __forceinline__ float4 je_across_groups(float4 a, int P) {  // same p
   }
   return a;
 }
+// (not tzr_dot4: an explicit fmaf chain, one rounding a step where the sum of four products rounds each product)
 __device__ __forceinline__ float je_dot4(float4 a, float4 b) {
   float d = a.x * b.x;
   d = fmaf(a.y, b.y, d); d = fmaf(a.z, b.z, d); d = fmaf(a.w, b.w, d);

@@ -15,8 +15,6 @@
 
 static_assert(LA_MAXD <= 4 * TZR_WAVE, "one float4 a lane");
 
-__device__ __forceinline__ float la_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
 // grid ceil(B / 4)
 __global__ __launch_bounds__(LA_THREADS) void tzr_label_attn_fwd_kernel(const float* __restrict__ I, int64_t is, const float* __restrict__ V, int64_t vs,
                                                                         const unsigned char* __restrict__ mask, int64_t B, int K, int D, float simi_pow,
@@ -34,7 +32,7 @@ __global__ __launch_bounds__(LA_THREADS) void tzr_label_attn_fwd_kernel(const fl
   for (int k = 0; k < LA_MAXK; ++k) {
     valid[k] = k < K && mask[b * K + k] != 0;
     x[k] = cok && valid[k] ? tzr_ld4(I + (b * K + k) * is + 4 * lane) : tzr_zero4();
-    s[k] = tzr_wave_sum(la_dot4(x[k], v)) * simi_pow;
+    s[k] = tzr_wave_sum(tzr_dot4(x[k], v)) * simi_pow;
     if (valid[k]) m = fmaxf(m, s[k]);
   }
   float sum = 0.f;
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(LA_THREADS) void tzr_label_attn_bwd_kernel(const fl
     valid[k] = k < K && mask[b * K + k] != 0;
     x[k] = cok && valid[k] ? tzr_ld4(I + (b * K + k) * is + 4 * lane) : tzr_zero4();
     wk[k] = valid[k] ? w[b * K + k] : 0.f;
-    t[k] = tzr_wave_sum(la_dot4(g, x[k]));
+    t[k] = tzr_wave_sum(tzr_dot4(g, x[k]));
     tw = fmaf(wk[k], t[k], tw);
   }
   float4 dv = tzr_zero4();

@@ -32,8 +32,6 @@
 #define LB_TS 16
 #define LB_MAX_WG 768  // 3 workgroups per CU resident on 256 CUs
 
-typedef float lb_f32x4 __attribute__((ext_vector_type(4)));
-
 int g_tzr_linear_bwd_wg = 0;  // tzr_tune("linear_bwd_wg"): > 0 caps the workgroups (tests: many tiles per workgroup on small inputs)
 
 template <int KS /* K / 4 */, int HB /* H / 64 */>
@@ -78,9 +76,9 @@ __global__ __launch_bounds__(LB_THREADS) TZR_WAVES_PER_EU(3) void tzr_linear_bwd
     float4 yv[HB];
 #pragma unroll
     for (int jb = 0; jb < HB; ++jb) yv[jb] = ok ? tzr_ldg4(y + row * y_stride + cb + 16 * jb + 4 * q) : tzr_zero4();
-    lb_f32x4 acc[HB];
+    tzr_f32x4 acc[HB];
 #pragma unroll
-    for (int jb = 0; jb < HB; ++jb) acc[jb] = lb_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int jb = 0; jb < HB; ++jb) acc[jb] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
     const float* const A = &TA[buf][r * P + 4 * q];
 #pragma unroll
     for (int e = 0; e < KS / 4; ++e) {

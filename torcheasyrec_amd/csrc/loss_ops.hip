@@ -68,6 +68,7 @@ __device__ __forceinline__ void ls_block_sum2(float a, float b, float* sa, float
 }
 
 __device__ __forceinline__ float ls_softplus(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
+// (not tzr_sigmoid: the overflow-safe form through exp(-|z|), other roundings for z < 0)
 __device__ __forceinline__ float ls_sigmoid(float z) {
   const float e = expf(-fabsf(z));
   return z >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);

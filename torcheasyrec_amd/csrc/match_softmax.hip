@@ -52,8 +52,6 @@
 static_assert(sizeof(TzrMatchSoftmax) == 224, "TzrMatchSoftmax: the layout _lib.py mirrors");
 static_assert(MS_THREADS / 16 == MS_ROWS, "prologue and epilogue: sixteen threads per own row");
 
-typedef float ms_f4 __attribute__((ext_vector_type(4)));
-
 struct MsArgs {
   const float* U;
   const float* V;
@@ -79,11 +77,8 @@ struct MsArgs {
   int64_t dus, dvs;
 };
 
-__device__ __forceinline__ ms_f4 ms_zero() {
-  ms_f4 z = {0.f, 0.f, 0.f, 0.f};
-  return z;
-}
-__device__ __forceinline__ float ms_sum16(float v) {  // over the sixteen threads of a row (a fixed xor tree)
+// over the sixteen threads of a row (a fixed xor tree; not tzr_sum16: masks 8, 4, 2, 1 end on another association than 1, 2, 4, 8)
+__device__ __forceinline__ float ms_sum16(float v) {
   for (int m = 8; m > 0; m >>= 1) v += __shfl_xor(v, m);
   return v;
 }
@@ -91,7 +86,6 @@ __device__ __forceinline__ float ms_sum16(float v) {  // over the sixteen thread
 // inverse norm is an ulp of the score, which exp turns into a relative error of 20 ulp
 __device__ __forceinline__ double ms_rnorm(float ss) { return 1.0 / fmax(sqrt((double)ss), (double)MS_EPS); }
 __device__ __forceinline__ float ms_sq4(float4 a) { return a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w; }
-__device__ __forceinline__ float ms_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 ms_scale4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 
 // exp(x) for x <= 0 (up to rounding) as exp2f(x log2 e): two instructions where expf is a dozen, and per score this head does
@@ -114,14 +108,14 @@ __device__ __forceinline__ float ms_score(float acc, double ru, double rv, float
 // acc[t][r] = <other row o0 + 4q + r, own row 16 t + li of Os>; *ss: this lane's share of |other row o0 + li|^2 (columns 16 s + 4 q ..)
 template <int RT>
 __device__ __forceinline__ void ms_scores(const float* Os, const float* __restrict__ Oth, int64_t os, int64_t o0, int64_t On, int D, int li, int q,
-                                          ms_f4* acc, float* ss) {
+                                          tzr_f32x4* acc, float* ss) {
   const bool ook = o0 + li < On;
   const float* op = Oth + (ook ? o0 + li : On - 1) * os;  // (a row past the end: the last row's, zeroed; no branch around a load)
-  ms_f4 c[RT][4];
+  tzr_f32x4 c[RT][4];
 #pragma unroll
   for (int t = 0; t < RT; ++t)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) c[t][e] = ms_zero();
+    for (int e = 0; e < 4; ++e) c[t][e] = tzr_acc_zero();
   float sq = 0.f;
   for (int k0 = 0; k0 < D; k0 += 64) {
     float4 a[4];
@@ -141,6 +135,7 @@ __device__ __forceinline__ void ms_scores(const float* Os, const float* __restri
       for (int t = 0; t < RT; ++t) {
         const float* bp = Os + (16 * t + li) * MS_LS + (kok ? k : 0);
         const float4 b = kok ? make_float4(bp[0], bp[1], bp[2], bp[3]) : tzr_zero4();
+        // (spelled out, not tzr_mfma4: through the helper the code moves and the in-batch pass measured 0.7 % slower)
         c[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].x, b.x, c[t][0], 0, 0, 0);
         c[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].y, b.y, c[t][1], 0, 0, 0);
         c[t][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s].z, b.z, c[t][2], 0, 0, 0);
@@ -149,7 +144,7 @@ __device__ __forceinline__ void ms_scores(const float* Os, const float* __restri
     }
   }
 #pragma unroll
-  for (int t = 0; t < RT; ++t) acc[t] = (c[t][0] + c[t][1]) + (c[t][2] + c[t][3]);
+  for (int t = 0; t < RT; ++t) acc[t] = tzr_join4(c[t]);
   *ss = sq;
 }
 
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(MS_THREADS) void tzr_match_softmax_fwd_kernel(MsArg
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int k = 4 * c + 64 * s;
-      dot += ms_dot4(u[s], v[s]);
+      dot += tzr_dot4(u[s], v[s]);
       if (k < D) {
         float* d = Os + row * MS_LS + k;
         d[0] = u[s].x, d[1] = u[s].y, d[2] = u[s].z, d[3] = u[s].w;
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(MS_THREADS) void tzr_match_softmax_fwd_kernel(MsArg
   const int64_t ntile = (A.M - obeg + 15) >> 4;
   for (int64_t tile = wv; tile < ntile; tile += MS_WAVES) {
     const int64_t o0 = obeg + 16 * tile;
-    ms_f4 acc[MS_RT];
+    tzr_f32x4 acc[MS_RT];
     float ss;
     ms_scores<MS_RT>(Os, A.V, A.vs, o0, A.M, D, li, q, acc, &ss);
     double rvl = 1.0;
@@ -358,15 +353,15 @@ __global__ __launch_bounds__(MS_THREADS) void tzr_match_softmax_bwd_kernel(MsArg
     pos_t[t] = ok ? A.pos[it] : 0.f;
     wp_t[t] = ok ? (A.w ? A.w[it] : 1.0f) * gs : 0.f;
   }
-  ms_f4 dacc[RT][NDT];
+  tzr_f32x4 dacc[RT][NDT];
 #pragma unroll
   for (int t = 0; t < RT; ++t)
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) dacc[t][dt] = ms_zero();
+    for (int dt = 0; dt < NDT; ++dt) dacc[t][dt] = tzr_acc_zero();
   const int64_t ntile = (oend - obeg + 15) >> 4;
   for (int64_t tile = wv; tile < ntile; tile += MS_WAVES) {
     const int64_t o0 = obeg + 16 * tile;
-    ms_f4 acc[RT];
+    tzr_f32x4 acc[RT];
     float ss;
     // what the tile's other rows bring, loaded ahead of the product and without a branch per load (a row past the end reads the
     // last row's; its g is zeroed below): a conditional load each made four more load latencies a tile (NOTES.md)
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(MS_THREADS) void tzr_match_softmax_bwd_kernel(MsArg
     }
     ms_scores<RT>(Os, Oth, oths, o0, oend, D, li, q, acc, &ss);
     const bool diag = !sampled && o0 < own0 + 16 * RT && o0 + 16 > own0;  // (uniform) the tile holds a label column
-    ms_f4 G[RT];
+    tzr_f32x4 G[RT];
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
       const int64_t ownrow = own0 + 16 * t + li;
@@ -472,9 +467,9 @@ __global__ __launch_bounds__(MS_THREADS) void tzr_match_softmax_bwd_kernel(MsArg
       v[s] = kok && eok ? ms_scale4(tzr_ld4(A.V + ei * A.vs + k), rvi) : tzr_zero4();
       dx[s] = tzr_fma4(g0, v[s], dx[s]);
       dv[s] = ms_scale4(x[s], g0);
-      vd += ms_dot4(v[s], dv[s]);
+      vd += tzr_dot4(v[s], dv[s]);
     }
-    xd += ms_dot4(x[s], dx[s]);
+    xd += tzr_dot4(x[s], dx[s]);
   }
   xd = ms_sum16(xd);
   if (pair) vd = ms_sum16(vd);

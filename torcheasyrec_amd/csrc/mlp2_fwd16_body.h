@@ -8,8 +8,6 @@
 #define MT_H1 64
 #define MT_P1 (MT_H1 + 4)  // row pitches: 16-byte aligned rows, b128 reads of 16 rows spread over the banks
 
-typedef float mm_f32x4 __attribute__((ext_vector_type(4)));
-
 // ---- bottom MLP: ha = relu(x Wa^T + ba) [B, 64], hb = relu(ha Wb^T + bb) [B, 16]; K0 <= 16 ---------------------------------
 #define MB_H1 64
 #define MB_H2 16
@@ -55,9 +53,9 @@ __device__ __forceinline__ void mb_fwd16_tiles(
         xa[ks] = (k < K0 && b0 + r < B) ? v : 0.f;
       }
     }
-    mm_f32x4 acc[4];
+    tzr_f32x4 acc[4];
 #pragma unroll
-    for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -69,7 +67,7 @@ __device__ __forceinline__ void mb_fwd16_tiles(
       for (int j = 0; j < 4; ++j) T1[(4 * q + j) * MT_P1 + 16 * hbk + r] = fmaxf(acc[hbk][j] + bav[hbk], 0.f);
     __builtin_amdgcn_wave_barrier();
     // ---- ha out (rows of 256 bytes, 16 bytes per lane) and hb = relu(ha Wb^T + bb): A = ha[sample r][16 q + ks]
-    mm_f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+    tzr_f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = lane + TZR_WAVE * i, row = e >> 4, c4 = e & 15;

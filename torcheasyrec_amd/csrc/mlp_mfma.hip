@@ -9,7 +9,7 @@
 // accumulator reg j of lane (r = l & 15, q = l >> 4) is D[row 4 q + j][col r].  A contraction index may be permuted freely
 // as long as both operands agree: rows of activations are read as one ds_read_b128 per four k-steps.
 #include "tzr_common.h"
-#include "mlp2_fwd16_body.h"  // MM_TS, MT_H1, MT_P1, MB_*, mm_f32x4 and the bottom MLP's forward body
+#include "mlp2_fwd16_body.h"  // MM_TS, MT_H1, MT_P1, MB_* and the bottom MLP's forward body
 
 #define MM_WAVES 4
 #define MM_THREADS (MM_WAVES * TZR_WAVE)
@@ -17,13 +17,6 @@
 
 extern int g_tzr_mlp_mfma;  // mlp_ops.hip: > 0 also caps the workgroups (tests: many tiles per wave on small batches)
 
-__device__ __forceinline__ float mm_sum16(float v) {  // over the 16 lanes that share l >> 4 (all of them get the sum)
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
 __device__ __forceinline__ float mm_sum_q(float v) {  // over the 4 lanes that share l & 15
   v += __shfl_xor(v, 16);
   v += __shfl_xor(v, 32);
@@ -72,11 +65,11 @@ __global__ __launch_bounds__(MM_THREADS) TZR_WAVES_PER_EU(2) void tzr_mlp_tail64
   }
   const float bias3 = b3 ? b3[0] : 0.f;
   const float inv = 1.0f / (float)B;
-  mm_f32x4 accW[2][4];  // dW2[c = 16 jb + 4 q + j][h = 16 hb + r]
+  tzr_f32x4 accW[2][4];  // dW2[c = 16 jb + 4 q + j][h = 16 hb + r]
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
-    for (int hb = 0; hb < 4; ++hb) accW[jb][hb] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int hb = 0; hb < 4; ++hb) accW[jb][hb] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   float db2a[2] = {0.f, 0.f}, dw3a[2] = {0.f, 0.f}, db1a[4] = {0.f, 0.f, 0.f, 0.f}, db3a = 0.f, lossa = 0.f;
 
   const int64_t tiles = (B + MM_TS - 1) / MM_TS;
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(MM_THREADS) TZR_WAVES_PER_EU(2) void tzr_mlp_tail64
     fetch(yt, t + nw < tiles ? t + nw : t);
     __builtin_amdgcn_wave_barrier();
     // ---- y2 = relu(y1 W2^T + b2): A = y1[sample r][16 q + ks]
-    mm_f32x4 y2a[2] = {mm_f32x4{0.f, 0.f, 0.f, 0.f}, mm_f32x4{0.f, 0.f, 0.f, 0.f}};
+    tzr_f32x4 y2a[2] = {tzr_f32x4{0.f, 0.f, 0.f, 0.f}, tzr_f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float4 av = tzr_ld4(T1 + r * MT_P1 + 16 * q + 4 * i);
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(MM_THREADS) TZR_WAVES_PER_EU(2) void tzr_mlp_tail64
     for (int j = 0; j < 4; ++j) {
       y2v[0][j] = fmaxf(y2a[0][j] + b2v[0], 0.f);
       y2v[1][j] = fmaxf(y2a[1][j] + b2v[1], 0.f);
-      z[j] = mm_sum16(fmaf(y2v[0][j], w3v[0], y2v[1][j] * w3v[1])) + bias3;  // (a fixed shuffle tree: deterministic)
+      z[j] = tzr_sum16(fmaf(y2v[0][j], w3v[0], y2v[1][j] * w3v[1])) + bias3;  // (a fixed shuffle tree: deterministic)
     }
     // ---- loss and d(loss)/d(logit) of samples 4 q .. 4 q + 3 (every lane of the group computes them)
     float dl[4];
@@ -172,9 +165,9 @@ __global__ __launch_bounds__(MM_THREADS) TZR_WAVES_PER_EU(2) void tzr_mlp_tail64
         for (int hb = 0; hb < 4; ++hb) accW[jb][hb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[jb], yb[hb], accW[jb][hb], 0, 0, 0);
     }
     // ---- g1 = (g2 W2) masked by y1 > 0: A = g2[sample r][8 q + ks]
-    mm_f32x4 g1a[4];
+    tzr_f32x4 g1a[4];
 #pragma unroll
-    for (int hb = 0; hb < 4; ++hb) g1a[hb] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int hb = 0; hb < 4; ++hb) g1a[hb] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const float4 av = tzr_ld4(T2 + r * MT_P2 + 8 * q + 4 * i);
@@ -302,9 +295,9 @@ __global__ __launch_bounds__(MM_THREADS) void tzr_mlp2_bwd16_kernel(
   for (int hbk = 0; hbk < 4; ++hbk)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) Wf[hbk][ks] = Wb[(4 * q + ks) * MB_H1 + 16 * hbk + r];
-  mm_f32x4 accWb[4], accWa[4];  // dWb[unit 4 q + j][16 hbk + r]; dWa[16 hbk + 4 q + j][input r]
+  tzr_f32x4 accWb[4], accWa[4];  // dWb[unit 4 q + j][16 hbk + r]; dWa[16 hbk + 4 q + j][input r]
 #pragma unroll
-  for (int hbk = 0; hbk < 4; ++hbk) accWb[hbk] = accWa[hbk] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int hbk = 0; hbk < 4; ++hbk) accWb[hbk] = accWa[hbk] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   float dbba[4] = {0.f, 0.f, 0.f, 0.f}, dbaa[4] = {0.f, 0.f, 0.f, 0.f};
   const int trow = lane >> 2, tc4 = lane & 3;  // this lane's 16-byte piece of a [16 x 16] tile
   const int64_t tiles = (B + MM_TS - 1) / MM_TS;
@@ -360,9 +353,9 @@ __global__ __launch_bounds__(MM_THREADS) void tzr_mlp2_bwd16_kernel(
     fetch(in, t + nw < tiles ? t + nw : t);
     __builtin_amdgcn_wave_barrier();
     // ---- ga = (gb Wb) masked by ha > 0: A = gb[sample r][4 q + ks]
-    mm_f32x4 acc[4];
+    tzr_f32x4 acc[4];
 #pragma unroll
-    for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int hbk = 0; hbk < 4; ++hbk) acc[hbk] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
     {
       const float4 av = tzr_ld4(Tgb + r * MB_PX + 4 * q);
       const float a4[4] = {av.x, av.y, av.z, av.w};

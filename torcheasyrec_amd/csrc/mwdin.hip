@@ -60,8 +60,6 @@
 static_assert(sizeof(TzrMwdin) == 400, "TzrMwdin: the layout _lib.py mirrors");
 static_assert(MW_MAXS <= MW_THREADS && MW_MAXC <= MW_THREADS, "one thread a position / a column");
 
-typedef float mw_f4 __attribute__((ext_vector_type(4)));
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MW_NOPK __attribute__((target("no-packed-fp32-ops")))
 #else
@@ -94,13 +92,9 @@ struct MwArgs {
   int P, oW[MW_MAXL], ob[MW_MAXL], ow3, ob3, osl, oal;  // the layout of a partial row (= of dparams)
 };
 
-// sample b: its first row, its length, the rows that take part (offsets outside [0, N] are clamped: no access leaves the buffers)
+// sample b: its first row, its length (the clamped span: no access leaves the buffers), the rows that take part
 __device__ __forceinline__ void mw_sample(const MwArgs& A, int64_t b, int64_t* start, int64_t* len, int* s) {
-  int64_t s0 = A.off[b], s1 = A.off[b + 1];
-  s0 = s0 < 0 ? 0 : (s0 > A.N ? A.N : s0);
-  s1 = s1 < s0 ? s0 : (s1 > A.N ? A.N : s1);
-  *start = s0;
-  *len = s1 - s0;
+  tzr_jagged_span(A.off, b, b + 1, A.N, start, len);
   *s = (int)(*len < (int64_t)A.S ? *len : (int64_t)A.S);
 }
 
@@ -108,17 +102,6 @@ __device__ __forceinline__ float mw_act(float z, float slope) { return z > 0.f ?
 __device__ __forceinline__ float mw_dact(float z, float slope) { return z > 0.f ? 1.0f : slope; }
 __device__ __forceinline__ float4 mw_act4(float4 z, float slope) {
   return make_float4(mw_act(z.x, slope), mw_act(z.y, slope), mw_act(z.z, slope), mw_act(z.w, slope));
-}
-__device__ __forceinline__ mw_f4 mw_mfma4(float4 a, float4 b, mw_f4* acc) {  // four k-slots of one float4 load, four chains
-  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[0], 0, 0, 0);
-  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[1], 0, 0, 0);
-  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[2], 0, 0, 0);
-  acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[3], 0, 0, 0);
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-__device__ __forceinline__ void mw_zero(mw_f4* acc) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] = mw_f4{0.f, 0.f, 0.f, 0.f};
 }
 // the four parts of a row (lanes li, li + 16, li + 32, li + 48) added in a fixed tree; every lane of the row ends with the sum
 __device__ __forceinline__ float mw_row_sum(float v) {
@@ -163,15 +146,18 @@ __device__ __forceinline__ void mw_chain(const MwArgs& A, const float* Ks, const
       const int col = 16 * ct + li;
       const bool cok = col < H1;
       const float* wr = A.Wl[0] + (int64_t)(cok ? col : 0) * 3 * C;
-      mw_f4 acc[4], z;
-      mw_zero(acc);
+      tzr_f32x4 acc[4], z;
+      tzr_acc_zero(acc, 4);
       for (int k0 = 0; k0 < C; k0 += 16) {
         const int k = k0 + 4 * g;
         const bool kok = k < C;
         const float4 a = kok ? tzr_ld4(kr + k) : tzr_zero4(), qq = kok ? tzr_ld4(Qs + k) : tzr_zero4();
         const float4 wa = cok && kok ? tzr_ld4(wr + k) : tzr_zero4(), wb = cok && kok ? tzr_ld4(wr + C + k) : tzr_zero4();
-        mw_mfma4(a, wa, acc);
-        z = mw_mfma4(make_float4(a.x * qq.x, a.y * qq.y, a.z * qq.z, a.w * qq.w), wb, acc);
+        tzr_mfma4(a, wa, acc);
+        tzr_mfma4(make_float4(a.x * qq.x, a.y * qq.y, a.z * qq.z, a.w * qq.w), wb, acc);
+        // (here and below the join is written inside the k loop, only the last one is used: written behind the loop the
+        // backward's register counts move, <32, 2> across an occupancy step -- the class table above is of this form)
+        z = tzr_join4(acc);
       }
       if (cok) {
         const float hq = Hq[col];
@@ -191,12 +177,13 @@ __device__ __forceinline__ void mw_chain(const MwArgs& A, const float* Ks, const
         const int col = 16 * ct + li;
         const bool cok = col < Hc;
         const float* wr = A.Wl[l] + (int64_t)(cok ? col : 0) * Hp;
-        mw_f4 acc[4], z;
-        mw_zero(acc);
+        tzr_f32x4 acc[4], z;
+        tzr_acc_zero(acc, 4);
         for (int k0 = 0; k0 < Hp; k0 += 16) {
           const int k = k0 + 4 * g;
           const bool kok = k < Hp;
-          z = mw_mfma4(kok ? mw_act4(tzr_ld4(tr + k), slp[l - 1]) : tzr_zero4(), cok && kok ? tzr_ld4(wr + k) : tzr_zero4(), acc);
+          tzr_mfma4(kok ? mw_act4(tzr_ld4(tr + k), slp[l - 1]) : tzr_zero4(), cok && kok ? tzr_ld4(wr + k) : tzr_zero4(), acc);
+          z = tzr_join4(acc);
         }
         if (cok) {
           const float bias = A.bl[l][col];
@@ -342,8 +329,8 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
         for (int t = wv; t < nit * njt; t += MW_WAVES) {  // dW_l += g_l^T act(z_{l-1}): tile t on wave t mod 4, a chain a block
           const int it = t / njt, jt = t - it * njt;
           const int ci = 16 * it + li, cj = 16 * jt + li;
-          mw_f4 acc[4];
-          mw_zero(acc);
+          tzr_f32x4 acc[4];
+          tzr_acc_zero(acc, 4);
 #pragma unroll
           for (int wb = 0; wb < MW_WAVES; ++wb) {
             if (wb < nb) {
@@ -357,7 +344,7 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
               }
             }
           }
-          const mw_f4 d = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+          const tzr_f32x4 d = tzr_join4(acc);
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if (16 * it + 4 * g + r < Hc && cj < Hp) part[A.oW[l] + (16 * it + 4 * g + r) * Hp + cj] += d[r];
@@ -374,14 +361,15 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
           for (int ct = 0; 16 * ct < Hp; ++ct) {
             const int col = 16 * ct + li;
             const bool cok = col < Hp;
-            mw_f4 acc[4], u;
-            mw_zero(acc);
+            tzr_f32x4 acc[4], u;
+            tzr_acc_zero(acc, 4);
             for (int k0 = 0; k0 < Hc; k0 += 16) {
               const int k = k0 + 4 * g;
               const bool kok = k < Hc;
               const float* wp = A.Wl[l] + (int64_t)k * Hp + col;
               const bool ok = cok && kok;
-              u = mw_mfma4(kok ? tzr_ld4(tr + k) : tzr_zero4(), ok ? make_float4(wp[0], wp[Hp], wp[2 * Hp], wp[3 * Hp]) : tzr_zero4(), acc);
+              tzr_mfma4(kok ? tzr_ld4(tr + k) : tzr_zero4(), ok ? make_float4(wp[0], wp[Hp], wp[2 * Hp], wp[3 * Hp]) : tzr_zero4(), acc);
+              u = tzr_join4(acc);
             }
             if (cok) {
 #pragma unroll
@@ -401,8 +389,8 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
           const int half = t / (nit * njt), u = t - half * nit * njt, it = u / njt, jt = u - it * njt;
           const int ci = 16 * it + li, cj = 16 * jt + li;
           const float qf = half ? (cj < C ? Qs[cj] : 0.f) : 1.0f;
-          mw_f4 acc[4];
-          mw_zero(acc);
+          tzr_f32x4 acc[4];
+          tzr_acc_zero(acc, 4);
 #pragma unroll
           for (int wb = 0; wb < MW_WAVES; ++wb) {
             if (wb < nb) {
@@ -416,7 +404,7 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
               }
             }
           }
-          const mw_f4 d = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+          const tzr_f32x4 d = tzr_join4(acc);
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if (16 * it + 4 * g + r < H1 && cj < C) part[A.oW[0] + (16 * it + 4 * g + r) * 3 * C + half * C + cj] += d[r];
@@ -434,15 +422,16 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
           {
             const int col = 16 * ct + li;
             const bool cok = col < C;
-            mw_f4 acca[4], accb[4], ua, ub;
-            mw_zero(acca), mw_zero(accb);
+            tzr_f32x4 acca[4], accb[4], ua, ub;
+            tzr_acc_zero(acca, 4), tzr_acc_zero(accb, 4);
             for (int k0 = 0; k0 < H1; k0 += 16) {
               const int k = k0 + 4 * g;
               const bool kok = k < H1, ok = cok && kok;
               const float* wp = A.Wl[0] + (int64_t)k * 3 * C + col;
               const float4 a = kok ? tzr_ld4(tr + k) : tzr_zero4();
-              ua = mw_mfma4(a, ok ? make_float4(wp[0], wp[3 * C], wp[6 * C], wp[9 * C]) : tzr_zero4(), acca);
-              ub = mw_mfma4(a, ok ? make_float4(wp[C], wp[4 * C], wp[7 * C], wp[10 * C]) : tzr_zero4(), accb);
+              tzr_mfma4(a, ok ? make_float4(wp[0], wp[3 * C], wp[6 * C], wp[9 * C]) : tzr_zero4(), acca);
+              tzr_mfma4(a, ok ? make_float4(wp[C], wp[4 * C], wp[7 * C], wp[10 * C]) : tzr_zero4(), accb);
+              ua = tzr_join4(acca), ub = tzr_join4(accb);
             }
             float dqp = 0.f;
             if (cok) {
@@ -480,9 +469,9 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
     }
   }
   if (blockIdx.x == 0) {  // rows in front of offsets[0] and behind offsets[B] belong to no sample: zero gradient rows, by workgroup 0
-    int64_t lo = A.off[0], hi = A.off[A.B];
-    lo = lo < 0 ? 0 : (lo > A.N ? A.N : lo);
-    hi = hi < lo ? lo : (hi > A.N ? A.N : hi);
+    int64_t lo, n;
+    tzr_jagged_span(A.off, 0, A.B, A.N, &lo, &n);
+    const int64_t hi = lo + n;
     for (int64_t i = tid; i < (lo + A.N - hi) * C4; i += MW_THREADS) {
       const int64_t n = i / C4;
       tzr_st4(A.dK + (n < lo ? n : hi + (n - lo)) * A.dks + 4 * (i - n * C4), tzr_zero4());
@@ -508,8 +497,6 @@ MW_NOPK __global__ __launch_bounds__(MW_THREADS) void tzr_mwdin_bwd_kernel(MwArg
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-
-static inline int64_t mw_bwd_grid(int64_t B) { return B < TZR_MWDIN_BWD_MAX_GRID ? B : TZR_MWDIN_BWD_MAX_GRID; }
 
 // the floats of dparams: per layer [W_l | b_l], w3, b3, a slope a layer, alpha; 0: a shape outside the limits
 static int64_t mw_params(const TzrMwdin* m) {
@@ -541,7 +528,7 @@ static bool mw_limits(const TzrMwdin* m, int* S) {
   return true;
 }
 
-static inline size_t mw_ws_bytes(const TzrMwdin* m) { return tzr_align_up((size_t)mw_bwd_grid(m->B) * mw_params(m) * sizeof(float)); }
+static inline size_t mw_ws_bytes(const TzrMwdin* m) { return tzr_align_up((size_t)tzr_capped_grid(m->B, TZR_MWDIN_BWD_MAX_GRID) * mw_params(m) * sizeof(float)); }
 
 // sizes, limits (nothing else is looked at for a shape this build has no kernel for), then the pointers both directions read
 static int mw_check(const TzrMwdin* m, MwArgs* A) {
@@ -631,7 +618,7 @@ extern "C" int tzr_mwdin_bwd(const TzrMwdin* h_mw, void* stream) {
   A.dqs = h_mw->dq_stride;
   A.parts = reinterpret_cast<float*>(h_mw->ws);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int G = (int)mw_bwd_grid(h_mw->B);
+  const int G = (int)tzr_capped_grid(h_mw->B, TZR_MWDIN_BWD_MAX_GRID);
   MW_LAUNCH(tzr_mwdin_bwd_kernel, G, s, A);
   TZR_CHECK_LAUNCH();
   hipLaunchKernelGGL(tzr_parts_sum_finish_kernel<>, dim3((unsigned)((A.P + TZR_WAVE - 1) / TZR_WAVE)), dim3(TZR_FIN_THREADS), 0, s, A.parts, G, A.P,

@@ -175,8 +175,6 @@ __device__ __forceinline__ float bwd_group_sum(float v, int lg, int lane_in_grou
   return s;
 }
 
-__device__ __forceinline__ float bwd_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
 // ---- the row arithmetic every form of the update shares (the loads and stores stay with the callers) ----
 __device__ __forceinline__ float4 bwd_clip(const BwdOpt& opt, float4 g) {
   if (opt.clip) {
@@ -238,8 +236,8 @@ __device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const Bwd
   float* const mp = reinterpret_cast<float*>(tb.m) + row * (int64_t)tb.m_stride + 4 * c;
   const float wd = opt.wd;
   if (kind == TZR_OPT_LARS_SGD) {
-    const float wn = sqrtf(bwd_group_sum(active ? bwd_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
-    const float gn = sqrtf(bwd_group_sum(active ? bwd_dot4(g, g) : 0.f, lg, lane_in_group, lane));
+    const float wn = sqrtf(bwd_group_sum(active ? tzr_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
+    const float gn = sqrtf(bwd_group_sum(active ? tzr_dot4(g, g) : 0.f, lg, lane_in_group, lane));
     const float den = gn + wd * wn;
     const float lam = den > 0.f ? lr * opt.beta2 * wn / den : 0.f;  // beta2 = eta
     const float mu = opt.beta1;
@@ -262,7 +260,7 @@ __device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const Bwd
     v4 = active ? tzr_ld4(mp + tb.dim) : tzr_zero4();
     bwd_adam_v(g, b2, v4);
   } else {  // partial row-wise: one v per row, the mean of g^2 over the row's columns
-    const float ss = bwd_group_sum(active ? bwd_dot4(g, g) : 0.f, lg, lane_in_group, lane);
+    const float ss = bwd_group_sum(active ? tzr_dot4(g, g) : 0.f, lg, lane_in_group, lane);
     float vold = (active && lane_in_group == 0) ? *vrow : 0.f;
     vold = __shfl(vold, lane - lane_in_group, 64);
     vnew = b2 * vold + (1.0f - b2) * (ss / (float)tb.dim);
@@ -275,8 +273,8 @@ __device__ __forceinline__ void bwd_apply_row_norm(const TzrTable& tb, const Bwd
   u.w = (m4.w / c1) / (sqrtf(v4.w / c2) + opt.eps) + wd * w4.w;
   float step = lr;
   if (kind != TZR_OPT_PARTIAL_ROWWISE_ADAM) {  // the two LAMB kinds: trust ratio |w| / |u|
-    const float wn = sqrtf(bwd_group_sum(active ? bwd_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
-    const float un = sqrtf(bwd_group_sum(active ? bwd_dot4(u, u) : 0.f, lg, lane_in_group, lane));
+    const float wn = sqrtf(bwd_group_sum(active ? tzr_dot4(w4, w4) : 0.f, lg, lane_in_group, lane));
+    const float un = sqrtf(bwd_group_sum(active ? tzr_dot4(u, u) : 0.f, lg, lane_in_group, lane));
     step = un > 0.f ? lr * (wn / un) : 0.f;
   }
   if (active) {

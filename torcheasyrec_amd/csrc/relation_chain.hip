@@ -56,8 +56,6 @@ static_assert(RC_WG_WAVES == 8 && RC_WG_UN == 8, "the pairwise joins below are w
 
 static_assert(sizeof(TzrRelationChain) == 2176, "TzrRelationChain: the layout _lib.py mirrors");
 
-typedef float rc_f4 __attribute__((ext_vector_type(4)));
-
 struct RcTower {
   const float* x;
   int64_t xs;
@@ -85,14 +83,9 @@ struct RcArgs {
   RcTower t[RC_T];
 };
 
-__device__ __forceinline__ rc_f4 rc_zero() {
-  rc_f4 z = {0.f, 0.f, 0.f, 0.f};
-  return z;
-}
-
 // acc[u][c] += As[16, kc] W for the wave's tiles t0 + wv + RC_WAVES u: A(i, k) = As[i AS + k] (LDS), W(k, j) = W[k wks + j wjs], j < N
 __device__ __forceinline__ void rc_mma(const float* As, int AS, int kc, const float* __restrict__ W, size_t wks, size_t wjs, int N, int t0, int wv,
-                                       int q, int li, rc_f4 (*acc)[RC_CH]) {
+                                       int q, int li, tzr_f32x4 (*acc)[RC_CH]) {
   const int NT = (N + 15) >> 4;
   for (int k0 = 0; k0 < kc; k0 += 4 * RC_CH) {
 #pragma unroll
@@ -114,13 +107,13 @@ __device__ __forceinline__ void rc_mma(const float* As, int AS, int kc, const fl
     }
   }
 }
-__device__ __forceinline__ rc_f4 rc_join(const rc_f4* a) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
+__device__ __forceinline__ tzr_f32x4 rc_join(const tzr_f32x4* a) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
 static_assert(RC_CH == 8, "rc_join is written out for eight chains");
-__device__ __forceinline__ void rc_clear(rc_f4 (*acc)[RC_CH]) {
+__device__ __forceinline__ void rc_clear(tzr_f32x4 (*acc)[RC_CH]) {
 #pragma unroll
   for (int u = 0; u < RC_TPW; ++u)
 #pragma unroll
-    for (int c = 0; c < RC_CH; ++c) acc[u][c] = rc_zero();
+    for (int c = 0; c < RC_CH; ++c) acc[u][c] = tzr_acc_zero();
 }
 
 // grid min(B / 16 rounded up, RC_MAXGRID).  NR: the class's bound on the towers with layers (the emulator's __shared__ is a
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(RC_THREADS) void tzr_relation_chain_fwd_kernel(RcAr
 #pragma unroll 1
       for (int l = 0; l < tw.L; ++l) {
         const int N = tw.n[l], NT = (N + 15) >> 4;
-        rc_f4 acc[RC_TPW][RC_CH];
+        tzr_f32x4 acc[RC_TPW][RC_CH];
         rc_clear(acc);
         if (l == 0) {
           for (int c0 = 0; c0 < tw.K0; c0 += RC_KC) {
@@ -179,7 +172,7 @@ __global__ __launch_bounds__(RC_THREADS) void tzr_relation_chain_fwd_kernel(RcAr
         for (int u = 0; u < RC_TPW; ++u) {
           const int tile = wv + RC_WAVES * u, col = 16 * tile + li;
           if (tile < NT && col < N) {
-            const rc_f4 sum = rc_join(acc[u]);
+            const tzr_f32x4 sum = rc_join(acc[u]);
             const float bias = tw.b[l][col];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(RC_THREADS) void tzr_relation_chain_bwd_rows_kernel
 #pragma unroll 1
       for (int l = tw.L - 1; l >= 1; --l) {
         const int Nk = tw.n[l], No = tw.n[l - 1], NT = (No + 15) >> 4;
-        rc_f4 acc[RC_TPW][RC_CH];
+        tzr_f32x4 acc[RC_TPW][RC_CH];
         rc_clear(acc);
         rc_mma(Ds + (l & 1) * RC_ROWS * RC_WS, RC_WS, Nk, tw.w[l], No, 1, No, 0, wv, q, li, acc);
         float* ds = Ds + ((l - 1) & 1) * RC_ROWS * RC_WS;
@@ -255,7 +248,7 @@ __global__ __launch_bounds__(RC_THREADS) void tzr_relation_chain_bwd_rows_kernel
         for (int u = 0; u < RC_TPW; ++u) {
           const int tile = wv + RC_WAVES * u, col = 16 * tile + li;
           if (tile < NT && col < No) {
-            const rc_f4 sum = rc_join(acc[u]);
+            const tzr_f32x4 sum = rc_join(acc[u]);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int row = 4 * q + r;
@@ -272,14 +265,14 @@ __global__ __launch_bounds__(RC_THREADS) void tzr_relation_chain_bwd_rows_kernel
       const int N0 = tw.n[0], KT = (tw.K0 + 15) >> 4;
 #pragma unroll 1
       for (int c0 = 0; c0 < KT; c0 += RC_WAVES * RC_TPW) {
-        rc_f4 acc[RC_TPW][RC_CH];
+        tzr_f32x4 acc[RC_TPW][RC_CH];
         rc_clear(acc);
         rc_mma(Ds, RC_WS, N0, tw.w[0], tw.K0, 1, tw.K0, c0, wv, q, li, acc);
 #pragma unroll
         for (int u = 0; u < RC_TPW; ++u) {
           const int tile = c0 + wv + RC_WAVES * u, col = 16 * tile + li;
           if (tile < KT && col < tw.K0) {
-            const rc_f4 sum = rc_join(acc[u]);
+            const tzr_f32x4 sum = rc_join(acc[u]);
             int s = 0;
             while (col >= tw.off[s + 1]) ++s;
             const int sc = col - tw.off[s];
@@ -337,10 +330,10 @@ __global__ __launch_bounds__(RC_WG_THREADS) void tzr_relation_chain_wgrad_kernel
     pu += kcol - tw.off[s];
   }
   const float* pz = tw.dz[l] + (nok ? n : 0);
-  rc_f4 acc[RC_WG_UN];
+  tzr_f32x4 acc[RC_WG_UN];
   float cs[RC_WG_UN];
 #pragma unroll
-  for (int u = 0; u < RC_WG_UN; ++u) acc[u] = rc_zero(), cs[u] = 0.f;
+  for (int u = 0; u < RC_WG_UN; ++u) acc[u] = tzr_acc_zero(), cs[u] = 0.f;
   const int64_t steps = (B + 3) >> 2;
   for (int64_t s0 = wv; s0 < steps; s0 += RC_WG_UN * RC_WG_WAVES) {  // RC_WG_UN of the wave's steps at a time, each on its own chain
     float va[RC_WG_UN], vb[RC_WG_UN];
@@ -359,7 +352,7 @@ __global__ __launch_bounds__(RC_WG_THREADS) void tzr_relation_chain_wgrad_kernel
       acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[u], vb[u], acc[u], 0, 0, 0);
     }
   }
-  const rc_f4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  const tzr_f32x4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wv * 256 + r * 64 + lane] = sum[r];
   redc[wv * TZR_WAVE + lane] = ((cs[0] + cs[1]) + (cs[2] + cs[3])) + ((cs[4] + cs[5]) + (cs[6] + cs[7]));

@@ -38,8 +38,6 @@
 static_assert(sizeof(TzrStuOutput) == 240, "TzrStuOutput: the layout _lib.py mirrors");
 static_assert(SO_BLOCK == 32, "two 16-row MFMA tiles a workgroup");
 
-typedef float so_f4 __attribute__((ext_vector_type(4)));
-
 struct SoArgs {
   const float *u, *attn, *x, *gamma, *beta, *wo, *g;
   const int64_t* seed;
@@ -61,7 +59,6 @@ __device__ __forceinline__ float so_keep(const SoArgs& A, uint64_t seed, int64_t
   const uint64_t n = (uint64_t)i * (uint64_t)(3 * A.W) + (uint64_t)c + 1ull;
   return (uint32_t)(so_mix(seed + n * 0x9E3779B97F4A7C15ull) >> 40) >= A.thr ? A.scale : 0.f;
 }
-__device__ __forceinline__ float so_sigmoid(float s) { return 1.0f / (1.0f + expf(-s)); }
 __device__ __forceinline__ int so_gidx(const SoArgs& A, int j) { return A.group ? j / A.nw : j; }  // gamma / beta of column j
 __device__ __forceinline__ int so_stat(const SoArgs& A, int j) { return A.group ? j / A.nw : 0; }  // the row's group of column j
 
@@ -73,7 +70,7 @@ __device__ __forceinline__ void so_load_rows(float* dst, const float* src, int64
     const int r = idx / w4, c = 4 * (idx - r * w4);
     const int64_t i = i0 + r;
     float4 v = tzr_ld4(src + (i < L ? i : L - 1) * rs + c);
-    if (SILU) v = make_float4(v.x * so_sigmoid(v.x), v.y * so_sigmoid(v.y), v.z * so_sigmoid(v.z), v.w * so_sigmoid(v.w));
+    if (SILU) v = make_float4(v.x * tzr_sigmoid(v.x), v.y * tzr_sigmoid(v.y), v.z * tzr_sigmoid(v.z), v.w * tzr_sigmoid(v.w));
     tzr_st4(dst + r * (w + 4) + c, i < L ? v : tzr_zero4());
   }
 }
@@ -117,9 +114,9 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_fwd_kernel(SoArgs A) {
     col[t] = 16 * tn + li;
     cok[t] = t < per && col[t] < E;
   }
-  so_f4 acc[2][NT], tot[2][NT];  // a run of SO_RUN steps, the runs: two levels keep a sum of 3 W terms short chains
+  tzr_f32x4 acc[2][NT], tot[2][NT];  // a run of SO_RUN steps, the runs: two levels keep a sum of 3 W terms short chains
 #pragma unroll
-  for (int t = 0; t < NT; ++t) acc[0][t] = acc[1][t] = tot[0][t] = tot[1][t] = so_f4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NT; ++t) acc[0][t] = acc[1][t] = tot[0][t] = tot[1][t] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   const uint64_t seed = A.drop ? (uint64_t)*A.seed : 0ull;
   const int nch = (W + 15) >> 4, steps = 3 * nch;
   int64_t irow[2], srow[2];
@@ -190,7 +187,7 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_fwd_kernel(SoArgs A) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         tot[0][t] += acc[0][t], tot[1][t] += acc[1][t];
-        acc[0][t] = acc[1][t] = so_f4{0.f, 0.f, 0.f, 0.f};
+        acc[0][t] = acc[1][t] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
 #pragma unroll
@@ -235,9 +232,9 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_rows_kernel(SoArgs
     const int j = 16 * (wv * per + jt) + li;
     const bool jok = jt < per && j < W;
     const int jc = jok ? j : 0;
-    so_f4 acc[3][2], tot[3][2];
+    tzr_f32x4 acc[3][2], tot[3][2];
 #pragma unroll
-    for (int s = 0; s < 3; ++s) acc[s][0] = acc[s][1] = tot[s][0] = tot[s][1] = so_f4{0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < 3; ++s) acc[s][0] = acc[s][1] = tot[s][0] = tot[s][1] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
     if (jt < per) {  // (uniform in the wave)
       float4 b[3], bn[3];
       auto fetch = [&](int ch, float4* dst) {  // Wo's rows s W + j at the columns 16 ch + 4 g ..
@@ -270,7 +267,7 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_rows_kernel(SoArgs
 #pragma unroll
           for (int s = 0; s < 3; ++s) {
             tot[s][0] += acc[s][0], tot[s][1] += acc[s][1];
-            acc[s][0] = acc[s][1] = so_f4{0.f, 0.f, 0.f, 0.f};
+            acc[s][0] = acc[s][1] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
           }
         }
 #pragma unroll
@@ -290,7 +287,7 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_rows_kernel(SoArgs
         const float uv = A.u[ic * A.us + jc], av = A.attn[ic * A.as + jc];
         const int64_t si = ic * A.hs + so_stat(A, jc);
         const float rstd = A.rstd[si], nh = (av - A.mean[si]) * rstd;
-        const float sg = so_sigmoid(uv), usv = uv * sg, nrm = fmaf(nh, gam, bet);
+        const float sg = tzr_sigmoid(uv), usv = uv * sg, nrm = fmaf(nh, gam, bet);
         float dcu = tot[0][rt][r], da = tot[1][rt][r], dcy = tot[2][rt][r];
         if (A.drop) {
           dcu *= so_keep(A, seed, ic, jc);
@@ -399,9 +396,9 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_w_kernel(SoArgs A)
     col[t] = 16 * (((int)blockIdx.y * (SO_THREADS / TZR_WAVE) + wv) * NT + t) + li;
     nok[t] = col[t] < E;
   }
-  so_f4 acc[NT], tot[NT];
+  tzr_f32x4 acc[NT], tot[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = tot[t] = so_f4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NT; ++t) acc[t] = tot[t] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
   float pu[4], pa[4], pm[4], pr[4];
   auto fetch = [&](int64_t i0) {  // (clamped rows: no branch around the loads)
 #pragma unroll
@@ -431,7 +428,7 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_w_kernel(SoArgs A)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int64_t i = i0 + tr + 16 * q;
-      const float usv = pu[q] * so_sigmoid(pu[q]);
+      const float usv = pu[q] * tzr_sigmoid(pu[q]);
       float v = s == 0 ? usv : (s == 1 ? pa[q] : usv * fmaf((pa[q] - pm[q]) * pr[q], gam, bet));
       if (A.drop) v *= so_keep(A, seed, i, cc);
       Ct[buf][tr + 16 * q][tc] = cok && i < A.L ? v : 0.f;
@@ -450,7 +447,7 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_w_kernel(SoArgs A)
     if (++run == SO_RUN || i0 + SO_STEP >= A.L) {
       run = 0;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) tot[t] += acc[t], acc[t] = so_f4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < NT; ++t) tot[t] += acc[t], acc[t] = tzr_f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
 #pragma unroll
@@ -464,13 +461,12 @@ __global__ __launch_bounds__(SO_THREADS) void tzr_stu_out_bwd_w_kernel(SoArgs A)
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static bool so_dim_ok(int d) { return d >= 4 && d <= TZR_STU_OUT_MAX_DIM && !(d & 3); }
 
 // sizes and limits, then -- with rows -- the operands both directions read
 static int so_check(const TzrStuOutput* m, SoArgs* A) {
   if (m->L < 0 || m->H < 1 || m->Dv < 1 || !(m->p >= 0.f) || !(m->p < 1.f)) return TZR_ERR_INVALID;
   const int64_t W = (int64_t)m->H * m->Dv;
-  if (!so_dim_ok(m->E) || W > TZR_STU_OUT_MAX_DIM || !so_dim_ok((int)W) || (m->group_norm && (m->Dv & 3)) || m->L >= (1ll << 31))
+  if (!tzr_dim4_ok(m->E, TZR_STU_OUT_MAX_DIM) || W > TZR_STU_OUT_MAX_DIM || !tzr_dim4_ok((int)W, TZR_STU_OUT_MAX_DIM) || (m->group_norm && (m->Dv & 3)) || m->L >= (1ll << 31))
     return TZR_ERR_UNSUPPORTED;
   if (m->L == 0) return TZR_OK;
   A->L = m->L, A->E = m->E, A->W = (int)W, A->group = m->group_norm ? 1 : 0;

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "../../include/tzrec_hip.h"
+#include "tzr_tile.h"
 #include <tzr_gfx950.h>
 
 #define TZR_WAVE 64

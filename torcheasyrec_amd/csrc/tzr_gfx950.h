@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tzr_tile.h"  // tzr_f32x4
+
 typedef __attribute__((address_space(1))) uint32_t tzr_gu32;
 typedef __attribute__((address_space(1))) uint64_t tzr_gu64;
 
@@ -78,7 +80,6 @@ __device__ __forceinline__ float tzr_relu(float x) {
 // LDS read then also waits for all the row gathers in flight.
 #define TZR_GLOBAL_AS __attribute__((address_space(1)))
 // (through builtin vector types: a HIP float4 is a struct whose copy operators take a generic `this` -- FLAT again)
-typedef float tzr_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned tzr_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float tzr_ldg(const float* p) { return *(const TZR_GLOBAL_AS float*)p; }
 __device__ __forceinline__ void tzr_stg(float* p, float v) { *(TZR_GLOBAL_AS float*)p = v; }

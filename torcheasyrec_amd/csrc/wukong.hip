@@ -47,20 +47,13 @@
 #define WK_MAXD 128
 #define WK_MAXGRID 512  // workgroups of a pass over the batch = rows of partial sums the finishing launch adds
 
-typedef float wk_f4 __attribute__((ext_vector_type(4)));
-
 constexpr int wk_pad(int n) { return n % 64 == 0 ? n + 8 : n + 1; }
-
-__device__ __forceinline__ wk_f4 wk_zero() {
-  wk_f4 z = {0.f, 0.f, 0.f, 0.f};
-  return z;
-}
 
 // acc += A[16 mt .. 16 mt + 15, 0..K) B[0..K, 16 nt .. 16 nt + 15]: A(i, k) = A[i ars + k acs] for i < M, B(k, j) = B[k brs + j bcs]
 // for j < N, both in LDS; whatever lies outside is a zero operand (the address clamped to element 0, the value dropped).
 // Every lane of the wave calls it with the same arguments.  q = lane >> 4, li = lane & 15.
-__device__ __forceinline__ wk_f4 wk_tile(const float* A, int ars, int acs, int M, const float* B, int brs, int bcs, int N, int K, int mt, int nt,
-                                         int q, int li, wk_f4 acc) {
+__device__ __forceinline__ tzr_f32x4 wk_tile(const float* A, int ars, int acs, int M, const float* B, int brs, int bcs, int N, int K, int mt, int nt,
+                                         int q, int li, tzr_f32x4 acc) {
   const int i = 16 * mt + li, j = 16 * nt + li;
   const bool iok = i < M, jok = j < N;
   const float* ap = A + (iok ? i : 0) * ars;
@@ -101,7 +94,7 @@ __device__ __forceinline__ void wk_fm_pz(const float* Xs, int XS, const float* W
   const int DT = (D + 15) >> 4, FT = (F + 15) >> 4;
   for (int tile = wv; tile < DT * NT; tile += WK_WAVES) {
     const int mt = tile / NT, nt = tile - mt * NT;
-    const wk_f4 acc = wk_tile(Xs, 1, XS, D, Ws, KS, 1, k, F, mt, nt, q, li, wk_zero());
+    const tzr_f32x4 acc = wk_tile(Xs, 1, XS, D, Ws, KS, 1, k, F, mt, nt, q, li, tzr_acc_zero());
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int d = 16 * mt + 4 * q + r, c = 16 * nt + li;
@@ -111,7 +104,7 @@ __device__ __forceinline__ void wk_fm_pz(const float* Xs, int XS, const float* W
   __syncthreads();
   for (int tile = wv; tile < FT * NT; tile += WK_WAVES) {
     const int mt = tile / NT, nt = tile - mt * NT;
-    const wk_f4 acc = wk_tile(Xs, XS, 1, F, Ps, KS, 1, k, D, mt, nt, q, li, wk_zero());
+    const tzr_f32x4 acc = wk_tile(Xs, XS, 1, F, Ps, KS, 1, k, D, mt, nt, q, li, tzr_acc_zero());
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int f = 16 * mt + 4 * q + r, c = 16 * nt + li;
@@ -208,9 +201,9 @@ __global__ __launch_bounds__(WK_THREADS) void wk_fm_bwd_kernel(const float* __re
     gam[j] = e < n ? gamma[e] : 0.f;
     acc_g[j] = acc_b[j] = 0.f;
   }
-  wk_f4 accw[TPW];
+  tzr_f32x4 accw[TPW];
 #pragma unroll
-  for (int a = 0; a < TPW; ++a) accw[a] = wk_zero();
+  for (int a = 0; a < TPW; ++a) accw[a] = tzr_acc_zero();
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     wk_stage(x + b * xs, F, D, Xs, XS);
@@ -248,7 +241,7 @@ __global__ __launch_bounds__(WK_THREADS) void wk_fm_bwd_kernel(const float* __re
     // dP = X^T gZ
     for (int tile = wv; tile < DT * NT; tile += WK_WAVES) {
       const int mt = tile / NT, nt = tile - mt * NT;
-      const wk_f4 acc = wk_tile(Xs, 1, XS, D, Zs, KS, 1, k, F, mt, nt, q, li, wk_zero());
+      const tzr_f32x4 acc = wk_tile(Xs, 1, XS, D, Zs, KS, 1, k, F, mt, nt, q, li, tzr_acc_zero());
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int d = 16 * mt + 4 * q + r, c = 16 * nt + li;
@@ -259,7 +252,7 @@ __global__ __launch_bounds__(WK_THREADS) void wk_fm_bwd_kernel(const float* __re
     // gX = gZ P^T + W dP^T
     for (int tile = wv; tile < FT * DT; tile += WK_WAVES) {
       const int mt = tile / DT, nt = tile - mt * DT;
-      wk_f4 acc = wk_tile(Zs, KS, 1, F, Ps, 1, KS, D, k, mt, nt, q, li, wk_zero());
+      tzr_f32x4 acc = wk_tile(Zs, KS, 1, F, Ps, 1, KS, D, k, mt, nt, q, li, tzr_acc_zero());
       acc = wk_tile(Ws, KS, 1, F, dPs, 1, KS, D, k, mt, nt, q, li, acc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -319,7 +312,7 @@ __device__ __forceinline__ void wk_mix_pre(const float* Xs, float* Pre, int XS, 
   const int OT = (Fo + 15) >> 4, DT = (D + 15) >> 4;
   for (int tile = wv; tile < OT * DT; tile += WK_WAVES) {
     const int mt = tile / DT, nt = tile - mt * DT;
-    const wk_f4 acc = wk_tile(Wcs, 1, WS, Fo, Xs, XS, 1, D, F, mt, nt, q, li, wk_zero());
+    const tzr_f32x4 acc = wk_tile(Wcs, 1, WS, Fo, Xs, XS, 1, D, F, mt, nt, q, li, tzr_acc_zero());
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int o = 16 * mt + 4 * q + r, d = 16 * nt + li;
@@ -390,9 +383,9 @@ __global__ __launch_bounds__(WK_THREADS) void wk_mix_bwd_kernel(const float* __r
   const bool ok0 = lane < D, ok1 = lane + 64 < D;
   const float g0 = ok0 ? gamma[lane] : 0.f, g1 = ok1 ? gamma[lane + 64] : 0.f;
   float ag0 = 0.f, ag1 = 0.f, ab0 = 0.f, ab1 = 0.f;
-  wk_f4 accw[TPW];
+  tzr_f32x4 accw[TPW];
 #pragma unroll
-  for (int a = 0; a < TPW; ++a) accw[a] = wk_zero();
+  for (int a = 0; a < TPW; ++a) accw[a] = tzr_acc_zero();
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     wk_stage(x + b * xs, F, D, Xs, XS);
@@ -420,7 +413,7 @@ __global__ __launch_bounds__(WK_THREADS) void wk_mix_bwd_kernel(const float* __r
     // gX = Wc gpre
     for (int tile = wv; tile < FT * DT; tile += WK_WAVES) {
       const int mt = tile / DT, nt = tile - mt * DT;
-      const wk_f4 acc = wk_tile(Wcs, WS, 1, F, Pre, XS, 1, D, Fo, mt, nt, q, li, wk_zero());
+      const tzr_f32x4 acc = wk_tile(Wcs, WS, 1, F, Pre, XS, 1, D, Fo, mt, nt, q, li, tzr_acc_zero());
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int f = 16 * mt + 4 * q + r, d = 16 * nt + li;
