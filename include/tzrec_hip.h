@@ -1071,6 +1071,27 @@ typedef struct TzrHstuAttn {
 int tzr_hstu_attn_fwd(const TzrHstuAttn* h_at, void* stream);
 int tzr_hstu_attn_bwd(const TzrHstuAttn* h_at, void* stream);
 
+/* The same operation on bf16 operands (csrc/hstu_attention_bf16.hip, v_mfma_f32_16x16x32_bf16 with fp32 accumulators): the same
+ * struct, read with bf16 pointers (q, k, v, out, grad_out, dq, dk, dv all bf16) and strides in bf16 ELEMENTS; the same mask, walk,
+ * launches (one forward, two backward), zeros for the rows outside a sample's kept rows, and order of checks.  Numeric contract:
+ *   - scores s = alpha <q, k> accumulate in fp32 from the bf16 operands;
+ *   - sigmoid, silu', the mask and 1 / scale are fp32 (expf and a true division, as in the fp32 kernels);
+ *   - P = valid silu(s) / scale and dS = valid dP silu'(s) alpha / scale are rounded ONCE to bf16, to nearest even, as the second
+ *     product's operand; dP = dO V^T accumulates in fp32;
+ *   - every output (out, dq, dk, dv) accumulates in fp32 over all its keys (rows) and is rounded once to bf16 at its single
+ *     store: there are no bf16 partial sums.  One owner and one fixed order of additions per element: two runs are bit-equal.
+ * Limits (TZR_ERR_UNSUPPORTED beyond): Da, Dv multiples of 8 in [8, TZR_HSTU_MAX_DIM] (independently; a width that is no
+ *   multiple of the instruction's contraction depth 32 is padded with zeros in registers, never in memory); unit column
+ *   stride, row and head strides multiples of 8 elements, head stride >= the width, row stride >= (H - 1) head stride + width
+ *   (the column slices of one bf16 uvqk matrix are read where they lie); the other limits of tzr_hstu_attn_*, the grid counted in
+ *   TZR_HSTU_BF16_BLOCK rows.  TZR_ERR_INVALID: a null pointer or one not 16-byte aligned, negative sizes.  B == 0 or N == 0:
+ *   TZR_OK without a launch.  TZR_HSTU_BF16_BLOCK rows (keys in the column pass) a workgroup, TZR_HSTU_BF16_TILE keys (rows) a
+ *   tile.  New entry points on the existing struct: the ABI version stays 15. */
+#define TZR_HSTU_BF16_BLOCK 64
+#define TZR_HSTU_BF16_TILE 32
+int tzr_hstu_attn_bf16_fwd(const TzrHstuAttn* h_at, void* stream);
+int tzr_hstu_attn_bf16_bwd(const TzrHstuAttn* h_at, void* stream);
+
 /* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
  * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
  *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied

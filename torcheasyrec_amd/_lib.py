@@ -219,6 +219,8 @@ class TzrMwdin(C.Structure):
 assert C.sizeof(TzrMwdin) == 400
 # limits and tile sizes of tzr_hstu_attn_* (include/tzrec_hip.h: TZR_HSTU_*)
 HSTU_MAX_DIM, HSTU_MAX_SEQ_LEN, HSTU_BLOCK, HSTU_TILE = 128, 268435456, 64, 16
+# tile sizes of tzr_hstu_attn_bf16_* (TZR_HSTU_BF16_*)
+HSTU_BF16_BLOCK, HSTU_BF16_TILE = 64, 32
 
 
 class TzrHstuAttn(C.Structure):
@@ -506,6 +508,8 @@ _SIGNATURES = {
     "tzr_mwdin_bwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_fwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_bwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_attn_bf16_fwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_attn_bf16_bwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
     "tzr_stu_output_bwd": (_i32, [_vp, _vp]),
@@ -682,6 +686,15 @@ def heads_ok(t: torch.Tensor) -> bool:
         return False
     (_, H, D), (rs, hs, one) = t.shape, t.stride()
     return one == 1 and rs % 4 == 0 and hs % 4 == 0 and hs >= D and rs >= (H - 1) * hs + D and t.data_ptr() % 16 == 0
+
+
+def heads_bf16_ok(t: torch.Tensor) -> bool:
+    """what `tzr_hstu_attn_bf16_*` takes as an [N, H, D] operand: bf16, unit column stride, both strides multiples of 8 elements,
+    heads and rows that share no element, 16-byte aligned data (the column slice of a bf16 uvqk matrix, viewed [N, H, D], passes)"""
+    if t.dim() != 3 or t.dtype != torch.bfloat16:
+        return False
+    (_, H, D), (rs, hs, one) = t.shape, t.stride()
+    return one == 1 and rs % 8 == 0 and hs % 8 == 0 and hs >= D and rs >= (H - 1) * hs + D and t.data_ptr() % 16 == 0
 
 
 def rows16(t: torch.Tensor) -> torch.Tensor:

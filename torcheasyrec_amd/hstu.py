@@ -3,8 +3,10 @@ tzrec/modules/gr/stu.py: STULayer, STUStack): the operation under hstu_match, dl
 
 `hstu_mha` runs csrc/hstu_attention.hip (tzr_hstu_attn_fwd / _bwd: one launch forward, two backward, nothing of size N x N in
 memory, work following sum(n_i^2)) when FUSED_HSTU_MHA is on and `hstu_mha_ok` takes the operands; otherwise -- the switch off, a
-shape outside `hstu_mha_limit`, a double backward -- the literal padded form [B, H, N, N] out of plain torch ops.  Built: causal,
-no attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32; the rest is refused by name.
+shape outside `hstu_mha_limit`, a double backward -- the literal padded form [B, H, N, N] out of plain torch ops.  bf16 q, k, v
+take csrc/hstu_attention_bf16.hip (tzr_hstu_attn_bf16_fwd / _bwd: the same launches on the bf16 MFMAs, fp32 accumulation, bf16
+out and gradients) when FUSED_HSTU_MHA_BF16 is on as well; mixed dtypes and fp16 take the literal form.  Built: causal, no
+attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32 and bf16; the rest is refused by name.
 
 `stu_output` is the layer's stage behind the attention (the reference's hstu_compute_output): silu(u), the layer or group norm of
 the attention's rows, their product, the concat [u, attn, y], dropout and addmm(x, ., `_output_weight`) on csrc/stu_output.hip
@@ -24,6 +26,7 @@ from . import _lib
 
 FUSED_STU_OUTPUT = False  # profiles/stu_output, forward + backward: 6.20 ms fused against 2.84 ms literal (0.56 against 0.94 GB): the literal form stays
 FUSED_HSTU_MHA = True  # profiles/hstu_attention, forward + backward: 24.4 ms fused against 32.4 ms literal, 0.72 against 14.06 GB
+FUSED_HSTU_MHA_BF16 = True  # bf16 q, k, v on csrc/hstu_attention_bf16.hip (needs FUSED_HSTU_MHA too); profiles/hstu_attention_bf16
 
 
 def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int) -> torch.Tensor:
@@ -73,12 +76,17 @@ def hstu_mha_literal(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.T
     return v.new_zeros(L, H, v.shape[2]).index_put((idx[keep],), dense[keep])
 
 
-def hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, max_attn_len: int = 0, contextual_seq_len: int = 0, B: int = 1) -> Optional[str]:
-    """None when tzr_hstu_attn_* has a kernel for the shape, else the limit of csrc/hstu_attention.hip it misses (include/tzrec_hip.h)"""
+def hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, max_attn_len: int = 0, contextual_seq_len: int = 0, B: int = 1,
+                   dtype: torch.dtype = torch.float32) -> Optional[str]:
+    """None when tzr_hstu_attn_* (fp32) or tzr_hstu_attn_bf16_* (bf16) has a kernel for the shape, else the limit of
+    csrc/hstu_attention.hip / hstu_attention_bf16.hip it misses (include/tzrec_hip.h)"""
     D, S = _lib.HSTU_MAX_DIM, _lib.HSTU_MAX_SEQ_LEN
+    if dtype not in (torch.float32, torch.bfloat16):
+        return f"dtype {dtype} must be float32 or bfloat16"
+    step = 8 if dtype == torch.bfloat16 else 4  # (16 bytes of a row)
     for name, d in (("attention_dim", Da), ("hidden_dim", Dv)):
-        if d % 4 or not 4 <= d <= D:
-            return f"{name} {d} must be a multiple of 4 in [4, {D}]"
+        if d % step or not step <= d <= D:
+            return f"{name} {d} must be a multiple of {step} in [{step}, {D}]"
     if H < 1:
         return f"num_heads {H} must be at least 1"
     if not 1 <= max_seq_len <= S:
@@ -87,28 +95,38 @@ def hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, max_attn_len: int
         return f"max_attn_len {max_attn_len} must be in [0, {S}]"
     if not 0 <= contextual_seq_len <= S:
         return f"contextual_seq_len {contextual_seq_len} must be in [0, {S}]"
-    if (max_seq_len + _lib.HSTU_BLOCK - 1) // _lib.HSTU_BLOCK * max(B, 1) * H >= 2 ** 31:
-        return f"grid: ceil({max_seq_len} / {_lib.HSTU_BLOCK}) x {B} x {H} workgroups must stay below 2^31"
+    block = _lib.HSTU_BF16_BLOCK if dtype == torch.bfloat16 else _lib.HSTU_BLOCK
+    if (max_seq_len + block - 1) // block * max(B, 1) * H >= 2 ** 31:
+        return f"grid: ceil({max_seq_len} / {block}) x {B} x {H} workgroups must stay below 2^31"
     return None
 
 
 def hstu_mha_ok(max_seq_len: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
                 num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0) -> bool:
-    """what tzr_hstu_attn_* takes: q, k [L, H, Da], v [L, H, Dv] as `_lib.heads_ok` operands (column slices of one uvqk matrix
-    are fine), offsets int64 [B + 1] and num_targets int64 [B] contiguous, a shape inside `hstu_mha_limit`, everything on the
-    device of the loaded library"""
+    """what tzr_hstu_attn_* / tzr_hstu_attn_bf16_* takes: q, k [L, H, Da], v [L, H, Dv] of ONE dtype, fp32 as `_lib.heads_ok`
+    operands or bf16 as `_lib.heads_bf16_ok` operands (column slices of one uvqk matrix are fine), offsets int64 [B + 1] and
+    num_targets int64 [B] contiguous, a shape inside `hstu_mha_limit` for that dtype, everything on the device of the loaded library"""
     if q.dim() != 3 or k.shape != q.shape or v.dim() != 3 or v.shape[:2] != q.shape[:2] or seq_offsets.dim() != 1 or seq_offsets.numel() < 1:
         return False
     dev, (L, H, Da), B = q.device, q.shape, seq_offsets.numel() - 1
-    if not _lib.takes(q) or any(t.device != dev for t in (k, v, seq_offsets)) or L >= 2 ** 31:
+    if not _lib.takes(q) or any(t.device != dev for t in (k, v, seq_offsets)) or L >= 2 ** 31 or k.dtype != q.dtype or v.dtype != q.dtype:
         return False
-    if hstu_mha_limit(H, Da, v.shape[2], max_seq_len, max_attn_len, contextual_seq_len, B) is not None or (B == 0 and L > 0):
+    if hstu_mha_limit(H, Da, v.shape[2], max_seq_len, max_attn_len, contextual_seq_len, B, q.dtype) is not None or (B == 0 and L > 0):
         return False  # (no sample, yet rows: the entry points launch nothing, so nobody would write the rows)
     if seq_offsets.dtype != torch.int64 or not seq_offsets.is_contiguous():
         return False
     if num_targets is not None and not (num_targets.shape == (B,) and num_targets.dtype == torch.int64 and num_targets.is_contiguous() and num_targets.device == dev):
         return False
-    return L == 0 or all(_lib.heads_ok(t) for t in (q, k, v))
+    return L == 0 or all(_heads_ok(t) for t in (q, k, v))
+
+
+def _heads_ok(t: torch.Tensor) -> bool:
+    return _lib.heads_bf16_ok(t) if t.dtype == torch.bfloat16 else _lib.heads_ok(t)
+
+
+def _entry(name: str, dtype: torch.dtype) -> str:
+    """the entry point of the operands' dtype: tzr_hstu_attn_<name> or tzr_hstu_attn_bf16_<name>"""
+    return f"tzr_hstu_attn_bf16_{name}" if dtype == torch.bfloat16 else f"tzr_hstu_attn_{name}"
 
 
 def _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen):
@@ -128,11 +146,11 @@ def _operands(m, **tensors):
 
 def hstu_attn_fwd(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen) -> torch.Tensor:
     """tzr_hstu_attn_fwd on operands `hstu_mha_ok` took -> out [L, H, Dv] (torch.empty: the kernel writes every row)"""
-    out = torch.empty(q.shape[0], q.shape[1], v.shape[2], dtype=torch.float32, device=q.device)
+    out = torch.empty(q.shape[0], q.shape[1], v.shape[2], dtype=q.dtype, device=q.device)
     m = _lib.TzrHstuAttn()
     _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
     _operands(m, out=out)
-    _lib.launch("tzr_hstu_attn_fwd", m, q.device)
+    _lib.launch(_entry("fwd", q.dtype), m, q.device)
     return out
 
 
@@ -140,15 +158,15 @@ def hstu_attn_bwd(gout, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, m
                   scaling_seqlen) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """tzr_hstu_attn_bwd -> dq, dk, dv: column slices of ONE [L, H (2 Da + Dv)] buffer, every row written by the kernels"""
     (L, H, Da), Dv = q.shape, v.shape[2]
-    g = gout.to(torch.float32)
-    if L > 0 and not _lib.heads_ok(g):
+    g = gout.to(q.dtype)
+    if L > 0 and not _heads_ok(g):
         g = g.clone(memory_format=torch.contiguous_format)  # (.contiguous() keeps the odd strides of a one-row gradient: _lib.rows16)
-    buf = torch.empty(L, H * (2 * Da + Dv), dtype=torch.float32, device=q.device)
+    buf = torch.empty(L, H * (2 * Da + Dv), dtype=q.dtype, device=q.device)
     dq, dk, dv = (t.view(L, H, d) for t, d in zip(torch.split(buf, [H * Da, H * Da, H * Dv], dim=1), (Da, Da, Dv)))
     m = _lib.TzrHstuAttn()
     _fill(m, max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
     _operands(m, grad_out=g, dq=dq, dk=dk, dv=dv)
-    _lib.launch("tzr_hstu_attn_bwd", m, q.device)
+    _lib.launch(_entry("bwd", q.dtype), m, q.device)
     return dq, dk, dv
 
 
@@ -189,7 +207,8 @@ def hstu_mha(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.Tensor, v
     if attn_func is not None:
         raise NotImplementedError("hstu_mha: attn_func (SLA / NFUNC masks) is not built")
     max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen = int(max_seq_len), int(max_attn_len), int(contextual_seq_len), int(scaling_seqlen)
-    if FUSED_HSTU_MHA and not double_backward and (q.is_cuda or _lib.emulated()) and q.dtype == torch.float32 and \
+    if FUSED_HSTU_MHA and not double_backward and (q.is_cuda or _lib.emulated()) and \
+            (q.dtype == torch.float32 or (q.dtype == torch.bfloat16 and FUSED_HSTU_MHA_BF16)) and \
             hstu_mha_ok(max_seq_len, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len):
         return _HstuMhaFn.apply(q, k, v, seq_offsets, num_targets, (max_seq_len, float(alpha), max_attn_len, contextual_seq_len, scaling_seqlen))
     return hstu_mha_literal(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)

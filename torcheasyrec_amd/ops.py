@@ -263,7 +263,7 @@ def hstu_mha_fwd(q: Tensor, k: Tensor, v: Tensor, seq_offsets: Tensor, num_targe
 
 @hstu_mha_fwd.register_fake
 def _(q, k, v, seq_offsets, num_targets, max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen):
-    return q.new_empty(q.shape[0], q.shape[1], v.shape[2], dtype=torch.float32)
+    return q.new_empty(q.shape[0], q.shape[1], v.shape[2])  # (fp32, or bf16 from tzr_hstu_attn_bf16_fwd: the inputs' dtype)
 
 
 @torch.library.custom_op(f"{_NS}::hstu_mha_bwd", mutates_args=())
@@ -280,7 +280,7 @@ def hstu_mha_bwd(gout: Tensor, q: Tensor, k: Tensor, v: Tensor, seq_offsets: Ten
 
 @hstu_mha_bwd.register_fake
 def _(gout, q, k, v, seq_offsets, num_targets, max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen):
-    return (q.new_empty(q.shape, dtype=torch.float32), q.new_empty(q.shape, dtype=torch.float32), v.new_empty(v.shape, dtype=torch.float32))
+    return (q.new_empty(q.shape), q.new_empty(q.shape), v.new_empty(v.shape))
 
 
 def _hstu_setup(ctx, inputs, output):
