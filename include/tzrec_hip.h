@@ -1092,6 +1092,60 @@ int tzr_hstu_attn_bwd(const TzrHstuAttn* h_at, void* stream);
 int tzr_hstu_attn_bf16_fwd(const TzrHstuAttn* h_at, void* stream);
 int tzr_hstu_attn_bf16_bwd(const TzrHstuAttn* h_at, void* stream);
 
+/* HSTU's delta attention (tzrec/ops/hstu_attention.py::delta_hstu_mha under STULayer.cached_forward): the last `delta` rows of
+ * every sample as queries against that sample's whole key / value sequence, forward only, fp32 (csrc/hstu_delta.hip).
+ *   Keys and values come from two segments, read where they lie (no concatenated copy exists):
+ *     cached rows  k [Nc, H, Da], v [Nc, H, Dv], jagged by offsets [B + 1] (clamped into [0, Nc]): n1_b rows of sample b;
+ *     delta rows   k_delta [B delta, H, Da], v_delta [B delta, H, Dv], dense (sample b owns the rows b delta .. b delta + delta - 1),
+ *                  behind the cached rows: n_b = n1_b + delta.  k_delta == 0 and v_delta == 0 (both or neither): n_b = n1_b, k / v
+ *                  hold the full sequences and their last delta rows are the delta keys (the reference's form).
+ *   Every operand is pointer + floats between rows + floats between heads, by the rules of tzr_hstu_attn_* (the column slices of
+ *   a uvqk matrix pass).  delta_q [B delta, H, Da].  For sample b, head h, delta row r, with i = n_b - delta + r:
+ *     out[b delta + r, h, :] = sum_{j < n_b} valid(i, j) silu(alpha <delta_q[b delta + r, h], k_b[j, h]>) / scale v_b[j, h, :]
+ *   valid, id, max_id and scale exactly as for tzr_hstu_attn_* above, on the n_b rows of the full sequence (max_seq_len counts
+ *   cache + delta).  A sample with n_b > max_seq_len or n_b < delta gets zeros in all its delta rows: the caller's duty, made
+ *   memory-safe.  A call that launches writes every row of out.
+ *   A workgroup owns (sample, head, 16 delta rows, TZR_HSTU_DELTA_CHUNK keys); its four waves take different 16-key tiles and their
+ *   partials are added in wave order.  ceil(max_seq_len / TZR_HSTU_DELTA_CHUNK) > 1 chunks: each workgroup stores its partial in
+ *   `ws` (tzr_hstu_delta_workspace bytes: [chunks][B delta][H][Dv] floats) and a finishing launch adds the chunks a sample has in
+ *   order 0, 1, ..  No atomics: two runs are bit-equal, and the two forms on the same rows are bit-equal.  Key tiles without a
+ *   valid pair (in front of the window, targets of other rows) are skipped.  The grid follows max_seq_len alone: nothing is read
+ *   back on the host.
+ * Order of the checks: B, Nc, max_attn_len or contextual_seq_len < 0 (TZR_ERR_INVALID); the limits (TZR_ERR_UNSUPPORTED): Da, Dv
+ *   multiples of 4 in [4, TZR_HSTU_MAX_DIM], H >= 1, delta >= 1, 1 <= max_seq_len <= TZR_HSTU_MAX_SEQ_LEN, max_attn_len and
+ *   contextual_seq_len at most that, Nc and B delta H < 2^31, chunks x ceil(delta / 16) x B x H < 2^31 (the grid); B == 0: TZR_OK
+ *   without a launch; then pointers (null or misaligned: TZR_ERR_INVALID; k and v are looked at only when Nc > 0; one of k_delta /
+ *   v_delta without the other: TZR_ERR_INVALID) and strides (TZR_ERR_UNSUPPORTED); with more than one chunk, ws null, not 256-byte
+ *   aligned or too small: TZR_ERR_WORKSPACE.  A refused call launches nothing.  A new struct and entry points, no change to
+ *   existing ones: the ABI version stays 15. */
+#ifndef TZR_HSTU_DELTA_CHUNK       /* (scripts/profile_hstu_delta.py times libraries built with other values) */
+#define TZR_HSTU_DELTA_CHUNK 256
+#endif
+typedef struct TzrHstuDelta {
+  int64_t B, Nc;
+  int32_t H, Da, Dv, delta, max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen;
+  float alpha;
+  int32_t reserved;
+  uint64_t delta_q;                  /* const float* [B delta, H, Da] */
+  int64_t delta_q_stride, delta_q_head_stride;
+  uint64_t k;                        /* const float* [Nc, H, Da] */
+  int64_t k_stride, k_head_stride;
+  uint64_t v;                        /* const float* [Nc, H, Dv] */
+  int64_t v_stride, v_head_stride;
+  uint64_t k_delta;                  /* const float* [B delta, H, Da], nullable (with v_delta) */
+  int64_t k_delta_stride, k_delta_head_stride;
+  uint64_t v_delta;                  /* const float* [B delta, H, Dv], nullable (with k_delta) */
+  int64_t v_delta_stride, v_delta_head_stride;
+  uint64_t offsets;                  /* const int64_t* [B + 1]: the cached rows (the full rows without k_delta) */
+  uint64_t num_targets;              /* const int64_t* [B], nullable */
+  uint64_t out;                      /* float* [B delta, H, Dv] */
+  int64_t out_stride, out_head_stride;
+  uint64_t ws;                       /* workspace, read only with more than one chunk */
+  uint64_t ws_bytes;
+} TzrHstuDelta;
+size_t tzr_hstu_delta_workspace(const TzrHstuDelta* h_dl);
+int tzr_hstu_delta_fwd(const TzrHstuDelta* h_dl, void* stream);
+
 /* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
  * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
  *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied

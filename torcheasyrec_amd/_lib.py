@@ -241,6 +241,27 @@ class TzrHstuAttn(C.Structure):
 
 
 assert C.sizeof(TzrHstuAttn) == 264
+# keys a workgroup of tzr_hstu_delta_fwd (TZR_HSTU_DELTA_CHUNK)
+HSTU_DELTA_CHUNK = 256
+
+
+class TzrHstuDelta(C.Structure):
+    _fields_ = [
+        ("B", C.c_int64), ("Nc", C.c_int64), ("H", C.c_int32), ("Da", C.c_int32), ("Dv", C.c_int32), ("delta", C.c_int32),
+        ("max_seq_len", C.c_int32), ("max_attn_len", C.c_int32), ("contextual_seq_len", C.c_int32), ("scaling_seqlen", C.c_int32),
+        ("alpha", C.c_float), ("reserved", C.c_int32),
+        ("delta_q", C.c_uint64), ("delta_q_stride", C.c_int64), ("delta_q_head_stride", C.c_int64),
+        ("k", C.c_uint64), ("k_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v", C.c_uint64), ("v_stride", C.c_int64), ("v_head_stride", C.c_int64),
+        ("k_delta", C.c_uint64), ("k_delta_stride", C.c_int64), ("k_delta_head_stride", C.c_int64),
+        ("v_delta", C.c_uint64), ("v_delta_stride", C.c_int64), ("v_delta_head_stride", C.c_int64),
+        ("offsets", C.c_uint64), ("num_targets", C.c_uint64),
+        ("out", C.c_uint64), ("out_stride", C.c_int64), ("out_head_stride", C.c_int64),
+        ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrHstuDelta) == 232
 # limit and rows per workgroup of tzr_stu_output_* (include/tzrec_hip.h: TZR_STU_OUT_*)
 STU_OUT_MAX_DIM, STU_OUT_BLOCK = 512, 32
 
@@ -510,6 +531,8 @@ _SIGNATURES = {
     "tzr_hstu_attn_bwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_bf16_fwd": (_i32, [_vp, _vp]),
     "tzr_hstu_attn_bf16_bwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_delta_workspace": (_sz, [_vp]),
+    "tzr_hstu_delta_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
     "tzr_stu_output_bwd": (_i32, [_vp, _vp]),

@@ -8,6 +8,13 @@ take csrc/hstu_attention_bf16.hip (tzr_hstu_attn_bf16_fwd / _bwd: the same launc
 out and gradients) when FUSED_HSTU_MHA_BF16 is on as well; mixed dtypes and fp16 take the literal form.  Built: causal, no
 attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32 and bf16; the rest is refused by name.
 
+`delta_hstu_mha` is the serving side (the reference's delta_hstu_mha under STULayer.cached_forward): the last `delta` rows of every
+sample against the sample's cached keys and values plus the delta rows' own.  With FUSED_HSTU_DELTA on and `delta_hstu_mha_ok`
+taking the operands it runs csrc/hstu_delta.hip (tzr_hstu_delta_fwd: forward only, fp32; the keys split over the waves of a
+workgroup and over workgroups, the cache and the delta rows read where they lie -- the reference's concatenated full_k / full_v
+are never built); otherwise `delta_hstu_mha_literal`, the padded torch form.  STULayer.forward with `kv_caching_lengths` fills the
+layer's cache (prefill), STULayer / STUStack.cached_forward score new rows against it.
+
 `stu_output` is the layer's stage behind the attention (the reference's hstu_compute_output): silu(u), the layer or group norm of
 the attention's rows, their product, the concat [u, attn, y], dropout and addmm(x, ., `_output_weight`) on csrc/stu_output.hip
 (tzr_stu_output_fwd / _bwd: one launch forward, two backward and a finishing one; the concat, the normed rows and the dropout
@@ -27,10 +34,13 @@ from . import _lib
 FUSED_STU_OUTPUT = False  # profiles/stu_output, forward + backward: 6.20 ms fused against 2.84 ms literal (0.56 against 0.94 GB): the literal form stays
 FUSED_HSTU_MHA = True  # profiles/hstu_attention, forward + backward: 24.4 ms fused against 32.4 ms literal, 0.72 against 14.06 GB
 FUSED_HSTU_MHA_BF16 = True  # bf16 q, k, v on csrc/hstu_attention_bf16.hip (needs FUSED_HSTU_MHA too); profiles/hstu_attention_bf16
+FUSED_HSTU_DELTA = True  # profiles/hstu_delta, one serving step: 95.1 us fused (94.6 - 100.9) against 646.7 us literal (644.3 - 703.2), 9.4 against 249.5 MB
 
 
-def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int) -> torch.Tensor:
-    """_get_valid_attn_mask (tzrec/ops/_pytorch/pt_hstu_attention.py) with causal=True on the rows each sample keeps: n [B] -> bool [B, N, N]"""
+def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int,
+                    rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """_get_valid_attn_mask (tzrec/ops/_pytorch/pt_hstu_attention.py) with causal=True on the rows each sample keeps: n [B] -> bool
+    [B, N, N]; with `rows` [B, R] (query positions in [0, N)) only those query rows: bool [B, R, N]"""
     ids = torch.arange(N, device=n.device).view(1, N)
     max_ids = n.view(-1, 1)
     if contextual_seq_len > 0:
@@ -40,9 +50,13 @@ def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor]
         max_ids = max_ids - num_targets.view(-1, 1)
         ids = torch.minimum(ids, max_ids)
     ids = ids.expand(n.numel(), N)
-    row, col, max_ids = ids.unsqueeze(2), ids.unsqueeze(1), max_ids.unsqueeze(2)
+    col, max_ids = ids.unsqueeze(1), max_ids.unsqueeze(2)
+    if rows is None:
+        row, eye = ids.unsqueeze(2), torch.eye(N, device=n.device, dtype=torch.bool).unsqueeze(0)
+    else:
+        row, eye = ids.gather(1, rows).unsqueeze(2), rows.unsqueeze(2) == torch.arange(N, device=n.device).view(1, 1, N)
     dist = row - col
-    valid = torch.eye(N, device=n.device, dtype=torch.bool).unsqueeze(0) | (dist > 0)
+    valid = eye | (dist > 0)
     if max_attn_len > 0:
         valid = valid & (dist <= max_attn_len)
     if contextual_seq_len > 0:
@@ -214,6 +228,138 @@ def hstu_mha(max_seq_len: int, alpha: float, q: torch.Tensor, k: torch.Tensor, v
     return hstu_mha_literal(max_seq_len, alpha, q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, scaling_seqlen)
 
 
+def concat_cache_delta(cache: torch.Tensor, delta_rows: torch.Tensor, cache_offsets: torch.Tensor, delta: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's concat_2D_jagged of the cached rows (jagged by cache_offsets [B + 1]; rows behind offsets[B] are spare) with
+    `delta` dense rows a sample -> (full rows [cache rows + B delta, ..], their offsets).  Plain torch ops, nothing read back."""
+    B, Lc, dev = cache_offsets.numel() - 1, cache.shape[0], cache.device
+    full_offsets = cache_offsets + delta * torch.arange(B + 1, device=dev)
+    pos = torch.arange(Lc + delta_rows.shape[0], device=dev)
+    b = torch.bucketize(pos, full_offsets[1:], right=True).clamp(max=max(B - 1, 0))
+    pos = pos - full_offsets[b]
+    n1 = (cache_offsets[1:] - cache_offsets[:-1])[b]
+    src = torch.where(pos < n1, cache_offsets[b] + pos, Lc + b * delta + (pos - n1).clamp(max=delta - 1))  # (spare rows: some delta row)
+    return torch.cat([cache, delta_rows])[src], full_offsets
+
+
+def delta_hstu_mha_literal(max_seq_len: int, alpha: float, delta_q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+                           num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0,
+                           scaling_seqlen: int = -1, delta_k: Optional[torch.Tensor] = None, delta_v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's padded form (pytorch_cached_hstu_mha) out of plain torch ops; in the two-segment form it concatenates the
+    cached and the delta rows first.  A sample whose n is above max_seq_len or below delta gets zero rows."""
+    (Ld, H, Da), Dv = delta_q.shape, v.shape[2]
+    N, B = int(max_seq_len), seq_offsets.numel() - 1
+    if B == 0 or Ld == 0:
+        return v.new_zeros(Ld, H, Dv)
+    delta = Ld // B
+    if delta_k is not None:
+        cache_offsets = seq_offsets
+        k, seq_offsets = concat_cache_delta(k.reshape(k.shape[0], H * Da), delta_k.reshape(Ld, H * Da), cache_offsets, delta)
+        v, _ = concat_cache_delta(v.reshape(v.shape[0], H * Dv), delta_v.reshape(Ld, H * Dv), cache_offsets, delta)
+    L = k.shape[0]
+    scale = float(scaling_seqlen if scaling_seqlen > 0 else max_seq_len)
+    n = seq_offsets[1:] - seq_offsets[:-1]
+    n = torch.where((n <= N) & (n >= delta), n, torch.zeros_like(n))  # (a refused sample keeps no key: zero rows)
+    pos = torch.arange(N, device=k.device).view(1, N)
+    keep = pos < n.view(-1, 1)
+    idx = (seq_offsets[:-1].view(-1, 1) + pos) % (L + 1)  # (padding as hstu_mha_literal)
+
+    def pad(x, D):  # [L, H D] -> [B, H, N, D], zeros for the rows a sample does not have
+        rows = torch.cat([x.reshape(L, H * D), x.new_zeros(1, H * D)])[idx]
+        return torch.where(keep.unsqueeze(2), rows, rows.new_zeros(())).view(B, N, H, D).transpose(1, 2)
+
+    rows =((n - delta).clamp(min=0).view(-1, 1) + torch.arange(delta, device=k.device).view(1, -1)).clamp(max=N - 1)  # the delta rows' positions
+    qk = F.silu(torch.einsum("bhxa,bhya->bhxy", delta_q.reshape(B, delta, H, Da).transpose(1, 2), pad(k, Da)) * alpha) / scale
+    qk = qk * hstu_valid_mask(n, N, num_targets, max_attn_len, contextual_seq_len, rows).unsqueeze(1)
+    return torch.einsum("bhxy,bhyv->bhxv", qk, pad(v, Dv)).transpose(1, 2).reshape(Ld, H, Dv)
+
+
+def delta_hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, delta: int, max_attn_len: int = 0, contextual_seq_len: int = 0,
+                         B: int = 1) -> Optional[str]:
+    """None when tzr_hstu_delta_fwd has a kernel for the shape, else the limit of csrc/hstu_delta.hip it misses (include/tzrec_hip.h)"""
+    word = hstu_mha_limit(H, Da, Dv, max_seq_len, max_attn_len, contextual_seq_len, 1)
+    if word is not None:
+        return word
+    if delta < 1:
+        return f"delta {delta} must be at least 1"
+    if max(B, 1) * delta * H >= 2 ** 31:
+        return f"rows: {B} x {delta} x {H} must stay below 2^31"
+    chunks = (max_seq_len + _lib.HSTU_DELTA_CHUNK - 1) // _lib.HSTU_DELTA_CHUNK
+    if chunks * ((delta + 15) // 16) * max(B, 1) * H >= 2 ** 31:
+        return f"grid: {chunks} x ceil({delta} / 16) x {B} x {H} workgroups must stay below 2^31"
+    return None
+
+
+def delta_hstu_mha_ok(max_seq_len: int, delta_q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+                      num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0,
+                      delta_k: Optional[torch.Tensor] = None, delta_v: Optional[torch.Tensor] = None) -> bool:
+    """what tzr_hstu_delta_fwd takes: delta_q [B delta, H, Da], k [Nc, H, Da], v [Nc, H, Dv] and, both or neither, delta_k [B delta, H,
+    Da], delta_v [B delta, H, Dv], all fp32 `_lib.heads_ok` operands (column slices of a uvqk matrix are fine), offsets int64 [B + 1]
+    and num_targets int64 [B] contiguous, a shape inside `delta_hstu_mha_limit`, everything on the device of the loaded library"""
+    if delta_q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape[1:] != delta_q.shape[1:] or v.shape[:2] != k.shape[:2] or seq_offsets.dim() != 1:
+        return False
+    dev, (Ld, H, Da), Dv, B = delta_q.device, delta_q.shape, v.shape[2], seq_offsets.numel() - 1
+    if (delta_k is None) != (delta_v is None) or B < 0 or (B == 0 and Ld > 0) or (B > 0 and (Ld == 0 or Ld % B)):
+        return False  # (no sample, yet rows: the entry point launches nothing, so nobody would write the rows)
+    rest = [t for t in (k, v, delta_k, delta_v) if t is not None]
+    if not _lib.takes(delta_q) or any(t.device != dev or t.dtype != torch.float32 for t in (delta_q, *rest)) or seq_offsets.device != dev or k.shape[0] >= 2 ** 31:
+        return False
+    if delta_k is not None and (delta_k.shape != delta_q.shape or delta_v.shape != (Ld, H, Dv)):
+        return False
+    if delta_hstu_mha_limit(H, Da, Dv, max_seq_len, Ld // B if B else 1, max_attn_len, contextual_seq_len, B) is not None:
+        return False
+    if seq_offsets.dtype != torch.int64 or not seq_offsets.is_contiguous():
+        return False
+    if num_targets is not None and not (num_targets.shape == (B,) and num_targets.dtype == torch.int64 and num_targets.is_contiguous() and num_targets.device == dev):
+        return False
+    return all(t.shape[0] == 0 or _lib.heads_ok(t) for t in (delta_q, *rest))
+
+
+class _HstuDeltaFn:
+    """tzr_hstu_delta_fwd on operands `delta_hstu_mha_ok` took.  Forward only: no autograd node (an input that needs a gradient
+    takes the literal form).  Capturable: every buffer is torch's, the workspace included; nothing is read back."""
+
+    calls = 0  # calls that took the kernel (tests)
+
+    @staticmethod
+    def apply(delta_q, k, v, seq_offsets, num_targets, delta_k, delta_v, cfg) -> torch.Tensor:
+        _HstuDeltaFn.calls += 1
+        max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen = cfg
+        (Ld, H, Da), Dv, B = delta_q.shape, v.shape[2], seq_offsets.numel() - 1
+        out = torch.empty(Ld, H, Dv, dtype=torch.float32, device=delta_q.device)  # (the kernels write every row)
+        if B == 0:
+            return out
+        m = _lib.TzrHstuDelta()
+        m.B, m.Nc, m.H, m.Da, m.Dv, m.delta = B, k.shape[0], H, Da, Dv, Ld // B
+        m.max_seq_len, m.max_attn_len, m.contextual_seq_len, m.scaling_seqlen, m.alpha = max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen, alpha
+        m.offsets, m.num_targets = _lib.ptr(seq_offsets), _lib.opt_ptr(num_targets)
+        _operands(m, delta_q=delta_q.detach(), k=k.detach(), v=v.detach(), out=out)
+        if delta_k is not None:
+            _operands(m, k_delta=delta_k.detach(), v_delta=delta_v.detach())
+        _lib.launch_ws("tzr_hstu_delta", m, delta_q.device, "tzr_hstu_delta_fwd")
+        return out
+
+
+def delta_hstu_mha(max_seq_len: int, alpha: float, delta_q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
+                   num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0, scaling_seqlen: int = -1,
+                   delta_k: Optional[torch.Tensor] = None, delta_v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's delta_hstu_mha: the last delta = delta_q.shape[0] // B rows of every sample as queries [B delta, H, Da] against
+    the sample's whole sequence -> [B delta, H, Dv].  Without delta_k / delta_v, k [L, H, Da], v [L, H, Dv] and seq_offsets are the
+    FULL sequences (the reference's meaning: their last delta rows are the delta keys).  With them, k, v, seq_offsets are the cached
+    rows alone and delta_k [B delta, H, Da], delta_v [B delta, H, Dv] follow them: the kernel reads both segments where they lie.
+    max_seq_len counts cache + delta in both forms; a sample above it (or, in the one-segment form, shorter than delta) gets zero
+    rows.  The kernel (csrc/hstu_delta.hip) is forward only: with FUSED_HSTU_DELTA off, an input that needs a gradient, a dtype
+    other than fp32 or a shape outside `delta_hstu_mha_limit`, the literal form runs."""
+    max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen = int(max_seq_len), int(max_attn_len), int(contextual_seq_len), int(scaling_seqlen)
+    given = [t for t in (delta_q, k, v, delta_k, delta_v) if t is not None]
+    if FUSED_HSTU_DELTA and (delta_q.is_cuda or _lib.emulated()) and delta_q.dtype == torch.float32 and \
+            not (torch.is_grad_enabled() and any(t.requires_grad for t in given)) and \
+            delta_hstu_mha_ok(max_seq_len, delta_q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, delta_k, delta_v):
+        return _HstuDeltaFn.apply(delta_q, k, v, seq_offsets, num_targets, delta_k, delta_v,
+                                  (max_seq_len, float(alpha), max_attn_len, contextual_seq_len, scaling_seqlen))
+    return delta_hstu_mha_literal(max_seq_len, alpha, delta_q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len,
+                                  scaling_seqlen, delta_k, delta_v)
+
+
 def stu_output_literal(u: torch.Tensor, attn: torch.Tensor, x: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tensor,
                        output_weight: torch.Tensor, num_heads: int, group_norm: bool, dropout_ratio: float, training: bool,
                        eps: float = 1e-6) -> torch.Tensor:
@@ -353,6 +499,7 @@ class STULayer(nn.Module):
             raise NotImplementedError("STULayer: sla_k1 / sla_k2 (SLA masks) are not built")
         if not causal:
             raise NotImplementedError("STULayer: causal=False is not built")
+        self.reset_kv_cache()
         self._num_heads, self._embedding_dim, self._hidden_dim, self._attention_dim = num_heads, embedding_dim, hidden_dim, attention_dim
         self._output_dropout_ratio, self._target_aware = output_dropout_ratio, target_aware
         self._max_attn_len = max_attn_len or 0
@@ -372,12 +519,12 @@ class STULayer(nn.Module):
 
     def forward(self, x: torch.Tensor, x_offsets: torch.Tensor, max_seq_len: int, num_targets: Optional[torch.Tensor] = None,
                 max_kv_caching_len: int = 0, kv_caching_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if max_kv_caching_len > 0 or kv_caching_lengths is not None:
-            raise NotImplementedError("STULayer: max_kv_caching_len / kv_caching_lengths (the kv cache) are not built")
+        """With `kv_caching_lengths` [B] (prefill) the first kv_caching_lengths[b] rows of k and v of every sample are kept as the
+        layer's cache (the reference's _update_kv_cache).  max_kv_caching_len == 0 reads their maximum back once, as the reference
+        does: a prefill captures into a hipGraph only with max_kv_caching_len given."""
         H, Dv, Da = self._num_heads, self._hidden_dim, self._attention_dim
-        normed = F.layer_norm(x, (self._embedding_dim,), self._input_norm_weight, self._input_norm_bias, 1e-6)
-        uvqk = torch.addmm(self._uvqk_beta, normed, self._uvqk_weight)
-        u, v, q, k = torch.split(uvqk, [Dv * H, Dv * H, Da * H, Da * H], dim=1)
+        u, v, q, k = self._uvqk(x)
+        self.update_kv_cache(max_seq_len, x_offsets, k, v, max_kv_caching_len, kv_caching_lengths)
         L = x.shape[0]
         attn = hstu_mha(max_seq_len, self._attn_alpha, q.view(L, H, Da), k.view(L, H, Da), v.view(L, H, Dv), x_offsets,
                         num_targets=num_targets if self._target_aware else None, max_attn_len=self._max_attn_len,
@@ -385,8 +532,67 @@ class STULayer(nn.Module):
         return stu_output(u, attn, x, self._output_norm_weight, self._output_norm_bias, self._output_weight, H, self._use_group_norm,
                           self._output_dropout_ratio, self.training)
 
-    def cached_forward(self, *args, **kwargs):
-        raise NotImplementedError("STULayer: cached_forward (the delta / kv-cache attention) is not built")
+    def _uvqk(self, x: torch.Tensor):
+        """input norm and the uvqk product -> the u, v, q, k column slices [rows, H D] where the product left them"""
+        H, Dv, Da = self._num_heads, self._hidden_dim, self._attention_dim
+        normed = F.layer_norm(x, (self._embedding_dim,), self._input_norm_weight, self._input_norm_bias, 1e-6)
+        uvqk = torch.addmm(self._uvqk_beta, normed, self._uvqk_weight)
+        return torch.split(uvqk, [Dv * H, Dv * H, Da * H, Da * H], dim=1)
+
+    def reset_kv_cache(self) -> None:
+        self.k_cache: Optional[torch.Tensor] = None  # [rows, H Da]; the rows behind kv_caching_offsets[B] are spare
+        self.v_cache: Optional[torch.Tensor] = None  # [rows, H Dv]
+        self.kv_caching_offsets: Optional[torch.Tensor] = None
+        self.max_kv_caching_len = 0
+
+    def update_kv_cache(self, max_seq_len: int, seq_offsets: torch.Tensor, k: torch.Tensor, v: torch.Tensor, max_kv_caching_len: int,
+                        kv_caching_lengths: Optional[torch.Tensor]) -> None:
+        """The reference's _update_kv_cache: with kv_caching_lengths [B], the first kv_caching_lengths[b] rows of k, v [L, H D] of
+        every sample, packed sample after sample, replace the cache; without, the cache stays.  The packed rows are written into
+        buffers of L + 1 rows (the count of kept rows is not read back; the last row takes the rows that are not kept)."""
+        if kv_caching_lengths is None:
+            return
+        L, B, dev = k.shape[0], seq_offsets.numel() - 1, k.device
+        offsets = torch.cat([kv_caching_lengths.new_zeros(1), kv_caching_lengths.cumsum(0)]).to(torch.int64)
+        pos = torch.arange(L, device=dev)
+        b = torch.bucketize(pos, seq_offsets[1:], right=True).clamp(max=max(B - 1, 0))
+        pos = pos - seq_offsets[b]
+        dst = torch.where((pos >= 0) & (pos < kv_caching_lengths[b]), offsets[b] + pos, torch.full_like(pos, L)) if B > 0 else torch.full_like(pos, L)
+        self.k_cache = k.new_zeros(L + 1, k.shape[1]).index_copy_(0, dst, k.detach())
+        self.v_cache = v.new_zeros(L + 1, v.shape[1]).index_copy_(0, dst, v.detach())
+        self.kv_caching_offsets = offsets
+        self.max_kv_caching_len = int(max_kv_caching_len) if max_kv_caching_len > 0 else (int(kv_caching_lengths.max().item()) if B > 0 else 0)
+
+    def construct_full_kv(self, delta_k: torch.Tensor, delta_v: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, int, torch.Tensor]:
+        """The reference's _construct_full_kv out of torch ops: the cached rows of every sample followed by its rows of delta_k, delta_v
+        [B delta, H D] -> (full_k, full_v, max_kv_caching_len + delta, their offsets).  `cached_forward` needs it only for a re-split."""
+        delta = delta_k.shape[0] // (self.kv_caching_offsets.numel() - 1)
+        full_k, offsets = concat_cache_delta(self.k_cache, delta_k, self.kv_caching_offsets, delta)
+        full_v, _ = concat_cache_delta(self.v_cache, delta_v, self.kv_caching_offsets, delta)
+        return full_k, full_v, self.max_kv_caching_len + delta, offsets
+
+    def cached_forward(self, delta_x: torch.Tensor, num_targets: Optional[torch.Tensor], max_kv_caching_len: int = 0,
+                       kv_caching_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The layer on delta = delta_x.shape[0] // B new rows a sample behind the cached ones (the reference's cached_forward): norm
+        and uvqk on the delta rows, `delta_hstu_mha` in its two-segment form on the cache and the delta slices of uvqk where they lie
+        (full_k / full_v are not built), `stu_output`.  With `kv_caching_lengths` (a re-split of cache + delta into a new cache) the
+        full rows are built with torch ops as the reference does, and the attention takes them in the one-segment form."""
+        if self.kv_caching_offsets is None:
+            raise RuntimeError("STULayer.cached_forward: no kv cache (run forward with kv_caching_lengths first)")
+        H, Dv, Da, Ld = self._num_heads, self._hidden_dim, self._attention_dim, delta_x.shape[0]
+        u, v, q, k = self._uvqk(delta_x)
+        B = self.kv_caching_offsets.numel() - 1
+        kw = dict(num_targets=num_targets if self._target_aware else None, max_attn_len=self._max_attn_len,
+                  contextual_seq_len=self._contextual_seq_len, scaling_seqlen=self._scaling_seqlen)
+        if kv_caching_lengths is None:
+            attn = delta_hstu_mha(self.max_kv_caching_len + Ld // max(B, 1), self._attn_alpha, q.view(Ld, H, Da), self.k_cache.view(-1, H, Da),
+                                  self.v_cache.view(-1, H, Dv), self.kv_caching_offsets, delta_k=k.view(Ld, H, Da), delta_v=v.view(Ld, H, Dv), **kw)
+        else:
+            full_k, full_v, max_seq_len, offsets = self.construct_full_kv(k, v)
+            self.update_kv_cache(max_seq_len, offsets, full_k, full_v, max_kv_caching_len, kv_caching_lengths)
+            attn = delta_hstu_mha(max_seq_len, self._attn_alpha, q.view(Ld, H, Da), full_k.view(-1, H, Da), full_v.view(-1, H, Dv), offsets, **kw)
+        return stu_output(u, attn.reshape(Ld, H * Dv), delta_x, self._output_norm_weight, self._output_norm_bias, self._output_weight, H,
+                          self._use_group_norm, self._output_dropout_ratio, self.training)
 
 
 class STUStack(nn.Module):
@@ -404,5 +610,9 @@ class STUStack(nn.Module):
             x = layer(x, x_offsets, max_seq_len, num_targets, max_kv_caching_len, kv_caching_lengths)
         return x
 
-    def cached_forward(self, *args, **kwargs):
-        raise NotImplementedError("STUStack: cached_forward (the delta / kv-cache attention) is not built")
+    def cached_forward(self, delta_x: torch.Tensor, num_targets: Optional[torch.Tensor], max_kv_caching_len: int = 0,
+                       kv_caching_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the layers' `cached_forward` in order, each against its own cache"""
+        for layer in self._stu_layers:
+            delta_x = layer.cached_forward(delta_x, num_targets, max_kv_caching_len, kv_caching_lengths)
+        return delta_x
