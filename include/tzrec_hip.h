@@ -1146,6 +1146,25 @@ typedef struct TzrHstuDelta {
 size_t tzr_hstu_delta_workspace(const TzrHstuDelta* h_dl);
 int tzr_hstu_delta_fwd(const TzrHstuDelta* h_dl, void* stream);
 
+/* The same operation on bf16 operands (csrc/hstu_delta_bf16.hip, v_mfma_f32_16x16x32_bf16 with fp32 accumulators), forward only:
+ * the same struct, read with bf16 pointers (delta_q, k, v, k_delta, v_delta, out all bf16) and strides in bf16 ELEMENTS; the same
+ * two segments, mask, skipped tiles, zeros for a refused sample and order of checks.  A workgroup owns (sample, head, 16 delta
+ * rows, TZR_HSTU_DELTA_CHUNK keys); its four waves take different 32-key tiles.  Numeric contract, that of tzr_hstu_attn_bf16_*:
+ *   - scores s = alpha <q, k> accumulate in fp32 from the bf16 operands; sigmoid, the mask and 1 / scale are fp32;
+ *   - P = valid silu(s) / scale is rounded ONCE to bf16, to nearest even, as the second product's operand;
+ *   - out accumulates in fp32 over all its keys -- the four waves' partials are added in wave order in fp32 and, with more than
+ *     one chunk, the chunks' fp32 partials in order 0, 1, .. by a finishing launch -- and is rounded once to bf16 at its single
+ *     store.  No atomics: two runs are bit-equal, and the two forms on the same rows are bit-equal.
+ * The workspace is the fp32 entry's: tzr_hstu_delta_workspace bytes, [chunks][B delta][H][Dv] FLOATS, read only with more than one
+ *   chunk (null, not 256-byte aligned or too small: TZR_ERR_WORKSPACE).
+ * Limits (TZR_ERR_UNSUPPORTED beyond): Da, Dv multiples of 8 in [8, TZR_HSTU_MAX_DIM] (independently; a width that is no multiple
+ *   of 32 is padded with zeros in registers); unit column stride, row and head strides multiples of 8 elements, head stride >=
+ *   the width, row stride >= (H - 1) head stride + width (the column slices of one bf16 uvqk matrix are read where they lie); the
+ *   other limits of tzr_hstu_delta_fwd.  TZR_ERR_INVALID: a null struct, a null pointer or one not 16-byte aligned, negative
+ *   sizes.  B == 0: TZR_OK without a launch, whatever the pointers are.  A new entry point on the existing struct: the ABI
+ *   version stays 15. */
+int tzr_hstu_delta_bf16_fwd(const TzrHstuDelta* h_dl, void* stream);
+
 /* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
  * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
  *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied

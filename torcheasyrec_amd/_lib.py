@@ -533,6 +533,7 @@ _SIGNATURES = {
     "tzr_hstu_attn_bf16_bwd": (_i32, [_vp, _vp]),
     "tzr_hstu_delta_workspace": (_sz, [_vp]),
     "tzr_hstu_delta_fwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_delta_bf16_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
     "tzr_stu_output_bwd": (_i32, [_vp, _vp]),

@@ -12,7 +12,9 @@ attention dropout, no min_full_attn_seq_len, no attn_func (SLA), fp32 and bf16; 
 sample against the sample's cached keys and values plus the delta rows' own.  With FUSED_HSTU_DELTA on and `delta_hstu_mha_ok`
 taking the operands it runs csrc/hstu_delta.hip (tzr_hstu_delta_fwd: forward only, fp32; the keys split over the waves of a
 workgroup and over workgroups, the cache and the delta rows read where they lie -- the reference's concatenated full_k / full_v
-are never built); otherwise `delta_hstu_mha_literal`, the padded torch form.  STULayer.forward with `kv_caching_lengths` fills the
+are never built) or, on bf16 operands with FUSED_HSTU_DELTA_BF16 on as well, csrc/hstu_delta_bf16.hip (tzr_hstu_delta_bf16_fwd: the
+same split on the bf16 MFMAs, fp32 accumulation, bf16 out -- a stack cast to bf16 keeps a bf16 cache and serves from it);
+otherwise -- mixed dtypes and fp16 too -- `delta_hstu_mha_literal`, the padded torch form.  STULayer.forward with `kv_caching_lengths` fills the
 layer's cache (prefill), STULayer / STUStack.cached_forward score new rows against it.
 
 `stu_output` is the layer's stage behind the attention (the reference's hstu_compute_output): silu(u), the layer or group norm of
@@ -35,6 +37,9 @@ FUSED_STU_OUTPUT = False  # profiles/stu_output, forward + backward: 6.20 ms fus
 FUSED_HSTU_MHA = True  # profiles/hstu_attention, forward + backward: 24.4 ms fused against 32.4 ms literal, 0.72 against 14.06 GB
 FUSED_HSTU_MHA_BF16 = True  # bf16 q, k, v on csrc/hstu_attention_bf16.hip (needs FUSED_HSTU_MHA too); profiles/hstu_attention_bf16
 FUSED_HSTU_DELTA = True  # profiles/hstu_delta, one serving step: 95.1 us fused (94.6 - 100.9) against 646.7 us literal (644.3 - 703.2), 9.4 against 249.5 MB
+# bf16 operands on csrc/hstu_delta_bf16.hip (needs FUSED_HSTU_DELTA too); profiles/hstu_delta_bf16, the same step: 54.7 us fused (54.5 - 63.5)
+# against 634.7 us for the literal form in bf16 (618.4 - 697.2) and 102.3 us for the fp32 kernel, 9.2 against 127.0 MB
+FUSED_HSTU_DELTA_BF16 = True
 
 
 def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int,
@@ -245,8 +250,13 @@ def delta_hstu_mha_literal(max_seq_len: int, alpha: float, delta_q: torch.Tensor
                            num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0,
                            scaling_seqlen: int = -1, delta_k: Optional[torch.Tensor] = None, delta_v: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The reference's padded form (pytorch_cached_hstu_mha) out of plain torch ops; in the two-segment form it concatenates the
-    cached and the delta rows first.  A sample whose n is above max_seq_len or below delta gets zero rows."""
+    cached and the delta rows first.  A sample whose n is above max_seq_len or below delta gets zero rows.  Operands of mixed
+    dtypes (a bf16 delta_q on an fp32 cache) are promoted to their common dtype first."""
     (Ld, H, Da), Dv = delta_q.shape, v.shape[2]
+    common = v.dtype
+    for t in (delta_q, k, delta_k, delta_v):
+        common = common if t is None else torch.promote_types(common, t.dtype)
+    delta_q, k, v, delta_k, delta_v = (t if t is None or t.dtype == common else t.to(common) for t in (delta_q, k, v, delta_k, delta_v))
     N, B = int(max_seq_len), seq_offsets.numel() - 1
     if B == 0 or Ld == 0:
         return v.new_zeros(Ld, H, Dv)
@@ -274,9 +284,10 @@ def delta_hstu_mha_literal(max_seq_len: int, alpha: float, delta_q: torch.Tensor
 
 
 def delta_hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, delta: int, max_attn_len: int = 0, contextual_seq_len: int = 0,
-                         B: int = 1) -> Optional[str]:
-    """None when tzr_hstu_delta_fwd has a kernel for the shape, else the limit of csrc/hstu_delta.hip it misses (include/tzrec_hip.h)"""
-    word = hstu_mha_limit(H, Da, Dv, max_seq_len, max_attn_len, contextual_seq_len, 1)
+                         B: int = 1, dtype: torch.dtype = torch.float32) -> Optional[str]:
+    """None when tzr_hstu_delta_fwd (fp32) or tzr_hstu_delta_bf16_fwd (bf16) has a kernel for the shape, else the limit of
+    csrc/hstu_delta.hip / hstu_delta_bf16.hip it misses (include/tzrec_hip.h): the widths go in steps of 4 (fp32) or 8 (bf16)"""
+    word = hstu_mha_limit(H, Da, Dv, max_seq_len, max_attn_len, contextual_seq_len, 1, dtype)
     if word is not None:
         return word
     if delta < 1:
@@ -292,31 +303,34 @@ def delta_hstu_mha_limit(H: int, Da: int, Dv: int, max_seq_len: int, delta: int,
 def delta_hstu_mha_ok(max_seq_len: int, delta_q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_offsets: torch.Tensor,
                       num_targets: Optional[torch.Tensor] = None, max_attn_len: int = 0, contextual_seq_len: int = 0,
                       delta_k: Optional[torch.Tensor] = None, delta_v: Optional[torch.Tensor] = None) -> bool:
-    """what tzr_hstu_delta_fwd takes: delta_q [B delta, H, Da], k [Nc, H, Da], v [Nc, H, Dv] and, both or neither, delta_k [B delta, H,
-    Da], delta_v [B delta, H, Dv], all fp32 `_lib.heads_ok` operands (column slices of a uvqk matrix are fine), offsets int64 [B + 1]
-    and num_targets int64 [B] contiguous, a shape inside `delta_hstu_mha_limit`, everything on the device of the loaded library"""
+    """what tzr_hstu_delta_fwd / tzr_hstu_delta_bf16_fwd takes: delta_q [B delta, H, Da], k [Nc, H, Da], v [Nc, H, Dv] and, both or
+    neither, delta_k [B delta, H, Da], delta_v [B delta, H, Dv], all of ONE dtype, fp32 as `_lib.heads_ok` operands or bf16 as
+    `_lib.heads_bf16_ok` operands (column slices of a uvqk matrix are fine), offsets int64 [B + 1] and num_targets int64 [B]
+    contiguous, a shape inside `delta_hstu_mha_limit` for that dtype, everything on the device of the loaded library"""
     if delta_q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape[1:] != delta_q.shape[1:] or v.shape[:2] != k.shape[:2] or seq_offsets.dim() != 1:
         return False
     dev, (Ld, H, Da), Dv, B = delta_q.device, delta_q.shape, v.shape[2], seq_offsets.numel() - 1
     if (delta_k is None) != (delta_v is None) or B < 0 or (B == 0 and Ld > 0) or (B > 0 and (Ld == 0 or Ld % B)):
         return False  # (no sample, yet rows: the entry point launches nothing, so nobody would write the rows)
     rest = [t for t in (k, v, delta_k, delta_v) if t is not None]
-    if not _lib.takes(delta_q) or any(t.device != dev or t.dtype != torch.float32 for t in (delta_q, *rest)) or seq_offsets.device != dev or k.shape[0] >= 2 ** 31:
+    dtype = delta_q.dtype
+    if not _lib.takes(delta_q) or dtype not in (torch.float32, torch.bfloat16) or any(t.device != dev or t.dtype != dtype for t in rest) or \
+            seq_offsets.device != dev or k.shape[0] >= 2 ** 31:
         return False
     if delta_k is not None and (delta_k.shape != delta_q.shape or delta_v.shape != (Ld, H, Dv)):
         return False
-    if delta_hstu_mha_limit(H, Da, Dv, max_seq_len, Ld // B if B else 1, max_attn_len, contextual_seq_len, B) is not None:
+    if delta_hstu_mha_limit(H, Da, Dv, max_seq_len, Ld // B if B else 1, max_attn_len, contextual_seq_len, B, dtype) is not None:
         return False
     if seq_offsets.dtype != torch.int64 or not seq_offsets.is_contiguous():
         return False
     if num_targets is not None and not (num_targets.shape == (B,) and num_targets.dtype == torch.int64 and num_targets.is_contiguous() and num_targets.device == dev):
         return False
-    return all(t.shape[0] == 0 or _lib.heads_ok(t) for t in (delta_q, *rest))
+    return all(t.shape[0] == 0 or _heads_ok(t) for t in (delta_q, *rest))
 
 
 class _HstuDeltaFn:
-    """tzr_hstu_delta_fwd on operands `delta_hstu_mha_ok` took.  Forward only: no autograd node (an input that needs a gradient
-    takes the literal form).  Capturable: every buffer is torch's, the workspace included; nothing is read back."""
+    """tzr_hstu_delta_fwd, or tzr_hstu_delta_bf16_fwd for bf16, on operands `delta_hstu_mha_ok` took -> out in their dtype.  Forward
+    only: no autograd node (an input that needs a gradient takes the literal form).  Capturable: every buffer is torch's, the workspace included; nothing is read back."""
 
     calls = 0  # calls that took the kernel (tests)
 
@@ -325,7 +339,7 @@ class _HstuDeltaFn:
         _HstuDeltaFn.calls += 1
         max_seq_len, alpha, max_attn_len, contextual_seq_len, scaling_seqlen = cfg
         (Ld, H, Da), Dv, B = delta_q.shape, v.shape[2], seq_offsets.numel() - 1
-        out = torch.empty(Ld, H, Dv, dtype=torch.float32, device=delta_q.device)  # (the kernels write every row)
+        out = torch.empty(Ld, H, Dv, dtype=delta_q.dtype, device=delta_q.device)  # (the kernels write every row)
         if B == 0:
             return out
         m = _lib.TzrHstuDelta()
@@ -335,7 +349,8 @@ class _HstuDeltaFn:
         _operands(m, delta_q=delta_q.detach(), k=k.detach(), v=v.detach(), out=out)
         if delta_k is not None:
             _operands(m, k_delta=delta_k.detach(), v_delta=delta_v.detach())
-        _lib.launch_ws("tzr_hstu_delta", m, delta_q.device, "tzr_hstu_delta_fwd")
+        # (one workspace symbol for both entries: the chunks' partials are fp32 either way)
+        _lib.launch_ws("tzr_hstu_delta", m, delta_q.device, "tzr_hstu_delta_bf16_fwd" if delta_q.dtype == torch.bfloat16 else "tzr_hstu_delta_fwd")
         return out
 
 
@@ -347,11 +362,13 @@ def delta_hstu_mha(max_seq_len: int, alpha: float, delta_q: torch.Tensor, k: tor
     FULL sequences (the reference's meaning: their last delta rows are the delta keys).  With them, k, v, seq_offsets are the cached
     rows alone and delta_k [B delta, H, Da], delta_v [B delta, H, Dv] follow them: the kernel reads both segments where they lie.
     max_seq_len counts cache + delta in both forms; a sample above it (or, in the one-segment form, shorter than delta) gets zero
-    rows.  The kernel (csrc/hstu_delta.hip) is forward only: with FUSED_HSTU_DELTA off, an input that needs a gradient, a dtype
-    other than fp32 or a shape outside `delta_hstu_mha_limit`, the literal form runs."""
+    rows.  The kernels (csrc/hstu_delta.hip for fp32, csrc/hstu_delta_bf16.hip for bf16 with FUSED_HSTU_DELTA_BF16 on as well) are
+    forward only: with FUSED_HSTU_DELTA off, an input that needs a gradient, mixed dtypes, a dtype other than fp32 and bf16 or a
+    shape outside `delta_hstu_mha_limit`, the literal form runs."""
     max_seq_len, max_attn_len, contextual_seq_len, scaling_seqlen = int(max_seq_len), int(max_attn_len), int(contextual_seq_len), int(scaling_seqlen)
     given = [t for t in (delta_q, k, v, delta_k, delta_v) if t is not None]
-    if FUSED_HSTU_DELTA and (delta_q.is_cuda or _lib.emulated()) and delta_q.dtype == torch.float32 and \
+    if FUSED_HSTU_DELTA and (delta_q.is_cuda or _lib.emulated()) and \
+            (delta_q.dtype == torch.float32 or (delta_q.dtype == torch.bfloat16 and FUSED_HSTU_DELTA_BF16)) and \
             not (torch.is_grad_enabled() and any(t.requires_grad for t in given)) and \
             delta_hstu_mha_ok(max_seq_len, delta_q, k, v, seq_offsets, num_targets, max_attn_len, contextual_seq_len, delta_k, delta_v):
         return _HstuDeltaFn.apply(delta_q, k, v, seq_offsets, num_targets, delta_k, delta_v,
