@@ -1165,6 +1165,77 @@ int tzr_hstu_delta_fwd(const TzrHstuDelta* h_dl, void* stream);
  *   version stays 15. */
 int tzr_hstu_delta_bf16_fwd(const TzrHstuDelta* h_dl, void* stream);
 
+/* HSTU's positional and timestamp encoder in front of the STU stack (tzrec/modules/gr/positional_encoder.py on
+ * tzrec/ops/position.py: add_positional_embeddings, add_timestamp_positional_embeddings), on the jagged rows where they lie
+ * (csrc/hstu_position.hip): nothing of size [B, max_seq_len, .] is in memory.
+ *   x, out, grad_out, dx [L, E] by pointer + ELEMENTS between rows (unit column stride: a column slice of a wider matrix passes);
+ *   pos [P, E] and, with use_time, ts [T + 1, E] contiguous; offsets [B + 1], num_targets [B] (nullable), timestamps [L],
+ *   query_time [B] (nullable) int64.  bf16 == 0: x, the tables and every output are fp32; bf16 != 0: all of them bf16, every sum
+ *   in fp32 and every output rounded once, to nearest even, at its store.
+ *   The rule.  Sample b owns the rows [offsets[b], offsets[b + 1]) (offsets clamped into [0, L], an end not in front of its
+ *   start); n = its row count, t = num_targets[b] (0 when not given), t2 = interleave_targets ? 2 t : t, c = contextual_seq_len,
+ *   i = a row's position in its sample.  A row with i >= max_seq_len, and a row outside [offsets[0], offsets[B]), gets
+ *   out = alpha x and adds to neither table's gradient.  Every other row:
+ *     use_time == 0 (positional):  high = min(n - t2, P - 1);  idx = max(min(i, high), 0)  (the reference fails at high < 0);
+ *                                  out = alpha x + pos[idx].
+ *     use_time != 0 (timestamp):   high = n - t2;  idx = min(high - min(i, high) + c, P - 1), then idx = i for i < c;
+ *                                  gap = query_time[b] - timestamps[row] in int64 (wrapping); query_time[b] defaults to the
+ *                                  timestamp of the sample's last row, offsets[b + 1] - 1, whatever max_seq_len is; in fp32:
+ *                                  u = max((float)gap, 1e-6f) / time_bucket_increments;  u = time_fn == 0 ? sqrt(u) : log(u)
+ *                                  (division and sqrt correctly rounded);  bucket = (int)(min(max(u / T, 0), 1) * T);
+ *                                  out = alpha x + (pos[idx] + ts[bucket]).
+ *   forward, one launch: a workgroup owns TZR_HSTU_POS_SLAB consecutive rows, finds each row's sample by bisection of the
+ *     offsets, computes idx and bucket once a row and streams x and the two table rows in 16-byte pieces; with use_time it stores
+ *     bucket [L] int32 (-1 for a row that gets alpha x only) for the backward.
+ *   backward from g = grad_out: dx = alpha g; dpos [P, E] and dts [T + 1, E] are fixed-order sums, every row of both written
+ *     (a row nobody maps to: zeros).  Launches: (1) the row pass, a workgroup a slab: dx, the slab's rows ranked by (bucket,
+ *     row) in LDS and one fp32 partial row per distinct bucket with the slab's sorted keys, and one partial per HOT position row
+ *     (timestamp: idx == c, every target, and idx == P - 1, the clamped head; positional: P - 1), all into `ws`; (2) the position
+ *     gather, a workgroup a table row that is not hot: the index rule inverted per sample gives one row, or one run of rows, of
+ *     g; the samples are split over the workgroup's column groups and added in group order; (3) the hot rows' partials added
+ *     in the interleaved order of csrc/parts_sum.h; (4) with use_time, a workgroup a bucket: walks the slabs in order, finds its
+ *     bucket in each slab's keys and adds that partial.  No atomics on floats, no scratch: two runs are bit-equal.  Nothing is
+ *     read back on the host.  The backward reads offsets, num_targets and bucket, never timestamps or x.
+ * Order of the checks: a null struct, L, B or contextual_seq_len < 0, time_bucket_increments not > 0 with use_time, time_fn
+ *   outside {0, 1} (TZR_ERR_INVALID); the limits (TZR_ERR_UNSUPPORTED): E a multiple of 4 (fp32) or 8 (bf16) in [that,
+ *   TZR_HSTU_POS_MAX_DIM], P >= 1, with use_time 1 <= T <= TZR_HSTU_POS_MAX_BUCKETS and contextual_seq_len <= P (the reference
+ *   indexes behind the table there), 1 <= max_seq_len <= TZR_HSTU_MAX_SEQ_LEN, L and B < 2^31; then pointers (null or misaligned
+ *   -- rows and tables 16 bytes, int64 operands 8, bucket 4: TZR_ERR_INVALID; the row operands, timestamps and bucket only when
+ *   L > 0, offsets only when B > 0) and row strides (no multiple of 4 / 8 elements, or below E: TZR_ERR_UNSUPPORTED); backward:
+ *   ws null, not 256-byte aligned or below tzr_hstu_pos_bwd_workspace: TZR_ERR_WORKSPACE.  L == 0: the forward is TZR_OK without
+ *   a launch; the backward still writes both tables (zeros).  A refused call launches nothing.  A new struct and entry points, no
+ *   change to existing ones: the ABI version stays 15. */
+#define TZR_HSTU_POS_MAX_DIM 512
+#define TZR_HSTU_POS_MAX_BUCKETS 16777216
+#define TZR_HSTU_POS_SLAB 64
+typedef struct TzrHstuPos {
+  int64_t L, B;
+  int32_t E, P, T, max_seq_len, contextual_seq_len, use_time, interleave_targets, time_fn, bf16, reserved;
+  float alpha, time_bucket_increments;
+  uint64_t x;                        /* const [L, E]              (forward) */
+  int64_t x_stride;
+  uint64_t pos;                      /* const [P, E]              (forward) */
+  uint64_t ts;                       /* const [T + 1, E]          (forward, use_time) */
+  uint64_t offsets;                  /* const int64_t* [B + 1] */
+  uint64_t num_targets;              /* const int64_t* [B], nullable */
+  uint64_t timestamps;               /* const int64_t* [L]        (forward, use_time) */
+  uint64_t query_time;               /* const int64_t* [B], nullable (forward, use_time) */
+  uint64_t out;                      /* [L, E]                    (forward writes) */
+  int64_t out_stride;
+  uint64_t bucket;                   /* int32_t* [L]              (use_time: forward writes, backward reads) */
+  uint64_t grad_out;                 /* const [L, E]              (backward) */
+  int64_t grad_out_stride;
+  uint64_t dx;                       /* [L, E]                    (backward) */
+  int64_t dx_stride;
+  uint64_t dpos;                     /* [P, E]                    (backward) */
+  uint64_t dts;                      /* [T + 1, E]                (backward, use_time) */
+  uint64_t ws;                       /* workspace                 (backward) */
+  uint64_t ws_bytes;
+} TzrHstuPos;
+int tzr_hstu_pos_fwd(const TzrHstuPos* h_po, void* stream);
+size_t tzr_hstu_pos_bwd_workspace(const TzrHstuPos* h_po);
+int tzr_hstu_pos_bwd(const TzrHstuPos* h_po, void* stream);
+
 /* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
  * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
  *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied

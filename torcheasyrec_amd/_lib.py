@@ -262,6 +262,23 @@ class TzrHstuDelta(C.Structure):
 
 
 assert C.sizeof(TzrHstuDelta) == 232
+# limits and rows per workgroup of tzr_hstu_pos_* (include/tzrec_hip.h: TZR_HSTU_POS_*)
+HSTU_POS_MAX_DIM, HSTU_POS_MAX_BUCKETS, HSTU_POS_SLAB = 512, 16777216, 64
+
+
+class TzrHstuPos(C.Structure):
+    _fields_ = [
+        ("L", C.c_int64), ("B", C.c_int64), ("E", C.c_int32), ("P", C.c_int32), ("T", C.c_int32), ("max_seq_len", C.c_int32),
+        ("contextual_seq_len", C.c_int32), ("use_time", C.c_int32), ("interleave_targets", C.c_int32), ("time_fn", C.c_int32),
+        ("bf16", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_float), ("time_bucket_increments", C.c_float),
+        ("x", C.c_uint64), ("x_stride", C.c_int64), ("pos", C.c_uint64), ("ts", C.c_uint64), ("offsets", C.c_uint64),
+        ("num_targets", C.c_uint64), ("timestamps", C.c_uint64), ("query_time", C.c_uint64), ("out", C.c_uint64), ("out_stride", C.c_int64),
+        ("bucket", C.c_uint64), ("grad_out", C.c_uint64), ("grad_out_stride", C.c_int64), ("dx", C.c_uint64), ("dx_stride", C.c_int64),
+        ("dpos", C.c_uint64), ("dts", C.c_uint64), ("ws", C.c_uint64), ("ws_bytes", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrHstuPos) == 216
 # limit and rows per workgroup of tzr_stu_output_* (include/tzrec_hip.h: TZR_STU_OUT_*)
 STU_OUT_MAX_DIM, STU_OUT_BLOCK = 512, 32
 
@@ -534,6 +551,9 @@ _SIGNATURES = {
     "tzr_hstu_delta_workspace": (_sz, [_vp]),
     "tzr_hstu_delta_fwd": (_i32, [_vp, _vp]),
     "tzr_hstu_delta_bf16_fwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_pos_fwd": (_i32, [_vp, _vp]),
+    "tzr_hstu_pos_bwd_workspace": (_sz, [_vp]),
+    "tzr_hstu_pos_bwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
     "tzr_stu_output_bwd": (_i32, [_vp, _vp]),

@@ -22,7 +22,14 @@ the attention's rows, their product, the concat [u, attn, y], dropout and addmm(
 (tzr_stu_output_fwd / _bwd: one launch forward, two backward and a finishing one; the concat, the normed rows and the dropout
 mask are never in memory, the mask follows the counter rule of include/tzrec_hip.h from a seed on the device) when
 FUSED_STU_OUTPUT is on and `stu_output_ok` takes the operands; otherwise `stu_output_literal`, the torch ops.  What stays torch ops
-in the layer: the input norm and the uvqk product in front of the attention."""
+in the layer: the input norm and the uvqk product in front of the attention.
+
+`add_positional_embeddings`, `add_timestamp_positional_embeddings` and `HSTUPositionalEncoder` are the encoder in front of the stack
+(tzrec/ops/position.py, tzrec/modules/gr/positional_encoder.py): alpha x plus a row of the position table and, in the timestamp
+form, a row of the time-bucket table, on the jagged rows.  With FUSED_HSTU_POSITION on and `hstu_position_ok` taking the operands
+they run csrc/hstu_position.hip (tzr_hstu_pos_fwd / _bwd, fp32 and bf16: one launch forward; backward dx and the two table
+gradients as fixed-order sums, no atomics, the rows' int32 buckets the only thing saved beside the integer inputs); otherwise
+-- mixed dtypes, fp16, a shape outside `hstu_position_limit`, a double backward -- the literal padded form out of torch ops."""
 from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple
@@ -40,6 +47,9 @@ FUSED_HSTU_DELTA = True  # profiles/hstu_delta, one serving step: 95.1 us fused 
 # bf16 operands on csrc/hstu_delta_bf16.hip (needs FUSED_HSTU_DELTA too); profiles/hstu_delta_bf16, the same step: 54.7 us fused (54.5 - 63.5)
 # against 634.7 us for the literal form in bf16 (618.4 - 697.2) and 102.3 us for the fp32 kernel, 9.2 against 127.0 MB
 FUSED_HSTU_DELTA_BF16 = True
+# profiles/hstu_position, forward + backward at 38 866 rows, E = 512: fp32 203.2 us fused (201.1 - 538.7) against 25.7 ms literal (25.5 - 26.8),
+# 263 against 485 MB; bf16 166.5 us fused (164.4 - 169.3) against 50.3 ms literal (49.6 - 54.6), 173 against 243 MB: on for both dtypes
+FUSED_HSTU_POSITION = True
 
 
 def hstu_valid_mask(n: torch.Tensor, N: int, num_targets: Optional[torch.Tensor], max_attn_len: int, contextual_seq_len: int,
@@ -633,3 +643,239 @@ class STUStack(nn.Module):
         for layer in self._stu_layers:
             delta_x = layer.cached_forward(delta_x, num_targets, max_kv_caching_len, kv_caching_lengths)
         return delta_x
+
+
+# ---- the positional and timestamp encoder in front of the stack ---------------------------------------------------------------
+_TIME_FNS = ("sqrt", "log")
+
+
+def _position_literal(alpha, max_seq_len, c, pos_w, ts_w, seq_offsets, seq_embeddings, timestamps, num_targets, interleave_targets,
+                      time_bucket_fn, time_bucket_increments, query_time):
+    """Both reference ops out of plain torch ops (ts_w None: the positional one): the index matrices [B, N] of
+    pt_position.py, two gathers [B, N, E], and their sum added to alpha x on the rows a sample keeps.  Padded as `hstu_mha_literal`
+    pads; rows at or behind max_seq_len and rows no sample owns get alpha x alone."""
+    L, B, N, dev = seq_embeddings.shape[0], seq_offsets.numel() - 1, int(max_seq_len), seq_embeddings.device
+    out = seq_embeddings * alpha
+    if B <= 0 or L == 0:
+        return out
+    n = seq_offsets[1:] - seq_offsets[:-1]
+    col = torch.arange(N, device=dev).view(1, N).expand(B, N)
+    keep = col < n.view(-1, 1)
+    rows = (seq_offsets[:-1].view(-1, 1) + col) % (L + 1)
+    high = n if num_targets is None else n - num_targets * (2 if interleave_targets else 1)
+    P = pos_w.shape[0]
+    if ts_w is None:
+        high = torch.clamp(high, max=P - 1).view(-1, 1)
+        dense = pos_w[torch.minimum(col, high).clamp(min=0)]
+    else:
+        high = high.view(-1, 1)
+        idx = torch.clamp(high - torch.minimum(col, high) + c, max=P - 1)
+        idx = torch.where(col < c, col, idx)
+        T = ts_w.shape[0] - 1
+        tm = torch.cat([timestamps, timestamps.new_zeros(1)])[rows]
+        qt = timestamps[(seq_offsets[1:] - 1).clamp(0, L - 1)] if query_time is None else query_time.to(timestamps.dtype)
+        u = (qt.view(-1, 1) - tm).clamp(min=1e-6) / time_bucket_increments
+        u = torch.log(u) if time_bucket_fn == "log" else torch.sqrt(u)
+        bucket = ((u / T).clamp(min=0, max=1) * T).int()
+        dense = ts_w[bucket] + pos_w[idx]
+    return out.index_put((rows[keep],), dense[keep].to(out.dtype), accumulate=True)
+
+
+def add_positional_embeddings_literal(alpha: float, max_seq_len: int, position_embeddings_weight: torch.Tensor, seq_offsets: torch.Tensor,
+                                      seq_lengths: Optional[torch.Tensor], seq_embeddings: torch.Tensor, num_targets: Optional[torch.Tensor],
+                                      interleave_targets: bool) -> torch.Tensor:
+    """pytorch_add_position_embeddings out of plain torch ops (no fbgemm)"""
+    return _position_literal(alpha, max_seq_len, 0, position_embeddings_weight, None, seq_offsets, seq_embeddings, None, num_targets,
+                             interleave_targets, "sqrt", 1.0, None)
+
+
+def add_timestamp_positional_embeddings_literal(alpha: float, max_seq_len: int, max_contextual_seq_len: int, position_embeddings_weight: torch.Tensor,
+                                                timestamp_embeddings_weight: torch.Tensor, seq_offsets: torch.Tensor,
+                                                seq_lengths: Optional[torch.Tensor], seq_embeddings: torch.Tensor, timestamps: torch.Tensor,
+                                                num_targets: Optional[torch.Tensor], interleave_targets: bool, time_bucket_fn: str = "sqrt",
+                                                time_bucket_increments: float = 60.0, query_time: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pytorch_add_timestamp_positional_embeddings behind `seq_embeddings * alpha`, out of plain torch ops (no fbgemm)"""
+    return _position_literal(alpha, max_seq_len, int(max_contextual_seq_len), position_embeddings_weight, timestamp_embeddings_weight, seq_offsets,
+                             seq_embeddings, timestamps, num_targets, interleave_targets, time_bucket_fn, time_bucket_increments, query_time)
+
+
+def hstu_position_limit(E: int, P: int, max_seq_len: int, T: Optional[int] = None, contextual_seq_len: int = 0,
+                        dtype: torch.dtype = torch.float32) -> Optional[str]:
+    """None when tzr_hstu_pos_* has a kernel for the shape (T None: the positional op), else the limit of csrc/hstu_position.hip it
+    misses (include/tzrec_hip.h)"""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return f"dtype {dtype} must be float32 or bfloat16"
+    step, D = 8 if dtype == torch.bfloat16 else 4, _lib.HSTU_POS_MAX_DIM
+    if E % step or not step <= E <= D:
+        return f"embedding_dim {E} must be a multiple of {step} in [{step}, {D}]"
+    if P < 1:
+        return f"position buckets {P} must be at least 1"
+    if not 1 <= max_seq_len <= _lib.HSTU_MAX_SEQ_LEN:
+        return f"max_seq_len {max_seq_len} must be in [1, {_lib.HSTU_MAX_SEQ_LEN}]"
+    if T is not None and not 1 <= T <= _lib.HSTU_POS_MAX_BUCKETS:
+        return f"time buckets {T} must be in [1, {_lib.HSTU_POS_MAX_BUCKETS}]"
+    if T is not None and not 0 <= contextual_seq_len <= P:
+        return f"max_contextual_seq_len {contextual_seq_len} must be in [0, {P}] (the position buckets)"
+    return None
+
+
+def _rows16_ok(t: torch.Tensor) -> bool:
+    """[L, E] fp32 or bf16 whose rows the 16-byte accesses take: unit column stride, rows a multiple of 16 bytes and a whole width
+    apart, 16-byte aligned data (a column slice of a wider matrix passes)"""
+    step = 8 if t.dtype == torch.bfloat16 else 4
+    stride = _lib.scalar_row_stride(t)
+    return t.stride(1) == 1 and stride % step == 0 and stride >= t.shape[1] and t.data_ptr() % 16 == 0
+
+
+def _int64_ok(t: Optional[torch.Tensor], shape: tuple, dev: torch.device) -> bool:
+    return t is None or (t.shape == shape and t.dtype == torch.int64 and t.is_contiguous() and t.device == dev)
+
+
+def hstu_position_ok(max_seq_len: int, position_embeddings_weight: torch.Tensor, seq_offsets: torch.Tensor, seq_embeddings: torch.Tensor,
+                     num_targets: Optional[torch.Tensor] = None, timestamp_embeddings_weight: Optional[torch.Tensor] = None,
+                     timestamps: Optional[torch.Tensor] = None, query_time: Optional[torch.Tensor] = None, max_contextual_seq_len: int = 0,
+                     time_bucket_fn: str = "sqrt", time_bucket_increments: float = 60.0) -> bool:
+    """what tzr_hstu_pos_* takes: seq_embeddings [L, E] and the tables [P, E], [T + 1, E] (contiguous) of ONE dtype, fp32 or bf16,
+    the rows as `_rows16_ok` takes them; offsets [B + 1], num_targets [B], timestamps [L], query_time [B] int64 and contiguous; a
+    shape inside `hstu_position_limit`; everything on the device of the loaded library"""
+    x, pw, tw = seq_embeddings, position_embeddings_weight, timestamp_embeddings_weight
+    if x.dim() != 2 or pw.dim() != 2 or pw.shape[1] != x.shape[1] or seq_offsets.dim() != 1 or seq_offsets.numel() < 1 or x.shape[0] >= 2 ** 31:
+        return False
+    dev, (L, E), B = x.device, x.shape, seq_offsets.numel() - 1
+    if not _lib.takes(x) or pw.dtype != x.dtype or pw.device != dev or not pw.is_contiguous() or pw.data_ptr() % 16:
+        return False
+    if tw is not None:
+        if tw.dim() != 2 or tw.shape[1] != E or tw.shape[0] < 2 or tw.dtype != x.dtype or tw.device != dev or not tw.is_contiguous() or tw.data_ptr() % 16:
+            return False
+        if timestamps is None or not _int64_ok(timestamps, (L,), dev) or not _int64_ok(query_time, (B,), dev):
+            return False
+        if time_bucket_fn not in _TIME_FNS or not time_bucket_increments > 0:
+            return False
+    if hstu_position_limit(E, pw.shape[0], max_seq_len, None if tw is None else tw.shape[0] - 1, max_contextual_seq_len, x.dtype) is not None:
+        return False
+    if not _int64_ok(seq_offsets, (B + 1,), dev) or not _int64_ok(num_targets, (B,), dev):
+        return False
+    return L == 0 or _rows16_ok(x)
+
+
+def _pos_fill(m, cfg, dtype, E, P, T, seq_offsets, num_targets, bucket):
+    max_seq_len, alpha, c, interleave, fn, incr = cfg
+    m.B, m.E, m.P, m.T, m.max_seq_len, m.contextual_seq_len = seq_offsets.numel() - 1, E, P, T or 0, max_seq_len, c
+    m.use_time, m.interleave_targets, m.time_fn, m.bf16 = int(T is not None), int(interleave), fn, int(dtype == torch.bfloat16)
+    m.alpha, m.time_bucket_increments = alpha, incr
+    m.offsets, m.num_targets, m.bucket = _lib.ptr(seq_offsets), _lib.opt_ptr(num_targets), _lib.opt_ptr(bucket)
+
+
+def hstu_pos_fwd(x, pos_w, ts_w, seq_offsets, num_targets, timestamps, query_time, cfg) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """tzr_hstu_pos_fwd on operands `hstu_position_ok` took -> out [L, E] (the kernel writes every row) and, with a timestamp
+    table, the rows' buckets int32 [L]"""
+    (L, E), dev = x.shape, x.device
+    out = torch.empty(L, E, dtype=x.dtype, device=dev)
+    bucket = None if ts_w is None else torch.empty(L, dtype=torch.int32, device=dev)
+    if L > 0:
+        m = _lib.TzrHstuPos()
+        _pos_fill(m, cfg, x.dtype, E, pos_w.shape[0], None if ts_w is None else ts_w.shape[0] - 1, seq_offsets, num_targets, bucket)
+        m.L, m.x, m.x_stride, m.out, m.out_stride = L, _lib.ptr(x), _lib.scalar_row_stride(x), _lib.ptr(out), E
+        m.pos, m.ts, m.timestamps, m.query_time = _lib.ptr(pos_w), _lib.opt_ptr(ts_w), _lib.opt_ptr(timestamps), _lib.opt_ptr(query_time)
+        _lib.launch("tzr_hstu_pos_fwd", m, dev)
+    return out, bucket
+
+
+def hstu_pos_bwd(gout, dtype, P, T, seq_offsets, num_targets, bucket, cfg):
+    """tzr_hstu_pos_bwd -> dx [L, E], dpos [P, E], dts [T + 1, E] or None; every element written by the kernels"""
+    (L, E), dev = gout.shape, gout.device
+    g = gout.to(dtype)
+    if L > 0 and not _rows16_ok(g):
+        g = g.clone(memory_format=torch.contiguous_format)
+    dx, dpos = torch.empty(L, E, dtype=dtype, device=dev), torch.empty(P, E, dtype=dtype, device=dev)
+    dts = None if T is None else torch.empty(T + 1, E, dtype=dtype, device=dev)
+    m = _lib.TzrHstuPos()
+    _pos_fill(m, cfg, dtype, E, P, T, seq_offsets, num_targets, bucket if L > 0 else None)
+    m.L, m.dpos, m.dts = L, _lib.ptr(dpos), _lib.opt_ptr(dts)
+    if L > 0:
+        m.grad_out, m.grad_out_stride, m.dx, m.dx_stride = _lib.ptr(g), _lib.scalar_row_stride(g), _lib.ptr(dx), E
+    _lib.launch_ws("tzr_hstu_pos_bwd", m, dev, "tzr_hstu_pos_bwd")
+    return dx, dpos, dts
+
+
+class _HstuPositionFn(torch.autograd.Function):
+    """Saved for the backward: the offsets, num_targets and the int32 buckets -- no row of x, no timestamp.  Capturable: every
+    buffer is torch's, the workspace included; nothing is read back.  Differentiable once (a double backward takes the literal form)."""
+
+    calls = 0  # forwards that took the kernel (tests)
+
+    @staticmethod
+    def forward(ctx, x, pos_w, ts_w, seq_offsets, num_targets, timestamps, query_time, cfg):
+        _HstuPositionFn.calls += 1
+        out, bucket = hstu_pos_fwd(x.detach(), pos_w.detach(), None if ts_w is None else ts_w.detach(), seq_offsets, num_targets, timestamps, query_time, cfg)
+        ctx.save_for_backward(seq_offsets, num_targets, bucket)
+        ctx.cfg, ctx.shape = cfg, (x.dtype, pos_w.shape[0], None if ts_w is None else ts_w.shape[0] - 1)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        dx, dpos, dts = hstu_pos_bwd(gout, *ctx.shape, *ctx.saved_tensors, ctx.cfg)
+        return dx, dpos, dts, None, None, None, None, None
+
+
+def _position(alpha, max_seq_len, c, pos_w, ts_w, seq_offsets, x, timestamps, num_targets, interleave_targets, time_bucket_fn,
+              time_bucket_increments, query_time, double_backward):
+    max_seq_len, c = int(max_seq_len), int(c)
+    if FUSED_HSTU_POSITION and not double_backward and (x.is_cuda or _lib.emulated()) and \
+            hstu_position_ok(max_seq_len, pos_w, seq_offsets, x, num_targets, ts_w, timestamps, query_time, c, time_bucket_fn, time_bucket_increments):
+        cfg = (max_seq_len, float(alpha), c, bool(interleave_targets), _TIME_FNS.index(time_bucket_fn), float(time_bucket_increments))
+        return _HstuPositionFn.apply(x, pos_w, ts_w, seq_offsets, num_targets, timestamps, query_time, cfg)
+    return _position_literal(alpha, max_seq_len, c, pos_w, ts_w, seq_offsets, x, timestamps, num_targets, interleave_targets, time_bucket_fn,
+                             time_bucket_increments, query_time)
+
+
+def add_positional_embeddings(alpha: float, max_seq_len: int, position_embeddings_weight: torch.Tensor, seq_offsets: torch.Tensor,
+                              seq_lengths: Optional[torch.Tensor], seq_embeddings: torch.Tensor, num_targets: Optional[torch.Tensor],
+                              interleave_targets: bool, double_backward: bool = False) -> torch.Tensor:
+    """The reference's add_positional_embeddings: row i of a sample with n rows gets alpha x + pos[min(i, high)], high =
+    min(n - num_targets (twice under interleave_targets), P - 1); [L, E] -> [L, E].  `seq_lengths` is accepted; the offsets are
+    what is read.  Rows at or behind max_seq_len of a sample get alpha x alone."""
+    return _position(alpha, max_seq_len, 0, position_embeddings_weight, None, seq_offsets, seq_embeddings, None, num_targets, interleave_targets,
+                     "sqrt", 1.0, None, double_backward)
+
+
+def add_timestamp_positional_embeddings(alpha: float, max_seq_len: int, max_contextual_seq_len: int, position_embeddings_weight: torch.Tensor,
+                                        timestamp_embeddings_weight: torch.Tensor, seq_offsets: torch.Tensor, seq_lengths: Optional[torch.Tensor],
+                                        seq_embeddings: torch.Tensor, timestamps: torch.Tensor, num_targets: Optional[torch.Tensor],
+                                        interleave_targets: bool, time_bucket_fn: str = "sqrt", time_bucket_increments: float = 60.0,
+                                        query_time: Optional[torch.Tensor] = None, double_backward: bool = False) -> torch.Tensor:
+    """The reference's add_timestamp_positional_embeddings: alpha x + pos[idx] + ts[bucket] by the rule of include/tzrec_hip.h (the
+    position counted back from the first target, the contextual prefix on its own rows; the bucket from the gap to `query_time`,
+    by default the timestamp of the sample's last row).  On csrc/hstu_position.hip when FUSED_HSTU_POSITION is on and
+    `hstu_position_ok` takes the operands, else the literal form."""
+    if time_bucket_fn not in _TIME_FNS:
+        raise ValueError(f"time_bucket_fn {time_bucket_fn!r} must be one of {_TIME_FNS}")
+    return _position(alpha, max_seq_len, max_contextual_seq_len, position_embeddings_weight, timestamp_embeddings_weight, seq_offsets, seq_embeddings,
+                     timestamps, num_targets, interleave_targets, time_bucket_fn, time_bucket_increments, query_time, double_backward)
+
+
+class HSTUPositionalEncoder(nn.Module):
+    """The reference's HSTUPositionalEncoder (constructor arguments, parameter names and initialisation): `_position_embeddings_weight`
+    [num_position_buckets, E] and, with use_time_encoding, `_timestamp_embeddings_weight` [num_time_buckets + 1, E], added to
+    sqrt(E) x by `add_timestamp_positional_embeddings` / `add_positional_embeddings`."""
+
+    def __init__(self, embedding_dim: int, num_position_buckets: int, num_time_buckets: int = 0, use_time_encoding: bool = False,
+                 contextual_seq_len: int = 0, time_bucket_fn: str = "sqrt", time_bucket_increments: float = 60.0, is_inference: bool = True) -> None:
+        super().__init__()
+        self._use_time_encoding, self._contextual_seq_len, self._embedding_dim = use_time_encoding, contextual_seq_len, embedding_dim
+        bound = (1.0 / num_position_buckets) ** 0.5
+        self._position_embeddings_weight = nn.Parameter(torch.empty(num_position_buckets, embedding_dim).uniform_(-bound, bound))
+        if use_time_encoding:
+            bound = (1.0 / num_time_buckets) ** 0.5
+            self._timestamp_embeddings_weight = nn.Parameter(torch.empty(num_time_buckets + 1, embedding_dim).uniform_(-bound, bound))
+            self._time_bucket_fn, self._time_bucket_increments = time_bucket_fn, time_bucket_increments
+
+    def forward(self, max_seq_len: int, seq_lengths: torch.Tensor, seq_offsets: torch.Tensor, seq_timestamps: torch.Tensor,
+                seq_embeddings: torch.Tensor, num_targets: Optional[torch.Tensor], query_time: Optional[torch.Tensor] = None) -> torch.Tensor:
+        alpha = self._embedding_dim ** 0.5
+        if self._use_time_encoding:
+            return add_timestamp_positional_embeddings(alpha, max_seq_len, self._contextual_seq_len, self._position_embeddings_weight,
+                                                       self._timestamp_embeddings_weight, seq_offsets, seq_lengths, seq_embeddings, seq_timestamps,
+                                                       num_targets, False, self._time_bucket_fn, self._time_bucket_increments, query_time)
+        return add_positional_embeddings(alpha, max_seq_len, self._position_embeddings_weight, seq_offsets, seq_lengths, seq_embeddings, num_targets, False)
