@@ -1236,6 +1236,52 @@ int tzr_hstu_pos_fwd(const TzrHstuPos* h_po, void* stream);
 size_t tzr_hstu_pos_bwd_workspace(const TzrHstuPos* h_po);
 int tzr_hstu_pos_bwd(const TzrHstuPos* h_po, void* stream);
 
+/* The jagged matmul with a weight matrix per sample under HSTU's parameterized contextual MLP
+ * (tzrec/modules/gr/contextualize_mlps.py on tzrec/ops/jagged_tensors.py::jagged_dense_bmm_broadcast_add), fp32, on the jagged
+ * rows where they lie (csrc/jagged_bmm.hip): nothing of size [B, max_seq_len, .] is in memory, the work follows the rows.
+ *     out[r] = jagged[r] dense[b] + bias[b]          for the rows r of sample b
+ *   jagged [L, K], out [L, N], grad_out [L, N], d_jagged [L, K] by pointer + FLOATS between rows (unit column stride: a column
+ *   slice of a wider matrix passes); dense, d_dense [B, K, N], bias, d_bias [B, N] contiguous; offsets [B + 1] int64.
+ *   Sample b owns the rows [offsets[b], offsets[b + 1]) (offsets clamped into [0, L], an end not in front of its start:
+ *   whatever the offsets hold, no access leaves the buffers) and keeps the first max_seq_len of them.  The rows it does not
+ *   keep, and the rows outside [offsets[0], offsets[B]), get zeros in out and d_jagged and add to neither d_dense nor d_bias.
+ *   forward, one launch: a workgroup of four waves owns TZR_JAGGED_BMM_BLOCK rows of one sample (a wave sixteen) and
+ *     TZR_JAGGED_BMM_CHUNK output columns; the product is computed transposed on v_mfma_f32_16x16x4_f32 (four accumulator
+ *     chains a 16 x 16 tile), dense[b]'s panel through LDS a step of sixteen k ahead, the rows straight into fragments.
+ *   backward from g = grad_out, two launches: d_jagged = g dense[b]^T by the forward's walk with K and N swapped;
+ *     d_dense[b] = jagged_b^T g_b and d_bias[b] = the column sums of g_b, a workgroup a (sample, 64 k, TZR_JAGGED_BMM_CHUNK n)
+ *     tile walking the sample's kept rows in order.  Every element of d_dense and d_bias is written (a sample that keeps no
+ *     row: zeros).  No atomics, no workspace, no scratch: every sum's order is a function of the shapes and the offsets alone,
+ *     two runs are bit-equal.  Nothing is read back on the host.
+ * Order of the checks: a null struct, L or B < 0, K or N no multiple of 4 in [4, TZR_JAGGED_BMM_MAX_DIM] (TZR_ERR_INVALID);
+ *   the limits (TZR_ERR_UNSUPPORTED): 1 <= max_seq_len <= TZR_HSTU_MAX_SEQ_LEN, L and B < 2^31, the grids below 2^31
+ *   workgroups; B == 0 or L == 0: TZR_OK without a launch, whatever the pointers are (the caller zeroes its outputs); then
+ *   pointers (null or misaligned -- rows, dense and bias 16 bytes, offsets 8: TZR_ERR_INVALID) and row strides (no multiple of
+ *   4 floats, or below the width: TZR_ERR_UNSUPPORTED).  A refused call launches nothing.  A new struct and entry points, no
+ *   change to existing ones: the ABI version stays 15. */
+#define TZR_JAGGED_BMM_MAX_DIM 512
+#define TZR_JAGGED_BMM_BLOCK 64
+#define TZR_JAGGED_BMM_CHUNK 128
+typedef struct TzrJaggedBmm {
+  int64_t L, B;
+  int32_t K, N, max_seq_len, reserved;
+  uint64_t jagged;                   /* const [L, K] */
+  int64_t jagged_stride;
+  uint64_t dense;                    /* const [B, K, N] */
+  uint64_t bias;                     /* const [B, N]              (forward) */
+  uint64_t offsets;                  /* const int64_t* [B + 1] */
+  uint64_t out;                      /* [L, N]                    (forward writes) */
+  int64_t out_stride;
+  uint64_t grad_out;                 /* const [L, N]              (backward) */
+  int64_t grad_out_stride;
+  uint64_t d_jagged;                 /* [L, K]                    (backward) */
+  int64_t d_jagged_stride;
+  uint64_t d_dense;                  /* [B, K, N]                 (backward) */
+  uint64_t d_bias;                   /* [B, N]                    (backward) */
+} TzrJaggedBmm;
+int tzr_jagged_bmm_fwd(const TzrJaggedBmm* h_jb, void* stream);
+int tzr_jagged_bmm_bwd(const TzrJaggedBmm* h_jb, void* stream);
+
 /* The output stage of an STU layer behind the attention (tzrec/modules/gr/stu.py; the reference's fused form is
  * tzrec/ops/hstu_compute.py::hstu_compute_output), fp32, W = H Dv, one launch forward, three backward:
  *     us = silu(u)                          u [L, W]: a column slice of the uvqk matrix, silu NOT yet applied

@@ -279,6 +279,20 @@ class TzrHstuPos(C.Structure):
 
 
 assert C.sizeof(TzrHstuPos) == 216
+# limit, rows and output columns per workgroup of tzr_jagged_bmm_* (include/tzrec_hip.h: TZR_JAGGED_BMM_*)
+JAGGED_BMM_MAX_DIM, JAGGED_BMM_BLOCK, JAGGED_BMM_CHUNK = 512, 64, 128
+
+
+class TzrJaggedBmm(C.Structure):
+    _fields_ = [
+        ("L", C.c_int64), ("B", C.c_int64), ("K", C.c_int32), ("N", C.c_int32), ("max_seq_len", C.c_int32), ("reserved", C.c_int32),
+        ("jagged", C.c_uint64), ("jagged_stride", C.c_int64), ("dense", C.c_uint64), ("bias", C.c_uint64), ("offsets", C.c_uint64),
+        ("out", C.c_uint64), ("out_stride", C.c_int64), ("grad_out", C.c_uint64), ("grad_out_stride", C.c_int64),
+        ("d_jagged", C.c_uint64), ("d_jagged_stride", C.c_int64), ("d_dense", C.c_uint64), ("d_bias", C.c_uint64),
+    ]
+
+
+assert C.sizeof(TzrJaggedBmm) == 136
 # limit and rows per workgroup of tzr_stu_output_* (include/tzrec_hip.h: TZR_STU_OUT_*)
 STU_OUT_MAX_DIM, STU_OUT_BLOCK = 512, 32
 
@@ -554,6 +568,8 @@ _SIGNATURES = {
     "tzr_hstu_pos_fwd": (_i32, [_vp, _vp]),
     "tzr_hstu_pos_bwd_workspace": (_sz, [_vp]),
     "tzr_hstu_pos_bwd": (_i32, [_vp, _vp]),
+    "tzr_jagged_bmm_fwd": (_i32, [_vp, _vp]),
+    "tzr_jagged_bmm_bwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_fwd": (_i32, [_vp, _vp]),
     "tzr_stu_output_bwd_workspace": (_sz, [_vp]),
     "tzr_stu_output_bwd": (_i32, [_vp, _vp]),
